@@ -12,6 +12,11 @@ settings, plane sizes 5/17/101/251/509/1021/2039/4093 m (extending src/Waves.cpp
 collective). The weak-scaling leg (8 cascades per GPU, seeds offset 4097*rank: disjoint noise tiles)
 is reported beside it under "weak_scaling".
 
+A plain run sets up, warms up, times the K steps, writes the last step's maps if --dump-outputs DIR is
+given, and prints the line. Every other leg (h0 seeding time, the bit-exact check, re-seed, one-cascade
+and weak scaling, EncodeIFFT / rocFFT, surface, the slab-decomposed grid and its 8-GPU projections,
+BASELINE configs 1-3, the CPU baseline) runs only with --full, where the --no-* switches take legs out.
+
 Launch: python bench.py [--gpus N --steps K --warmup W], one rank per GPU. Under torch.distributed.run
 (WORLD_SIZE set) the process is one rank. Started directly with --gpus N > 1, it first checks that N
 GPUs are visible, then starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a
@@ -75,6 +80,15 @@ def parse(argv=None):
     ap.add_argument("--n", type=int, default=4096, help="grid side N")
     ap.add_argument("--cascades", type=int, default=8,
                     help="cascades of the whole job (strong scaling: split over the GPUs; weak leg: per GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement also run every other leg (h0 seeding time, bit-exact check, "
+                         "re-seed, one-cascade / weak scaling, EncodeIFFT and rocFFT, surface, slab grid and its "
+                         "projections, BASELINE configs 1-3, CPU baseline); the --no-* switches then take legs out. "
+                         "Without it the run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the maps of the last step (what a caller of CalculateOcean reads: "
+                         "height, displacement, Jacobian of every cascade) as DIR/<map>_c<cascade>.npy, float32; above "
+                         "the size budget a fixed seeded sample of whole rows (dump_rows)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target CPU-baseline sample length")
     ap.add_argument("--no-profile", action="store_true", help="skip per-kernel HIP event timing")
@@ -121,6 +135,8 @@ def parse(argv=None):
                     help="launcher/rank plumbing only (no GPU work): every rank joins the process group, "
                          "runs the barrier + max-over-ranks protocol, and rank 0 prints a line naming n_gpus")
     args = ap.parse_args(argv)
+    if not args.full:
+        args.headline_only = True  # a plain run: only what the headline figure needs
     if args.headline_only:
         args.no_reseed = args.no_ifft = args.no_slab = args.no_surface = args.no_cpu_baseline = args.no_configs = True
         args.no_verify = True
@@ -792,6 +808,47 @@ def dev_equal(ptr_a: int, ptr_b: int, nbytes: int) -> bool:
 
 MAP_GETTERS = (("ocean_generator_height_map", 16), ("ocean_generator_displacement_map", 16),
                ("ocean_generator_jacobian_map", 4))
+
+
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000  # --dump-outputs: all files of a job together stay below 64 MB
+DUMP_SEED = 4093
+DUMP_MAPS = (("height", "GetHeightMap", 4), ("displacement", "GetDisplacementMap", 4), ("jacobian", "GetJacobianMap", 1))
+
+
+def dump_rows(n: int, cascades: int) -> list:
+    """The map rows --dump-outputs keeps of every cascade (36 B per texel over the three maps): all of
+    them while the job's maps fit DUMP_BUDGET_BYTES, else as many whole rows as fit, always the first
+    and the last and a draw seeded with DUMP_SEED of the others: the same rows for the same n and
+    cascade count, whatever the build or the number of ranks."""
+    import numpy as np
+
+    k = max(1, min(n, DUMP_BUDGET_BYTES // (36 * n * cascades)))
+    if k >= n:
+        return list(range(n))
+    inner = np.random.default_rng(DUMP_SEED).permutation(np.arange(1, n - 1))
+    return sorted(([0, n - 1] + [int(r) for r in inner])[:k])
+
+
+def dump_outputs(gen, mine, n: int, total: int, outdir: str) -> None:
+    """--dump-outputs: the rows dump_rows(n, total) of this rank's maps as they stand after the timed
+    loop, one float32 file per map and global cascade: <map>_c<cascade>.npy of shape [rows, n, 4]
+    (height, displacement) or [rows, n] (jacobian)."""
+    import numpy as np
+
+    from oceansimulation_amd import hip
+
+    os.makedirs(outdir, exist_ok=True)
+    rows = dump_rows(n, total)
+    gen.fft.synchronize()
+    for k, c in enumerate(mine):
+        for name, getter, lanes in DUMP_MAPS:
+            ptr = getattr(gen, getter)(k)
+            shape = (n, lanes) if lanes > 1 else (n,)
+            if len(rows) == n:
+                a = hip.to_host(ptr, (n,) + shape)
+            else:
+                a = np.stack([hip.to_host(ptr + r * n * lanes * 4, shape) for r in rows])
+            np.save(os.path.join(outdir, f"{name}_c{c}.npy"), a)
 
 
 def verify_cascades(ocean, fft, gen, mine, settings=None) -> dict:
@@ -1622,11 +1679,13 @@ def main(argv=None):
     gen.set_profiling(True)
     gen.GenerateSpectrum()  # first launch also loads the code object: not timed
     gen.kernel_times()
-    reps = 3
-    for _ in range(reps):
-        gen.GenerateSpectrum()
-    ms, cnt = gen.kernel_times()
-    h0_ms = ms[0] / reps  # all cascades, per regeneration
+    h0_ms = None
+    if args.full:
+        reps = 3
+        for _ in range(reps):
+            gen.GenerateSpectrum()
+        ms, cnt = gen.kernel_times()
+        h0_ms = ms[0] / reps  # all cascades, per regeneration
     overlap = use_frame_overlap(args, C, path, n)
     if overlap:
         gen.set_frame_overlap(True)
@@ -1646,9 +1705,11 @@ def main(argv=None):
     el = time.perf_counter() - t0
     el_max = max_over_ranks(el, world)
     ms, cnt = gen.kernel_times()
+    if args.dump_outputs:
+        dump_outputs(gen, mine, n, total, args.dump_outputs)
     # the headline checks its own maps (before the re-seed legs change how h0 is evaluated)
     if args.no_verify:
-        headline_check = {"verified": None, "skipped": "--no-verify / --headline-only (profiling runs)"}
+        headline_check = {"verified": None, "skipped": "no --full, or --no-verify / --headline-only (profiling runs)"}
     else:
         try:
             headline_check = verify_cascades(ocean, fft, gen, mine)
@@ -1778,7 +1839,8 @@ def main(argv=None):
         }
         out["kernels"]["frame_both_passes"] = {"avg_ms": p1_ms + p2_ms, "GB_per_s": frame_gbs,
                                                "frac_hbm_peak": frame_gbs / HBM_PEAK_GBS}
-        out["kernels"]["h0_seed_ms"] = h0_ms
+        if h0_ms is not None:
+            out["kernels"]["h0_seed_ms"] = h0_ms
     gen.close()
     watchdog = start_legs_watchdog(out, rank, args.legs_timeout)
     try:

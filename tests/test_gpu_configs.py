@@ -381,7 +381,7 @@ def test_bench_gpus_two_shared_gpu_reports_two_ranks(tmp_path):
     2-rank slab leg. Small sizes: this checks the launch path, not a measurement. Without
     --shared-gpu, --gpus 2 on a one-GPU box must refuse (rc 2)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    args = ["--gpus", "2", "--shared-gpu", "--n", "1024", "--cascades", "2", "--slab-n", "2048", "--steps", "3",
+    args = ["--full", "--gpus", "2", "--shared-gpu", "--n", "1024", "--cascades", "2", "--slab-n", "2048", "--steps", "3",
             "--warmup", "1", "--slab-steps", "2", "--no-cpu-baseline", "--no-surface", "--no-ifft", "--no-reseed"]
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True,
                        timeout=300, env=env, cwd=ROOT)
@@ -397,6 +397,52 @@ def test_bench_gpus_two_shared_gpu_reports_two_ranks(tmp_path):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], capture_output=True,
                            text=True, timeout=120, env=env, cwd=ROOT)
         assert r.returncode == 2 and "GPU(s) are visible" in r.stderr, (r.returncode, r.stderr[-2000:])
+
+
+@pytest.mark.parametrize("n,cascades", [(256, 3), (1024, 4)])
+def test_bench_plain_run_times_steps_and_dumps_last_maps(ocean, tmp_path, capsys, n, cascades):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` (run in this process) prints one line with
+    ms_per_step and value = points / time and no leg beside the headline; --dump-outputs writes the maps
+    after the last timed step as float32: whole at 256^2 x 3, the dump_rows sample at 1024^2 x 4 (above
+    the budget). Two runs with the same arguments write identical files, and they equal, bit for bit,
+    the maps of a generator stepped warmup + steps times with the same settings."""
+    b = _bench()
+    steps, warmup = 3, 2
+    args = ["--gpus", "1", "--n", str(n), "--cascades", str(cascades), "--steps", str(steps), "--warmup", str(warmup)]
+    for d in ("a", "b"):
+        assert b.main(args + ["--dump-outputs", str(tmp_path / d)]) == 0
+        lines = [l for l in capsys.readouterr().out.splitlines() if l.strip().startswith("{")]
+        assert len(lines) == 1, lines
+        line = json.loads(lines[0])
+        assert line["steps"] == steps and line["warmup"] == warmup and line["ms_per_step"] > 0
+        assert abs(line["value"] - n * n * cascades / (line["ms_per_step"] * 1e-3)) <= 1e-9 * line["value"]
+        assert line["unit"] == "height-field points/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+        for leg in ("strong_scaling", "reseed_every_frame", "ifft_only", "ifft_only_large", "surface", "slab", "configs",
+                    "cpu_baseline"):
+            assert leg not in line, leg
+    rows = b.dump_rows(n, cascades)
+    assert (len(rows) == n) == (n == 256)
+    fft = ocean.FFTCalculator(n)
+    gen = ocean.Generator(fft, cascades)
+    for c in range(cascades):
+        ocean.apply_settings(gen.GetOceanSettings(c), **b.cascade_settings(0, c))
+    for _ in range(warmup + steps):
+        gen.CalculateOcean(1.0 / 60.0)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and len(names) == 3 * cascades
+    total = 0
+    for c in range(cascades):
+        for name, ref in (("height", gen.height_map_host(c)), ("displacement", gen.displacement_map_host(c)),
+                          ("jacobian", gen.jacobian_map_host(c))):
+            got = np.load(tmp_path / "a" / f"{name}_c{c}.npy")
+            assert got.dtype == np.float32 and got.shape == (len(rows),) + ref.shape[1:], (name, c, got.shape)
+            assert np.isfinite(got).all() and np.abs(got).max() > 0
+            assert np.array_equal(got, np.load(tmp_path / "b" / f"{name}_c{c}.npy")), (name, c)
+            assert np.array_equal(got, ref[rows]), (name, c)
+            total += got.nbytes
+    assert total <= 64 * 1000 * 1000
+    gen.close()
+    fft.close()
 
 
 def test_rccl_all_to_all_large_pieces_world1(ocean):

@@ -74,6 +74,36 @@ def test_frame_overlap_mode_choice():
     assert not b.use_frame_overlap(b.parse(["--frame-overlap", "off"]), 1, "half", 1024)
 
 
+def test_bench_plain_run_has_no_extra_legs():
+    """Without --full every leg beside the headline is off (h0 timing, check, re-seed, one-cascade /
+    weak, EncodeIFFT, surface, slab, configs, CPU baseline); --full turns them on and the --no-*
+    switches still take legs out of it."""
+    b = _bench()
+    legs = ("no_verify", "no_reseed", "no_ifft", "no_surface", "no_slab", "no_configs", "no_cpu_baseline")
+    plain = b.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not plain.full and plain.headline_only and all(getattr(plain, k) for k in legs)
+    assert plain.steps == 7 and plain.warmup == 2 and plain.dump_outputs is None
+    full = b.parse(["--full"])
+    assert full.full and not full.headline_only and not any(getattr(full, k) for k in legs)
+    some = b.parse(["--full", "--no-slab", "--dump-outputs", "d"])
+    assert some.no_slab and not some.no_ifft and some.dump_outputs == "d"
+
+
+def test_bench_dump_rows_fixed_sample_within_budget():
+    """--dump-outputs keeps every row while the job's maps (36 B per texel and cascade) fit the budget,
+    else a fixed draw of whole rows with the first and the last, the same on every call, whose files
+    stay below 64 MB in all."""
+    b = _bench()
+    assert b.DUMP_BUDGET_BYTES <= 64 * 1000 * 1000
+    assert b.dump_rows(256, 3) == list(range(256))
+    for n, c in ((1024, 4), (4096, 8), (4096, 1), (16384, 1)):
+        rows = b.dump_rows(n, c)
+        assert rows == b.dump_rows(n, c) == sorted(set(rows))
+        assert rows[0] == 0 and rows[-1] == n - 1 and len(rows) < n
+        assert 36 * n * c * len(rows) <= b.DUMP_BUDGET_BYTES < 36 * n * c * (len(rows) + 1)
+    assert b.dump_rows(4096, 8) != list(range(len(b.dump_rows(4096, 8))))  # a draw, not the leading rows
+
+
 def test_lane_err_metric():
     from parity import lane_err, scalar_err
 

@@ -3,7 +3,7 @@
 # an earlier commit) against the tree's own, alternating, each run under its own time limit.
 #   AB_ARGS  bench.py arguments (default: the headline and the one-cascade leg only)
 set -u
-ARGS=${AB_ARGS:-"--steps 50 --warmup 5 --no-slab --no-ifft --no-surface --no-reseed --no-cpu-baseline"}
+ARGS=${AB_ARGS:-"--full --steps 50 --warmup 5 --no-slab --no-ifft --no-surface --no-reseed --no-cpu-baseline"}
 mkdir -p gpurun_out
 for r in 1 2 3; do
   for v in old new; do

@@ -14,12 +14,12 @@ case "${PART:-A}" in
 A)
   tools/gpu_step.sh ${T}_smoke 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" || exit 1
   tools/gpu_step.sh ${T}_suite 700 python -u -m pytest tests/ -m gpu -v --timeout 300 --timeout-method thread || exit 1
-  tools/gpu_step.sh ${T}_bench 600 python -u bench.py || exit 1
+  tools/gpu_step.sh ${T}_bench 600 python -u bench.py --full || exit 1
   ;;
 B)
   PREFIX=${T} tools/profile_gpu.sh || exit 1
-  PREFIX=${T}_16k BENCH_ARGS="--n 16384 --cascades 1 --steps 10 --warmup 2 --headline-only" tools/profile_gpu.sh || exit 1
-  PREFIX=${T}_ifft BENCH_ARGS="--steps 3 --warmup 1 --no-slab --no-surface --no-reseed --no-cpu-baseline --no-configs" \
+  PREFIX=${T}_16k BENCH_ARGS="--full --n 16384 --cascades 1 --steps 10 --warmup 2 --headline-only" tools/profile_gpu.sh || exit 1
+  PREFIX=${T}_ifft BENCH_ARGS="--full --steps 3 --warmup 1 --no-slab --no-surface --no-reseed --no-cpu-baseline --no-configs" \
     KERNEL_REGEX="k_cols_to_blocks|k_cols_pre|k_rows_final|k_cols|k_rows_ifft|k_cols4" tools/profile_gpu.sh || exit 1
   tools/gpu_step.sh ${T}_parity 400 python -u tools/parity_report.py || exit 1
   ;;

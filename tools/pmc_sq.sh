@@ -8,7 +8,7 @@
 # Output: gpurun_out/<prefix>_<k>/ (csv); summarise with tools/sq_summary.py.
 set -u
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-ARGS=${BENCH_ARGS:-"--steps 5 --warmup 2 --no-cpu-baseline --no-slab --no-ifft --no-surface --no-reseed --no-profile"}
+ARGS=${BENCH_ARGS:-"--full --steps 5 --warmup 2 --no-cpu-baseline --no-slab --no-ifft --no-surface --no-reseed --no-profile"}
 KRE=${KERNEL_REGEX:-"k_rows_half|k_rows_hp|k_cols_half"}
 P=${PREFIX:-pmc_sq}
 SETS=(
