@@ -59,22 +59,20 @@ $(APP): examples/waveapp_headless.cpp $(WAVES)
 	    -L$(PKG) -lwaves -loceanfft -Wl,-rpath,'$$ORIGIN/../$(PKG)' -L/opt/rocm/lib -lamdhip64
 
 MB := tools/microbench
-microbench: $(MB)/prebench $(MB)/detbench $(MB)/detbench_soffset $(MB)/rm16bench $(MB)/gen4bench $(MB)/ifft4bench $(MB)/gridbench $(MB)/halfbench_nohs $(MB)/ifftbench $(MB)/transbench $(MB)/scatterbench $(MB)/halfbench $(MB)/genbench $(MB)/colbench $(MB)/copybench $(MB)/genbench_noxch $(MB)/genbench_nobar $(MB)/layoutbench
+microbench: $(MB)/prebench $(MB)/detbench $(MB)/detbench_soffset $(MB)/rm16bench $(MB)/gen4bench $(MB)/ifft4bench $(MB)/gridbench $(MB)/ifftbench $(MB)/transbench $(MB)/scatterbench $(MB)/halfbench $(MB)/genbench $(MB)/colbench $(MB)/copybench $(MB)/genbench_noxch $(MB)/genbench_nobar $(MB)/layoutbench
 MB_DEPS := $(KERNEL_TUS:%=$(CSRC)/%.hip) $(DEVICE_H) $(MB)/ab_kernels.h $(MB)/all_kernels.h
 $(MB)/%: $(MB)/%.hip $(MB_DEPS)
 	$(HIPCC) $(HIPFLAGS) $< -o $@
 # timing ablations (wrong results by construction): no LDS exchanges / exchanges without barriers
 $(MB)/genbench_noxch: $(MB)/genbench.hip $(MB_DEPS)
 	$(HIPCC) $(HIPFLAGS) -DOCEAN_ABLATE_EXCHANGE $< -o $@
-$(MB)/halfbench_nohs: $(MB)/halfbench.hip $(MB_DEPS)
-	$(HIPCC) $(HIPFLAGS) -DOCEAN_ABLATE_HS $< -o $@
 $(MB)/detbench_soffset: $(MB)/detbench.hip $(MB_DEPS)
 	$(HIPCC) $(HIPFLAGS) -DOCEAN_SOFFSET_PIECES $< -o $@
 $(MB)/genbench_nobar: $(MB)/genbench.hip $(MB_DEPS)
 	$(HIPCC) $(HIPFLAGS) -DOCEAN_ABLATE_BARRIER $< -o $@
 
 clean:
-	rm -rf $(MB)/detbench $(MB)/detbench_soffset $(MB)/rm16bench $(MB)/gen4bench $(MB)/ifft4bench $(MB)/gridbench $(MB)/halfbench_nohs $(MB)/ifftbench $(MB)/transbench $(MB)/scatterbench $(MB)/halfbench $(MB)/genbench $(MB)/colbench $(MB)/copybench $(MB)/genbench_noxch $(MB)/genbench_nobar $(MB)/layoutbench $(CSRC)/build $(LIB) $(WAVES) $(CPPTEST) $(APP)
+	rm -rf $(MB)/detbench $(MB)/detbench_soffset $(MB)/rm16bench $(MB)/gen4bench $(MB)/ifft4bench $(MB)/gridbench $(MB)/ifftbench $(MB)/transbench $(MB)/scatterbench $(MB)/halfbench $(MB)/genbench $(MB)/colbench $(MB)/copybench $(MB)/genbench_noxch $(MB)/genbench_nobar $(MB)/layoutbench $(CSRC)/build $(LIB) $(WAVES) $(CPPTEST) $(APP)
 	$(MAKE) -s -C oracle clean
 
 .PHONY: all clean microbench

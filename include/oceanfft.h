@@ -312,10 +312,10 @@ int ocean_peers_debug_slot(const ocean_peers* peers, int slot, void** ptr, size_
 
 /* The whole-grid half-spectrum frame's layout pairing (N = 1024 .. 4096), host only: out = the field
  * strip width, gab/gde row group, gc row group and h0 strip width the column pass WRITES / reads {0..3},
- * the first three as the row pass (rows_variant 1 = k_rows_hp at 4096, 0 = k_rows_half) READS them
- * {4..6}, and the h0 strip width the seeding writes {7}. Each launcher picks its kernel from the same
- * descriptor it reports here (tests/test_capi_cpu.py checks the pairs over every shape). */
-int ocean_frame_plan(size_t texture_size, int cascades, int rows_variant, int32_t out[8]);
+ * the first three as the row pass READS them {4..6}, and the h0 strip width the seeding writes {7}.
+ * Both halves are the members of the shape types the launchers instantiate their kernels from
+ * (tests/test_capi_cpu.py checks the pairs over every shape). */
+int ocean_frame_plan(size_t texture_size, int cascades, int32_t out[8]);
 
 /* ---- instrumentation (bench) ------------------------------------------------------------- */
 /* When enabled, each kernel launch of the generator is bracketed by HIP events on its stream. */

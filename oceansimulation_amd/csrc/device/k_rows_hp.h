@@ -1,9 +1,9 @@
 // device/k_rows_hp.h — the half-spectrum row pass of whole 4096^2 grids (blocked field layout) with
 // the x transform split 16 x 256: one LDS transposition T_in that also does the mirror exchange, the
 // 256-point sub-transforms inside the wave (lane_xchg.h: v_permlane16/32_swap + DPP), a second
-// transposition T_out, a 16-point DFT in registers. Production k_rows_half moves the -u lanes through
-// the LDS, then runs fft_run<12> with two split exchanges: 2.5 LDS round trips and 10 barriers per
-// image against 2 and 7 here.
+// transposition T_out, a 16-point DFT in registers. k_rows_half moves the -u lanes through the LDS,
+// then runs fft_run with two split exchanges: 2.5 LDS round trips and 10 barriers per image against
+// 2 and 7 here.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -39,25 +39,22 @@ __device__ __forceinline__ int hp_swz(int n1) { return ((n1 >> 1) & 7) ^ (((n1 >
 __device__ __forceinline__ int hp_slot(int n1, int j) { return n1 * HpCfg::RS + (j ^ hp_swz(n1)); }
 
 // One row (both images; C loaded once, kept for image 1) per 256-thread workgroup, four per CU, the
-// 4 rows of a gc line on one XCD; default-policy loads, streamed stores (production k_rows_half's
-// item shape at 4096). RM: the fields are row-major behind a RowSrc (the strip-dealt slabs' row pass,
+// 4 rows of a gc line on one XCD; default-policy loads, streamed stores. RM: the fields are row-major
+// behind a RowSrc (the strip-dealt slabs' row pass,
 // rows = the rank's rows; streamed loads, C loaded per image, one row per workgroup in order), so slab
 // frames stay bit-identical to whole grids.
 //   T_in: thread (w, s, p) = (tid >> 6, tid & 3, (tid >> 2) & 15) receives x(n1 + 16 (p + 16 m)),
 //         n1 = 4 w + s (four 256-point sub-transforms per wave).
 //   sub-transform as k_rows_xp: v[b] = Y_n1(p + 16 b), then x W_N^(n1 (p + 16 b)).
 //   T_out: thread k2 = tid receives Z_n1(k2), n1 < 16; DFT-16: v[k1] = X(tid + 256 k1).
-// YP: the fields hold row y at storage row hx_store_row(y) (k_cols_half HX 2); items run over storage
-// rows, so the 4 rows of a gc line stay on one XCD. FB: field strips of FB columns (k_cols_half FB);
-// GRP: consecutive rows per XCD group (the rows of a gc line).
-// EARLY (round 5, as k_rows_xs EARLY): a wave retires its memory instructions in issue order, so loads
-// issued after an image's 16 map stores wait for those stores. 1: image 1's (D, E) loads are issued
-// before image 0's stores (32 VGPRs from the end of image 0's transform to image 1's T_in); 2: and
-// the next row's (A, B) and C before image 1's stores (the first row's in a prologue; persistent
-// grids); whole grids only.
-// MINB: the workgroups per CU the launch bounds ask for (4: 128 VGPRs; 3: 168, room for EARLY 2's
+// FB: field strips of FB columns (the column shape's FB); GRP: consecutive rows per XCD group (the
+// rows of a gc line).
+// EARLY (as k_rows_xs EARLY): a wave retires its memory instructions in issue order, so loads issued
+// after an image's 16 map stores wait for those stores. 1: image 1's (D, E) loads are issued before
+// image 0's stores (32 VGPRs from the end of image 0's transform to image 1's T_in); whole grids only.
+// MINB: the workgroups per CU the launch bounds ask for (4: 128 VGPRs; 3: 168, room for EARLY 1's
 // prefetch without spills).
-template <int RG, int RGC, bool RM = false, bool YP = false, int FB = 4, int GRP = 4, int EARLY = 0, int MINB = 4>
+template <int RG, int RGC, bool RM = false, int FB = 4, int GRP = 4, int EARLY = 0, int MINB = 4>
 __global__ __launch_bounds__(256, MINB) void k_rows_hp(FrameParams fp, const float4* __restrict__ gab,
                                                  const float4* __restrict__ gde, const float2* __restrict__ gc,
                                                  const float4* __restrict__ spec, float4* __restrict__ maps,
@@ -69,7 +66,6 @@ __global__ __launch_bounds__(256, MINB) void k_rows_hp(FrameParams fp, const flo
   using HC = HalfCfg<LOGN>;
   constexpr int N = S::N, T = S::T, B = 4, STRIPS = HC::STRIPS;
   static_assert(T == 256, "one 4-wave row per workgroup");
-  static_assert(!(RM && YP), "storage-row order is a whole-grid layout");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float2* tw = reinterpret_cast<float2*>(smem);
   float2* xs = reinterpret_cast<float2*>(smem + HpCfg::TW);
@@ -81,30 +77,23 @@ __global__ __launch_bounds__(256, MINB) void k_rows_hp(FrameParams fp, const flo
   constexpr int LA = RM ? kStream : 0;
   const int lcpr = RM ? 31 - __builtin_clz(rs.cpr) : 0, cmask = RM ? rs.cpr - 1 : 0;
   const int wave0 = __builtin_amdgcn_readfirstlane((int)threadIdx.x & ~63);
-  static_assert(!EARLY || !RM, "EARLY: whole-grid layouts");
-  float4 fpre[EARLY > 0 ? 8 : 1];  // EARLY: the next image's field texels, issued before the stores
-  float2 cpre[EARLY >= 2 ? 8 : 1];  // EARLY 2: the next row's C
-  // the field texels of image img of row item (whole grids), into f (and C into cdst)
-  auto issue = [&](int item, int img, float4* f, float2* cdst) __attribute__((always_inline)) {
-    const int c = item / nrows, yf = item - c * nrows;
+  static_assert(EARLY == 0 || (EARLY == 1 && !RM), "EARLY: whole-grid layouts");
+  float4 fpre[EARLY > 0 ? 8 : 1];  // EARLY: image 1's (D, E) texels, issued before image 0's stores
+  // the (D, E) texels of row item (whole grids), into f
+  auto issue = [&](int item, float4* f) __attribute__((always_inline)) {
+    const int c = item / nrows, y = item - c * nrows;
     const size_t base = (size_t)c * STRIPS * N * B;
     const int i = opaque((int)threadIdx.x);
 #pragma unroll
     for (int m = 0; m < 8; m++)
     {
       const int u = m * T + i;
-      f[m] = ld4<LA>((img == 0 ? gab : gde) + base, half_group_offset<LOGN, RG, FB>(yf, u / FB, u % FB) * 16);
-      if (cdst)
-        cdst[m] = ld2<0>(gc + base, half_group_offset<LOGN, RGC, FB>(yf, u / FB, u % FB) * 8);
+      f[m] = ld4<LA>(gde + base, half_group_offset<LOGN, RG, FB>(y, u / FB, u % FB) * 16);
     }
   };
-  const int item0 = RM ? (int)blockIdx.x : xcd_group_slot<GRP>(blockIdx.x, gridDim.x);
-  if (EARLY >= 2 && item0 < total)
-    issue(item0, 0, fpre, cpre);
-  for (int item = item0; item < total; item += gridDim.x)
+  for (int item = RM ? (int)blockIdx.x : xcd_group_slot<GRP>(blockIdx.x, gridDim.x); item < total; item += gridDim.x)
   {
-    const int c = item / nrows, yf = item - c * nrows;  // RM: yf is the local row (slabs start at an even row)
-    const int y = YP ? hx_row_of_store(yf) : yf;       // the output row; yf addresses the fields
+    const int c = item / nrows, y = item - c * nrows;  // RM: y is the local row (slabs start at an even row)
     const float dk = fp.c[c].dk;
     const size_t base = RM ? ((size_t)c * rows + y) * rs.lp : (size_t)c * STRIPS * N * B;
     const float sgy = (y & 1) ? -1.0f : 1.0f;
@@ -122,8 +111,8 @@ __global__ __launch_bounds__(256, MINB) void k_rows_hp(FrameParams fp, const flo
         const int u = m * T + i;
         // RM: source block of column u (wave-uniform, a scalar shift) and the element in its row
         const int src = RM ? (m * T + sopaque(wave0)) >> lcpr : 0;
-        const int off = RM ? (u & cmask) : half_group_offset<LOGN, RG, FB>(yf, u / FB, u % FB);
-        const int offc = RM ? off : half_group_offset<LOGN, RGC, FB>(yf, u / FB, u % FB);
+        const int off = RM ? (u & cmask) : half_group_offset<LOGN, RG, FB>(y, u / FB, u % FB);
+        const int offc = RM ? off : half_group_offset<LOGN, RGC, FB>(y, u / FB, u % FB);
         const float4* fab = RM ? reinterpret_cast<const float4*>(rs.ab + (size_t)src * rs.src_stride) : gab;
         const float4* fde = RM ? reinterpret_cast<const float4*>(rs.de + (size_t)src * rs.src_stride) : gde;
         const float2* fc = RM ? reinterpret_cast<const float2*>(rs.c + (size_t)src * rs.src_stride) : gc;
@@ -131,8 +120,8 @@ __global__ __launch_bounds__(256, MINB) void k_rows_hp(FrameParams fp, const flo
         const float4 s4 = ld4<0>(sp, (N / 2 - u) * 16);
         if (img == 0)
         {
-          const CPair p = raw_pair(EARLY >= 2 ? fpre[m] : ld4<LA>(fab + base, off * 16));
-          const float2 cc = EARLY >= 2 ? cpre[m] : ld2<0>(fc + base, offc * 8);
+          const CPair p = raw_pair(ld4<LA>(fab + base, off * 16));
+          const float2 cc = ld2<0>(fc + base, offc * 8);
           if constexpr (!RM)
             ckeep[m] = cc;
           const float Ar = p.re.x, Ai = p.im.x, Br = p.re.y, Bi = p.im.y, Cr = cc.x, Ci = cc.y;
@@ -161,8 +150,8 @@ __global__ __launch_bounds__(256, MINB) void k_rows_hp(FrameParams fp, const flo
       {
         // the Nyquist column u = -N/2 (first column of the last strip; RM: block nyq_src, column cpr)
         // replaces the unused -u lane of u = 0
-        const int off = RM ? rs.cpr : half_group_offset<LOGN, RG, FB>(yf, N / 2 / FB);
-        const int offc = RM ? off : half_group_offset<LOGN, RGC, FB>(yf, N / 2 / FB);
+        const int off = RM ? rs.cpr : half_group_offset<LOGN, RG, FB>(y, N / 2 / FB);
+        const int offc = RM ? off : half_group_offset<LOGN, RGC, FB>(y, N / 2 / FB);
         const size_t ns = RM ? (size_t)rs.nyq_src * rs.src_stride : 0;
         const float4* fab = RM ? reinterpret_cast<const float4*>(rs.ab + ns) : gab;
         const float4* fde = RM ? reinterpret_cast<const float4*>(rs.de + ns) : gde;
@@ -234,17 +223,8 @@ __global__ __launch_bounds__(256, MINB) void k_rows_hp(FrameParams fp, const flo
       }
       idft16(v);  // v[k1] = X(tid + T k1)
       if constexpr (EARLY > 0)
-      {
         if (img == 0)
-          issue(item, 1, fpre, nullptr);
-        else if constexpr (EARLY >= 2)
-        {
-          // unconditional (the last row re-reads its own image 0) so that the consumed registers are
-          // not kept as the loop's other incoming value
-          const int nx = item + (int)gridDim.x < total ? item + (int)gridDim.x : item;
-          issue(nx, 0, fpre, cpre);
-        }
-      }
+          issue(item, fpre);
       float4* dst = maps + ((size_t)cimg * nrows + y) * N;
 #pragma unroll
       for (int m = 0; m < 16; m++)

@@ -1,5 +1,5 @@
 // device/k_rows_xs.h — the row pass of N = 16384 (the four-step path's blocks, RowSrc): one row of both
-// images per 1024-thread workgroup with the x transform in four steps (XS, as k_rows_half<.., XS>),
+// images per 1024-thread workgroup with the x transform in four steps (XsCfg below),
 // the next image's field loads in flight during the current image's transform (PF), and a streaming
 // T_in (round 4): each kept element's own and -u CPairs are formed and their re-halves written to the
 // LDS at once, only the im-halves wait in registers for the second half. 3.738 -> 3.680 ms per 16384^2
@@ -14,15 +14,36 @@
 #include "ocean_internal.h"
 #include "device/fft.h"
 #include "device/grid.h"
-#include "device/k_half_rows.h"
 #include "device/memory.h"
 
 namespace oceanfft
 {
 
+// The x transform of one row per 16-wave workgroup (N = 16 T, T = 1024) in four steps, so that most of
+// it runs between workgroup barriers instead of across them. With n = n1 + 16 n2 and k = k2 + T k1: a
+// transposition through LDS (T_in, which also does the mirror exchange's job) gives wave n1 the T
+// inputs x(n1 + 16 n2); each wave runs its T-point sub-transform (fft_run<LOGN - 4>, 64 lanes x 16
+// points) in its own LDS region, ordered by the LDS's in-order execution of one wave's instructions
+// instead of barriers; twiddles W_N^(n1 k2); a second transposition (T_out) gives thread k2 the 16
+// values over n1, and a 16-point DFT in registers leaves X(k2 + T k1) in coalesced store order.
+// Barriers per image: 7 instead of the plain transform's 14 (mirror 2 + three exchanges of two halves
+// x 2 + 1); rm16bench priced the barriers of the 16384 pass at ~1 ms of 3.8. tw2_glob: the T-point
+// table (appended for 8192/16384 by ocean_fft_create).
+template <int LOGN>
+struct XsCfg
+{
+  static constexpr int L2 = LOGN - 4;
+  // region of one n1 (slots of 8 B): holds a sub-transform's padded exchange (PADDED + 4), and
+  // RS = 1 mod 16 spreads T_in's 16-lane writes (16 regions at once) over all 32 banks
+  static constexpr int RS = ((FftShape<L2>::PADDED + 4 + 14) / 16) * 16 + 1;
+  static constexpr int TW1 = ((FftShape<LOGN>::TW_ENTRIES * 8 + 15) / 16) * 16;
+  static constexpr int TW2 = ((FftShape<L2>::TW_ENTRIES * 8 + 15) / 16) * 16;
+  static constexpr int LDS = TW1 + TW2 + 16 * RS * 8;
+};
+
 // One row's 1024-thread workgroup holds 256 KiB of CPairs, half the CU's register file, so no second
-// workgroup shares the CU and nothing else hides the loads: k_rows_half<.., XS> waits for each image's
-// fields after the previous image's stores (3.81 ms per 16384^2 pass; 2.14 without loads,
+// workgroup shares the CU and nothing else hides the loads: without prefetch each image's fields are
+// awaited after the previous image's stores (3.81 ms per 16384^2 pass; 2.14 without loads,
 // tools/microbench/rm16bench). PF issues the 16-B field loads of the NEXT image right after the
 // current one's fields are consumed (image 1's (D, E) during image 0's transform; the next row's
 // (A, B) during image 1's), so most of the HBM latency runs under the T_in / sub-transform / T_out

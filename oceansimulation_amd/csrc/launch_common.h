@@ -59,40 +59,6 @@ inline int device_cu_count()
 
 inline bool g_force_persistent = false;  // tools/microbench A/B only
 
-// 4096 row pass (whole grids, launch_half_rows, and the strip-dealt slabs' row-major fields,
-// launch_rm_rows): 1 = k_rows_hp (production: T_in with the mirror, 256-point sub-transforms in the
-// wave through permlane / DPP swaps, T_out; device/k_rows_hp.h), 0 = k_rows_half (the mirror
-// exchange, then fft_run<12>). 8 x 4096^2: 1.377 -> 1.360 ms, maps within 1e-6 of max
-// (profiles/r04_halfbench_hp.log). Both paths switch together, so slabs stay bit-identical to whole grids.
-inline int half_rows_variant = 1;
-
-// Whole-grid half-spectrum fields at N = 4096 with <= 2 cascades per launch (the 4- and 8-GPU shares of
-// the headline): pass 1 on half strips, two 512-thread workgroups per CU, into field strips FB = 2
-// columns wide (whole-line stores: gab / gde row groups of 4, gc of 8), the row pass on that layout.
-// Same per-column arithmetic as the 4-column strips, so the maps are bit-identical to them; at one
-// cascade the frame takes 0.319 against 0.339 ms, at two 0.597 against 0.609, at three and more it
-// loses (profiles/r04_halfbench_fb2h_{1,2,3,4,8}.log). Both launchers take the layout from here.
-// N = 2048 (round 6) likewise: 256-thread half-strip workgroups, up to four per CU. At one cascade the
-// 4-column pass has 257 items for 256 CUs, and the CU that runs two sets the pass's time (0.0577 ms
-// against 0.0345 with 256 items, profiles/r06_halfbench_tail_11.log); the 513 half-strip items fit the
-// 1024 slots at once: column pass 0.0431 -> 0.0311 ms, frame 0.0945 -> 0.0862 ms, at two cascades
-// 0.1642 -> 0.1621 ms, at four it loses (0.2960 -> 0.3322), maps bit-identical
-// (profiles/r06_halfbench_h2k_{1,2,4}.log).
-inline int half_fields_fb(int logn, int cascades) { return (logn == 12 || logn == 11) && cascades <= 2 ? 2 : 4; }
-constexpr int kHalfRG2 = 4, kHalfRGC2 = 8;  // the FB = 2 layout's row groups
-
-// The whole-grid half-spectrum fields as one launcher writes / the other reads them: field strip width
-// FB, row groups of gab / gde (RG) and of gc (RGC), and the h0 strip width. launch_half_columns and
-// launch_half_rows each choose their kernel FROM their own descriptor (half_cols_layout /
-// half_rows_layout, launch_half.hip), and ocean_frame_plan reports both, so a CPU test can check every
-// (N, cascades, row-pass variant) pairs the layout the column pass writes with the one the row pass reads
-// (the round-4 fallback row pass read the FB = 4 layout the column pass no longer wrote at <= 2 cascades).
-struct HalfFieldLayout
-{
-  int fb, rg, rgc, h0_blk;
-};
-
-
 inline bool one_shot_grids(int cus)
 {
   const int d = device_cu_count();

@@ -75,37 +75,27 @@ hipError_t launch_half_slab_columns(int logn, const FrameParams& fp, const HalfS
                                     h0_full ? nullptr : h0row, ranks, blk, nullptr, stream, cus);
       if (e != hipSuccess || hsl.nstrips < 1)  // a rank past the last strip only builds the Nyquist-row term
         return e;
-      // slab items keep fewer pairs in VGPRs: with four, the SLAB store addressing spills 8-16 B (at
-      // N = 8192 already with two; one fits)
-      constexpr int HKS = LOGN == 13 ? 1 : kHalfHK - 1;
-      auto kern = put ? k_cols_half<LOGN, kStream, kStream, true, true, false, 1, 1, K::B, true, false, kHalfHL, HKS, 0, 4, true>
-                      : k_cols_half<LOGN, kStream, kStream, true, true, false, 1, 1, K::B, true, false, kHalfHL, HKS>;
-      const int lds = ((S::TW_ENTRIES * 8 + 15) / 16) * 16 + K::LDS1 + kHalfHL * K::WG1 * 16;
-      int grid = persistent_grid(kern, K::WG1, lds, fp.cascades * hsl.nstrips, cus2);
-      if (grid > hs_blocks)
-        grid = hs_blocks;
       unsigned char* target = put ? reinterpret_cast<unsigned char*>(const_cast<uint64_t*>(put->dst))
                                   : static_cast<unsigned char*>(send);
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(K::WG1), lds, stream, fp, h0, (float4*)nullptr, (float4*)nullptr,
-                         (float2*)nullptr, tw, hs, hsl, target, h0_full ? 1 : 0, (const SpectrumConsts*)nullptr);
-      return hipGetLastError();
+      auto launch = [&](auto sh) {
+        return launch_cols_half<decltype(sh)>(fp, hsl.nstrips, h0, nullptr, nullptr, nullptr, tw, hs, hs_blocks, hsl, target,
+                                              h0_full ? 1 : 0, nullptr, stream, cus2);
+      };
+      return put ? launch(ColsSlab<LOGN, true>{}) : launch(ColsSlab<LOGN, false>{});
     }
   });
 }
 
 // The row pass over row-major fields (RowSrc: the strip-dealt path's one block after k_half_to_rows,
-// or the four-step path's exchange blocks). N = 16384 (T = 1024, one row per workgroup): the XS x
-// transform (barriers 14 -> 7 per image), which needs tw2, the N/16-point table ocean_fft_create
-// appends for the sizes fourstep_table() names.
-// tools/microbench A/B at 16384: 0 = the plain transform, 1 = XS (k_rows_half), 2 = k_rows_xs, 3 =
-// k_rows_xs with 2 of the next image's 8 field loads in flight during the transform (PF; 4 spill), 4 =
-// k_rows_xs EARLY 4 on a resident grid: every image's loads issued before the previous image's stores,
-// and image 0's C kept for image 1 (round 5: 3.677 -> 3.158 (EARLY 3) -> 3.076 ms per 16384^2 pass,
-// maps bit-identical, profiles/r05_rm16bench_early.log, r05_rm16bench_keepc.log).
-// Measured and not kept: k_rows_xp (tools/microbench/k_rows_xp.h, the 64 x 256 split with the
-// sub-transforms' exchanges in the wave), 3.80-3.83 against 3.74 ms (profiles/r04_rm16bench_xp.log).
-inline int rm_rows_variant = 4;
-
+// or the four-step path's exchange blocks).
+//   4096: the whole grid's row pass (k_rows_hp, launch_half_rows) on row-major fields, so slab frames
+//   stay bit-identical to whole grids.
+//   N = 16384 (T = 1024, one row per workgroup): k_rows_xs EARLY 4 on a resident grid: every image's
+//   loads issued before the previous image's stores, and image 0's C kept for image 1 (3.677 -> 3.158
+//   (EARLY 3) -> 3.076 ms per 16384^2 pass, maps bit-identical, profiles/r05_rm16bench_early.log,
+//   r05_rm16bench_keepc.log). It needs tw2, the N/16-point table ocean_fft_create appends for the
+//   sizes fourstep_table() names.
+//   Everything else: k_rows_half, two rows per workgroup.
 template <int LOGN>
 hipError_t launch_rm_rows(const FrameParams& fp, const RowSrc& rs, const float4* spec, float4* maps, float* jac,
                           const FoamParams& foam, const float2* tw, const float2* tw2, int rows, hipStream_t stream,
@@ -118,47 +108,28 @@ hipError_t launch_rm_rows(const FrameParams& fp, const RowSrc& rs, const float4*
     return hipErrorInvalidValue;
   if constexpr (LOGN == 12)
   {
-    // the strip-dealt slabs at 4096: the whole grid's row pass (k_rows_hp, launch_half_rows) on
-    // row-major fields, so slab frames stay bit-identical to whole grids
-    if (half_rows_variant == 1)
-    {
-      auto kern = k_rows_hp<1, 1, true>;
-      const int grid = persistent_grid(kern, 256, HpCfg::LDS, fp.cascades * rows, cus);
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), HpCfg::LDS, stream, fp, (const float4*)nullptr,
-                         (const float4*)nullptr, (const float2*)nullptr, spec, maps, jac, foam, tw, rows, rs);
-      return hipGetLastError();
-    }
+    auto kern = k_rows_hp<1, 1, true>;
+    const int grid = persistent_grid(kern, 256, HpCfg::LDS, fp.cascades * rows, cus);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), HpCfg::LDS, stream, fp, (const float4*)nullptr,
+                       (const float4*)nullptr, (const float2*)nullptr, spec, maps, jac, foam, tw, rows, rs);
   }
-  if constexpr (RPW == 1)
+  else if constexpr (RPW == 1)
   {
-    if (rm_rows_variant >= 2)
-    {
-      if (!tw2)
-        return hipErrorInvalidValue;
-      auto kern = rm_rows_variant == 4 ? k_rows_xs<LOGN, 0, 4> : rm_rows_variant == 3 ? k_rows_xs<LOGN, 2> : k_rows_xs<LOGN, 0>;
-      const int lds = XsCfg<LOGN>::LDS;
-      const int grid = rm_rows_variant == 4 ? resident_grid(kern, S::T, lds, fp.cascades * rows, cus)
-                                            : persistent_grid(kern, S::T, lds, fp.cascades * rows, cus);
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(S::T), lds, stream, fp, spec, maps, jac, foam, tw, rows, rs, tw2);
-      return hipGetLastError();
-    }
-    if (rm_rows_variant != 0)
-    {
-      if (!tw2)
-        return hipErrorInvalidValue;
-      auto kern = k_rows_half<LOGN, kStream, kStream, 0, 1, true, true, 1, 1, 4, 2, true, true>;
-      const int lds = XsCfg<LOGN>::LDS;
-      const int grid = persistent_grid(kern, S::T, lds, fp.cascades * rows, cus);
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(S::T), lds, stream, fp, (const float4*)nullptr, (const float4*)nullptr,
-                         (const float2*)nullptr, spec, maps, jac, foam, tw, rows, rs, tw2);
-      return hipGetLastError();
-    }
+    if (!tw2)
+      return hipErrorInvalidValue;
+    auto kern = k_rows_xs<LOGN, 0, 4>;
+    const int lds = XsCfg<LOGN>::LDS;
+    const int grid = resident_grid(kern, S::T, lds, fp.cascades * rows, cus);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(S::T), lds, stream, fp, spec, maps, jac, foam, tw, rows, rs, tw2);
   }
-  auto kern = k_rows_half<LOGN, kStream, kStream, 0, RPW, true, true>;
-  const int lds = ((S::TW_ENTRIES * 8 + 15) / 16) * 16 + lds_row_slots<LOGN>(RPW) * 8;
-  const int grid = persistent_grid(kern, S::T * RPW, lds, fp.cascades * (rows / RPW), cus);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(S::T * RPW), lds, stream, fp, (const float4*)nullptr, (const float4*)nullptr,
-                     (const float2*)nullptr, spec, maps, jac, foam, tw, rows, rs, (const float2*)nullptr);
+  else
+  {
+    auto kern = k_rows_half<LOGN, kStream, true>;
+    const int lds = ((S::TW_ENTRIES * 8 + 15) / 16) * 16 + lds_row_slots<LOGN>(RPW) * 8;
+    const int grid = persistent_grid(kern, S::T * RPW, lds, fp.cascades * (rows / RPW), cus);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(S::T * RPW), lds, stream, fp, (const float4*)nullptr, (const float4*)nullptr,
+                       (const float2*)nullptr, spec, maps, jac, foam, tw, rows, rs);
+  }
   return hipGetLastError();
 }
 

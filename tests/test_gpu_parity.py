@@ -414,7 +414,7 @@ def test_batched_cascades_equal_individual(ocean):
 @pytest.mark.parametrize("n", [2048, 4096])
 def test_half_strip_shape_bit_exact_across_cascade_counts(ocean, n):
     """At 2048 and 4096 the column pass runs on half strips (FB = 2 fields, 2T-thread workgroups) when
-    a launch holds <= 2 cascades and on whole strips above (launch_common.h half_fields_fb). A
+    a launch holds <= 2 cascades and on whole strips above (launch_half.hip half_strip_launch). A
     cascade's maps and Jacobian are bit-identical in 1-, 2- and 3-cascade generators, for plain
     frames and for the fused re-seed frames of the reference app's loop (src/Generator.cpp:45-83,
     src/Waves.cpp:91-94)."""

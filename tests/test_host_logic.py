@@ -208,6 +208,9 @@ def test_traffic_attribution_needs_same_device_code(tmp_path, monkeypatch):
     g = vars(_parse_rocprof())
     assert g["device_source_sha256"]() == b.device_source_sha256()
     assert g["base_name"]("void oceanfft::k_rows_half<12, 0, 2>(oceanfft::FrameParams, float*)") == "k_rows_half"
+    shaped = "void oceanfft::k_cols_half<oceanfft::ColsWhole<12, false> >(oceanfft::FrameParams, float4 const*)"
+    assert g["base_name"](shaped) == "k_cols_half" and g["first_arg"](shaped) == "12"
+    assert g["size_key"](shaped, 12) == "k_cols_half" and g["size_key"](shaped, 11) == "k_cols_half<12>"
     # a fake tree: same device code, one matching and one stale summary
     root = tmp_path / "tree"
     shutil.copytree(os.path.join(ROOT, "oceansimulation_amd", "csrc"), root / "oceansimulation_amd" / "csrc",

@@ -9,7 +9,7 @@ namespace oceanfft
 
 // Pass 1 on half strips (whole grids): a 2T-thread workgroup (512 at N = 4096, 256 VGPRs, one per
 // CU) transforms 2 columns per item, so the thread's 16 evolved amplitudes H stay in VGPRs (32)
-// across the three rounds: no H scratch (k_cols_half<HS> moves 24 B per kept texel through it).
+// across the three rounds: no H scratch (k_cols_half moves 24 B per kept texel through it).
 // Field strips are FB = 2 columns wide (half_group_offset<.., 2>): with RG rows per group, one store
 // instruction of a wave (32 rows x 2 columns) writes whole 128-B lines when RG * 2 * 16 B = 128 B
 // (gab, gde: RG = 4; gc: RGC = 8). The two halves of an h0 strip (items 2p, 2p + 1) run together
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(2 * FftShape<LOGN>::T) void k_cols_half2(FrameParam
 // Pass 1 with H in VGPRs (whole grids, N = 4096): one 4-column strip per item on T * B / 2 = 512
 // threads, each holding two positions (ia, ia + T/2) of one column, i.e. 32 points (fft_run_x2), so
 // the 32 evolved amplitudes H (64 VGPRs) stay in registers across the three rounds: no H scratch
-// (k_cols_half<HS> moves 24 B per kept texel through it) and h0 read once. Each store instruction of
+// (k_cols_half moves 24 B per kept texel through it) and h0 read once. Each store instruction of
 // a wave still covers 16 rows x 4 columns, i.e. whole 128-B lines of the row-group layout. 512
 // threads with 139 KiB of LDS: one workgroup per CU, 256 VGPRs per thread.
 // HB: the second position's H goes through a per-block scratch slice (hs) instead (fewer VGPRs).
@@ -207,7 +207,21 @@ __global__ __launch_bounds__(FftShape<LOGN>::T * 2) void k_cols_half4(FrameParam
   }
 }
 
-// launch_half_columns with the A/B variants of halfbench (0 = production, numbered as in the logs)
+// A k_cols_half shape with every parameter free: the A/B legs that differ from the library's shapes
+// (device/k_half_cols.h) in field layout, kept H pairs or strip widths.
+template <int LOGN_, int RG_, int RGC_, int CPI_, int HL_, int HK_, int FB_ = 4, int HB_ = ColFirstCfg<LOGN_>::B,
+          bool NYQ_ = false, bool SEED_ = false>
+struct ColsAb
+{
+  static constexpr int LOGN = LOGN_, LA = SEED_ ? 0 : kStream;
+  static constexpr bool SLAB = false, SEED = SEED_, PUT = false, NYQ = NYQ_;
+  static constexpr int RG = RG_, RGC = RGC_, FB = FB_, CPI = CPI_, HB = HB_, HL = HL_, HK = HK_;
+};
+
+// The whole-strip column pass with the A/B variants of halfbench (0 = the library's shape without NYQ,
+// numbered as in the logs): 25..32 H pairs outside the scratch (HL, HK; 32 none), 33 the re-seed frame
+// with all pairs in the scratch, 34..36 field layouts (2, 2), (4, 4), (1, 1), 37 one workgroup per
+// scratch slice, 12..14 k_cols_half2, 22 k_cols_half4
 hipError_t launch_half_columns_ab(int logn, const FrameParams& fp, const float4* h0, float4* gab, float4* gcd, float2* ge,
                                float4* spec, const float2* tw, hipStream_t stream, int cus, float2* hs = nullptr,
                                int hs_blocks = 0, const void* seed_consts = nullptr, int variant = 0)
@@ -225,42 +239,6 @@ hipError_t launch_half_columns_ab(int logn, const FrameParams& fp, const float4*
       hipError_t e = launch_half_nyquist(fp, n, K::B, h0, spec, nullptr, 1, 0, seed, stream, cus);
       if (e != hipSuccess)
         return e;
-      // hs: per-block H scratch (half_hs_bytes): H evolved once instead of once per round
-      if (seed && !hs)
-        return hipErrorInvalidValue;
-      // HS: h0 is read once per item, streamed (nt), which leaves the XCD's L2 to the H scratch
-      // (0.972 -> 0.935 ms, tools/microbench/halfbench). variant (halfbench): 1 = default-policy h0
-      // loads, 2 = sc1 field stores (dropped from L2: slower), 3 = sc1 + nt stores
-      // 4..7: field layouts with row groups (RG, RGC) = (2, 2), (2, 4), (4, 4), (1, 1) (launch_half_rows 8..11)
-      constexpr int RG = kHalfRG, RGC = kHalfRGC;
-      // whole grids below 4096 keep 2 H pairs in VGPRs: 128 VGPRs, so two (2048) or four (1024)
-      // workgroups fit a CU (with 4: 134-136 VGPRs, one fewer)
-      constexpr int HKW = LOGN == 12 ? kHalfHK : 2;
-      // HP (the H scratch in 16-B pairs): 0.921 -> 0.910 ms (halfbench hpair); variant 23: unpaired
-      auto kern = seed && variant == 33 ? k_cols_half<LOGN, 0, kStream, true, false, true, RG, RGC, K::B, true>
-                  : seed ? k_cols_half<LOGN, 0, kStream, true, false, true, RG, RGC, K::B, true, false, kHalfHL, kHalfHKSeed>
-                       : !hs ? k_cols_half<LOGN, 0, kStream, false, false, false, RG, RGC>
-                       : variant == 1 ? k_cols_half<LOGN, 0, kStream, true, false, false, RG, RGC>
-                       : variant == 2 ? k_cols_half<LOGN, kStream, 16, true, false, false, RG, RGC>
-                       : variant == 3 ? k_cols_half<LOGN, kStream, 18, true, false, false, RG, RGC>
-                       : variant == 4 ? k_cols_half<LOGN, kStream, kStream, true, false, false, 2, 2>
-                       : variant == 5 ? k_cols_half<LOGN, kStream, kStream, true, false, false, 2, 4>
-                       : variant == 6 ? k_cols_half<LOGN, kStream, kStream, true, false, false, 4, 4>
-                       : variant == 7 ? k_cols_half<LOGN, kStream, kStream, true, false, false, 1, 1>
-                       : variant == 23 ? k_cols_half<LOGN, kStream, kStream, true, false, false, RG, RGC>
-                       : variant == 24 ? k_cols_half<LOGN, kStream, kStream, true, false, false, RG, RGC, K::B, true, true>
-                       : variant == 25 ? k_cols_half<LOGN, kStream, kStream, true, false, false, RG, RGC, K::B, true, false, 1, 0>
-                       : variant == 26 ? k_cols_half<LOGN, kStream, kStream, true, false, false, RG, RGC, K::B, true, false, 1, 1>
-                       : variant == 27 ? k_cols_half<LOGN, kStream, kStream, true, false, false, RG, RGC, K::B, true, false, 1, 2>
-                       : variant == 28 ? k_cols_half<LOGN, kStream, kStream, true, false, false, RG, RGC, K::B, true, false, 0, 2>
-                       : variant == 29 ? k_cols_half<LOGN, kStream, kStream, true, false, false, RG, RGC, K::B, true, false, 1, 3>
-                       : variant == 30 ? k_cols_half<LOGN, kStream, kStream, true, false, false, RG, RGC, K::B, true, false, 1, 4>
-                       : variant == 31 ? k_cols_half<LOGN, kStream, kStream, true, false, false, RG, RGC, K::B, true, false, 1, 5>
-                       : variant == 32 ? k_cols_half<LOGN, kStream, kStream, true, false, false, RG, RGC, K::B, true>
-                       : variant == 34 ? k_cols_half<LOGN, kStream, kStream, true, false, false, 2, 2, K::B, true, false, kHalfHL, kHalfHK>
-                       : variant == 35 ? k_cols_half<LOGN, kStream, kStream, true, false, false, 4, 4, K::B, true, false, kHalfHL, kHalfHK>
-                       : variant == 36 ? k_cols_half<LOGN, kStream, kStream, true, false, false, 1, 1, K::B, true, false, kHalfHL, kHalfHK>
-                                      : k_cols_half<LOGN, kStream, kStream, true, false, false, RG, RGC, K::B, true, false, kHalfHL, HKW>;
       if (variant >= 12 && variant <= 14 && !seed)  // half-strip items (k_cols_half2): H in VGPRs
       {
         auto hk = variant == 12   ? k_cols_half2<LOGN, 0, kStream, 4, 8>
@@ -282,46 +260,53 @@ hipError_t launch_half_columns_ab(int logn, const FrameParams& fp, const float4*
         hipLaunchKernelGGL(hk, dim3(hg), dim3(S::T * 2), hlds, stream, fp, h0, gab, gcd, ge, tw, hs);
         return hipGetLastError();
       }
-      if (variant == 20 && hs && !seed)  // half-strip items, two workgroups per CU (HS slices of half size)
-      {
-        auto hk = k_cols_half<LOGN, 0, 0, true, false, false, RG, RGC, K::B / 2>;
-        const int wg = S::T * (K::B / 2);
-        const int hlds = ((S::TW_ENTRIES * 8 + 15) / 16) * 16 + (K::B / 2) * S::PADDED * 8;
-        int hg = persistent_grid(hk, wg, hlds, fp.cascades * HalfCfg<LOGN>::STRIPS * 2, cus);
-        const int slices = hs_blocks * (K::WG1 / wg);
-        if (hg > slices)
-          hg = slices;
-        hg &= ~15;  // xcd_pair_slot needs a multiple of 16 blocks
-        if (hg < 16)
-          return hipErrorInvalidValue;
-        hipLaunchKernelGGL(hk, dim3(hg), dim3(wg), hlds, stream, fp, h0, gab, gcd, ge, tw, hs, HalfSlab{},
-                           (unsigned char*)nullptr, 1, seed);
-        return hipGetLastError();
-      }
-      // H pairs in LDS (HL): production kHalfHL; variants 25..31 as named in halfbench hkeep, 32 none
-      // the chain above with HL = 0 (34..36: production's H pairs with the field layouts of 4, 6, 7)
-      const bool named = (variant >= 1 && variant <= 7) || (variant >= 23 && variant <= 32);
-      const int hl = seed ? (variant == 33 ? 0 : kHalfHL)
-                     : !hs ? 0 : !named ? kHalfHL : (variant >= 25 && variant <= 31 && variant != 28) ? 1 : 0;
-      const int lds = ((S::TW_ENTRIES * 8 + 15) / 16) * 16 + K::LDS1 + hl * K::WG1 * 16;
-      int grid = persistent_grid(kern, K::WG1, lds, fp.cascades * HalfCfg<LOGN>::STRIPS, cus);
-      // hs holds hs_blocks slices for 1024-thread workgroups (half_hs_bytes); a block uses 16 x WG1
-      // entries, so below 4096 each slice serves 1024 / WG1 blocks (variant 37: one, as before)
-      const int slices = variant == 37 ? hs_blocks : hs_blocks * (1024 / K::WG1);
-      if (hs && grid > slices)
-        grid = slices;
-      if (grid < 1)
+      if (!hs)  // the H scratch (half_hs_bytes)
         return hipErrorInvalidValue;
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(K::WG1), lds, stream, fp, h0, gab, gcd, ge, tw, hs, HalfSlab{},
-                         (unsigned char*)nullptr, 1, seed);  // gcd/ge: (D, E) / C
-      return hipGetLastError();
+      constexpr int RG = kHalfRG, RGC = kHalfRGC, B = K::B;
+      // whole grids below 4096 keep 2 H pairs in VGPRs: 128 VGPRs, so two (2048) or four (1024)
+      // workgroups fit a CU (with 4: 134-136 VGPRs, one fewer)
+      constexpr int HKW = LOGN == 12 ? kHalfHK : 2;
+      auto launch = [&](auto sh) {
+        using G = ColsLaunch<decltype(sh)>;
+        auto kern = k_cols_half<decltype(sh)>;
+        int grid = persistent_grid(kern, G::WG, G::LDS, G::items(fp.cascades, HalfCfg<LOGN>::STRIPS), cus);
+        const int slices = variant == 37 ? hs_blocks : G::max_grid(hs_blocks);
+        if (grid > slices)
+          grid = slices;
+        if (grid < 1)
+          return hipErrorInvalidValue;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(G::WG), G::LDS, stream, fp, h0, gab, gcd, ge, tw, hs, HalfSlab{},
+                           (unsigned char*)nullptr, 1, seed);  // gcd/ge: (D, E) / C
+        return hipGetLastError();
+      };
+      if (seed)
+        return variant == 33 ? launch(ColsAb<LOGN, RG, RGC, B, 0, 0, 4, B, false, true>{})
+                             : launch(ColsAb<LOGN, RG, RGC, B, kHalfHL, kHalfHKSeed, 4, B, false, true>{});
+      switch (variant)
+      {
+      case 25: return launch(ColsAb<LOGN, RG, RGC, B, 1, 0>{});
+      case 26: return launch(ColsAb<LOGN, RG, RGC, B, 1, 1>{});
+      case 27: return launch(ColsAb<LOGN, RG, RGC, B, 1, 2>{});
+      case 28: return launch(ColsAb<LOGN, RG, RGC, B, 0, 2>{});
+      case 29: return launch(ColsAb<LOGN, RG, RGC, B, 1, 3>{});
+      case 30: return launch(ColsAb<LOGN, RG, RGC, B, 1, 4>{});
+      case 31: return launch(ColsAb<LOGN, RG, RGC, B, 1, 5>{});
+      case 32: return launch(ColsAb<LOGN, RG, RGC, B, 0, 0>{});
+      case 34: return launch(ColsAb<LOGN, 2, 2, B, kHalfHL, kHalfHK>{});
+      case 35: return launch(ColsAb<LOGN, 4, 4, B, kHalfHL, kHalfHK>{});
+      case 36: return launch(ColsAb<LOGN, 1, 1, B, kHalfHL, kHalfHK>{});
+      default: return launch(ColsAb<LOGN, RG, RGC, B, kHalfHL, HKW>{});
+      }
     }
   });
 }
 
+// k_rows_half (two-row workgroups) on the whole-strip fields; variant 7: streamed loads, 8..11: the field
+// layouts (2, 2), (2, 4), (4, 4), (1, 1) (launch_half_columns_ab 34..36), 13 / 14: the FB = 2 layouts of
+// k_cols_half2 (launch_half_columns_ab 13 / 14)
 hipError_t launch_half_rows_ab(int logn, const FrameParams& fp, const float4* gab, const float4* gcd, const float2* ge,
                             const float4* rcorr, float4* maps, float* jac, const FoamParams& foam, const float2* tw,
-                            hipStream_t stream, int cus, int ablation = 0)
+                            hipStream_t stream, int cus, int variant = 0)
 {
   return with_logn(logn, [&](auto L) -> hipError_t {
     constexpr int LOGN = decltype(L)::value;
@@ -329,54 +314,20 @@ hipError_t launch_half_rows_ab(int logn, const FrameParams& fp, const float4* ga
       return hipErrorInvalidValue;
     else
     {
-      using K = ColFirstCfg<LOGN>;
       using S = FftShape<LOGN>;
-      // ablation (tools/microbench; 1-3 on the production shape): 1 no HBM loads, 2 no x transform,
-      // 3 no mirror exchange,
-      // 4 / 5 ColFirstCfg's rows per workgroup (one 1024-thread workgroup per CU) / one row
-      // 0 (production): one item per row block for both images (C loaded once); 6: one image per
-      // item (C loaded by both items of a row block)
-      constexpr int R4 = K::RPW2;
-      // production at N = 4096: one row (both images) per 256-thread workgroup, four workgroups per
-      // CU, the 4 rows of a gc line on one XCD (GRP 4): 1.407 -> 1.377 ms per 8 x 4096^2, maps
-      // bit-identical (halfbench rowv 16); 17 = the two-row workgroups (production below 4096)
-      constexpr bool ONE_ROW = LOGN == 12;
-      const int rpw = ablation == 4 ? R4
-                      : (ablation == 5 || ablation == 16 || ablation == 18 || ablation == 19 || (ablation == 0 && ONE_ROW)) ? 1
-                                                                                                             : 2;
-      const int per_item = (ablation <= 3 || ablation >= 7) ? 1 : 2;
-      // production loads use the default policy: C's 128-B lines are shared by the paired items
-      // (xcd_pair_slot) and streamed loads lost them before the partner's read (-5 %,
-      // tools/microbench/halfbench); 7: streamed loads
-      // 8..11: the field layouts of launch_half_columns' variants 4..7
       constexpr int RG = kHalfRG, RGC = kHalfRGC;
-      // 16: one row (both images) per 256-thread workgroup, four per CU, rows of a gc line on one XCD
-      auto kern = ablation == 0 && ONE_ROW ? k_rows_half<LOGN, 0, kStream, 0, 1, true, false, RG, RGC, 4, 4>
-                  : ablation == 0 || ablation == 17 ? k_rows_half<LOGN, 0, kStream, 0, 2, true, false, RG, RGC>
-                  : ablation == 16 ? k_rows_half<LOGN, 0, kStream, 0, 1, true, false, RG, RGC, 4, 4>
-                  // 18 / 19: one row per 256-thread workgroup on the half-strip layouts of pass-1 variants
-                  // 12 / 14 (FB 2: gab/gde RG 4; gc RGC 8 / 4), the 4 rows of a 128-B line on one XCD
-                  : ablation == 18 ? k_rows_half<LOGN, 0, kStream, 0, 1, true, false, 4, 8, 2, 4>
-                  : ablation == 19 ? k_rows_half<LOGN, 0, kStream, 0, 1, true, false, 4, 4, 2, 4>
-                  : ablation == 8 ? k_rows_half<LOGN, 0, kStream, 0, 2, true, false, 2, 2>
-                  : ablation == 9 ? k_rows_half<LOGN, 0, kStream, 0, 2, true, false, 2, 4>
-                  : ablation == 10 ? k_rows_half<LOGN, 0, kStream, 0, 2, true, false, 4, 4>
-                  : ablation == 11 ? k_rows_half<LOGN, 0, kStream, 0, 2, true, false, 1, 1>
-                  : ablation == 12 ? k_rows_half<LOGN, 0, kStream, 0, 2, true, false, 4, 8, 2, 4>
-                  : ablation == 13 ? k_rows_half<LOGN, 0, kStream, 0, 2, true, false, 2, 4, 2, 2>
-                  : ablation == 14 ? k_rows_half<LOGN, 0, kStream, 0, 2, true, false, 4, 4, 2, 2>
-                  : ablation == 15 ? k_rows_half<LOGN, 0, kStream, 0, 2, true, false, RG, RGC, 4, 2, false>
-                  : ablation == 7 ? k_rows_half<LOGN, kStream, kStream, 0, 2, true, false, RG, RGC>
-                  : ablation == 6 ? k_rows_half<LOGN, kStream, kStream, 0, 2, false, false, RG, RGC>
-                  : ablation == 1 ? k_rows_half<LOGN, 0, kStream, 1, 2, true, false, RG, RGC>
-                  : ablation == 2 ? k_rows_half<LOGN, 0, kStream, 2, 2, true, false, RG, RGC>
-                  : ablation == 3 ? k_rows_half<LOGN, 0, kStream, 3, 2, true, false, RG, RGC>
-                  : ablation == 4 ? k_rows_half<LOGN, kStream, kStream, 0, R4>
-                                  : k_rows_half<LOGN, kStream, kStream, 0, 1>;
-      const int lds = ((S::TW_ENTRIES * 8 + 15) / 16) * 16 + lds_row_slots<LOGN>(rpw) * 8;
-      const int grid = persistent_grid(kern, S::T * rpw, lds, fp.cascades * per_item * (S::N / rpw), cus);
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(S::T * rpw), lds, stream, fp, gab, gcd, ge, rcorr, maps, jac, foam, tw,
-                         S::N, RowSrc{}, (const float2*)nullptr);
+      auto kern = variant == 7    ? k_rows_half<LOGN, kStream, false, RG, RGC>
+                  : variant == 8  ? k_rows_half<LOGN, 0, false, 2, 2>
+                  : variant == 9  ? k_rows_half<LOGN, 0, false, 2, 4>
+                  : variant == 10 ? k_rows_half<LOGN, 0, false, 4, 4>
+                  : variant == 11 ? k_rows_half<LOGN, 0, false, 1, 1>
+                  : variant == 13 ? k_rows_half<LOGN, 0, false, 2, 4, 2>
+                  : variant == 14 ? k_rows_half<LOGN, 0, false, 4, 4, 2>
+                                  : k_rows_half<LOGN, 0, false, RG, RGC>;
+      const int lds = ((S::TW_ENTRIES * 8 + 15) / 16) * 16 + lds_row_slots<LOGN>(2) * 8;
+      const int grid = persistent_grid(kern, S::T * 2, lds, fp.cascades * (S::N / 2), cus);
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(S::T * 2), lds, stream, fp, gab, gcd, ge, rcorr, maps, jac, foam, tw, S::N,
+                         RowSrc{});
       return hipGetLastError();
     }
   });

@@ -1,8 +1,7 @@
-// rm16bench.hip — the row pass of whole 16384^2 grids (k_rows_half, RM layout, one row of both
-// images per 1024-thread item): the plain x transform (14 barriers per image) against XS (the
-// four-step x transform with per-wave sub-transforms, 6 barriers), with timing ablations: no HBM
-// loads (ABL 1), no x transform (ABL 2). Ablated outputs are wrong by construction. Builds with
-// -DOCEAN_ABLATE_EXCHANGE / -DOCEAN_ABLATE_BARRIER price the exchanges and barriers.
+// rm16bench.hip — the row pass of whole 16384^2 grids (RM layout, one row of both images per
+// 1024-thread item): k_rows_xs (the four-step x transform with per-wave sub-transforms) with its
+// prefetch (PF) and early-load (EARLY) forms, its earlier forms and k_rows_xp (ab_kernels.h,
+// k_rows_xp.h).
 // Usage: rm16bench
 #include "all_kernels.h"
 
@@ -130,28 +129,13 @@ int main()
   foam.displacement[0] = 0.4f;
   float2* tw = table(LOGN);
   float2* tw2 = table(LOGN - 4);
-  const int lds = ((S::TW_ENTRIES * 8 + 15) / 16) * 16 + lds_row_slots<LOGN>(1) * 8;
   const RowSrc rs{reinterpret_cast<const unsigned char*>(rab), reinterpret_cast<const unsigned char*>(rde),
                   reinterpret_cast<const unsigned char*>(rc), 0, N / 2, PITCH, 0};
-  auto mk = [&](auto kern, int per = 1) {
-    CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    return [=] {
-      hipLaunchKernelGGL(kern, dim3(C * N * per), dim3(S::T), lds, 0, fp, rab, rde, rc, spec, maps, jac, foam, tw, N,
-                         rs, (const float2*)nullptr);
-    };
-  };
   struct V
   {
     std::string name;
     std::function<void()> run;
     std::vector<float> t;
-  };
-  auto mkx = [&](auto kern) {
-    CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, XsCfg<LOGN>::LDS));
-    return [=] {
-      hipLaunchKernelGGL(kern, dim3(C * N), dim3(S::T), XsCfg<LOGN>::LDS, 0, fp, rab, rde, rc, spec, maps, jac, foam, tw,
-                         N, rs, tw2);
-    };
   };
   auto mkn = [&](auto kern) {  // k_rows_xs (spec, maps, jac, foam, tw, rows, rs, tw2)
     CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, XsCfg<LOGN>::LDS));
@@ -184,12 +168,6 @@ int main()
     CHECK(hipFree(bad));
   }
   std::vector<V> vs = {
-      {"row pass, plain transform (round 2)", mk(k_rows_half<LOGN, kStream, kStream, 0, 1, true, true>), {}},
-      {"XS (four-step x transform)", mkx(k_rows_half<LOGN, kStream, kStream, 0, 1, true, true, 1, 1, 4, 2, true, true>), {}},
-      {"XS, default-policy loads", mkx(k_rows_half<LOGN, 0, kStream, 0, 1, true, true, 1, 1, 4, 2, true, true>), {}},
-      {"XS ABL 1: no HBM loads", mkx(k_rows_half<LOGN, kStream, kStream, 1, 1, true, true, 1, 1, 4, 2, true, true>), {}},
-      {"ABL 1: no HBM loads", mk(k_rows_half<LOGN, kStream, kStream, 1, 1, true, true>), {}},
-      {"ABL 2: no x transform", mk(k_rows_half<LOGN, kStream, kStream, 2, 1, true, true>), {}},
       {"k_rows_xs (C loaded per image)", mkn(k_rows_xs<LOGN, 0>), {}},
       {"k_rows_xs, 2 of 8 loads prefetched", mkn(k_rows_xs<LOGN, 2>), {}},
       {"k_rows_xs, 3 of 8 loads prefetched", mkn(k_rows_xs<LOGN, 3>), {}},
@@ -210,7 +188,7 @@ int main()
       {"k_rows_xs PF 0 EARLY 2, persistent grid (CUs)", mkg(k_rows_xs<LOGN, 0, 2>, cus), {}},
       {"k_rows_xs EARLY 4 (C kept for image 1), persistent", mkg(k_rows_xs<LOGN, 0, 4>, cus), {}},
   };
-  // XS vs the plain transform: same lanes, different rounding order (max |diff| vs max |value|)
+  // max |diff| vs max |value| of two variants' maps
   auto snapf = [&](const void* p, size_t n) {
     std::vector<float> h(n / 4);
     CHECK(hipMemcpy(h.data(), p, n, hipMemcpyDeviceToHost));
@@ -240,25 +218,20 @@ int main()
     std::printf("%s: maps max|diff| %.3g of max|v| %.3g; jac %.3g of %.3g%s\n", what, dm, am, dj, aj,
                 m0 == m1 && j0 == j1 ? " (bit-identical)" : "");
   };
-  compare(0, 1, "XS vs plain");
-  compare(1, 6, "k_rows_xs vs XS");
-  compare(1, 7, "k_rows_xs PF 2 vs XS");
-  compare(1, 8, "k_rows_xs PF 3 vs XS");
-  compare(7, 9, "k_rows_xs PF 2: shift vs division");
-  compare(1, 2, "XS streamed vs default-policy loads");
-  compare(7, 10, "k_rows_xp PF 0 vs k_rows_xs PF 2");
-  compare(7, 11, "k_rows_xp PF 2 vs k_rows_xs PF 2");
-  compare(10, 12, "k_rows_xp PF 3 vs PF 0");
-  compare(13, 7, "k_rows_xs PF 2 (streaming T_in) vs round 3");
-  compare(7, 14, "k_rows_xs PF 2: persistent vs one-shot grid");
-  compare(7, 17, "k_rows_xs PF 2 EARLY 1 vs PF 2");
-  compare(7, 18, "k_rows_xs PF 2 EARLY 2 vs PF 2");
-  compare(7, 19, "k_rows_xs PF 0 EARLY 1 vs PF 2");
-  compare(7, 20, "k_rows_xs PF 0 EARLY 2 vs PF 2");
-  compare(7, 21, "k_rows_xs EARLY 3 persistent vs PF 2");
-  compare(7, 22, "k_rows_xs EARLY 3 one-shot vs PF 2");
-  compare(7, 23, "k_rows_xs PF 0 EARLY 2 persistent vs PF 2");
-  compare(7, 24, "k_rows_xs EARLY 4 persistent vs PF 2");
+  compare(1, 3, "k_rows_xs PF 2: shift vs division");
+  compare(1, 4, "k_rows_xp PF 0 vs k_rows_xs PF 2");
+  compare(1, 5, "k_rows_xp PF 2 vs k_rows_xs PF 2");
+  compare(4, 6, "k_rows_xp PF 3 vs PF 0");
+  compare(7, 1, "k_rows_xs PF 2 (streaming T_in) vs round 3");
+  compare(1, 8, "k_rows_xs PF 2: persistent vs one-shot grid");
+  compare(1, 11, "k_rows_xs PF 2 EARLY 1 vs PF 2");
+  compare(1, 12, "k_rows_xs PF 2 EARLY 2 vs PF 2");
+  compare(1, 13, "k_rows_xs PF 0 EARLY 1 vs PF 2");
+  compare(1, 14, "k_rows_xs PF 0 EARLY 2 vs PF 2");
+  compare(1, 15, "k_rows_xs EARLY 3 persistent vs PF 2");
+  compare(1, 16, "k_rows_xs EARLY 3 one-shot vs PF 2");
+  compare(1, 17, "k_rows_xs PF 0 EARLY 2 persistent vs PF 2");
+  compare(1, 18, "k_rows_xs EARLY 4 persistent vs PF 2");
   for (int r = 0; r < 5; r++)
     for (auto& v : vs)
       v.t.push_back(time_ms(v.run, 3));

@@ -40,9 +40,15 @@ def base_name(symbol):
 
 
 def first_arg(symbol):
-    """The first template argument (log2 N of every frame kernel), or None."""
+    """The first template argument (log2 N of every frame kernel), or None. A kernel instantiated with a
+    shape type (k_cols_half<oceanfft::ColsWhole<12, false> >) yields the shape's first argument."""
     s = symbol.split("(")[0]
-    return s.split("<", 1)[1].split(",")[0].split(">")[0].strip() if "<" in s else None
+    if "<" not in s:
+        return None
+    rest = s.split("<", 1)[1]
+    while "<" in rest.split(",")[0]:
+        rest = rest.split("<", 1)[1]
+    return rest.split(",")[0].split(">")[0].strip()
 
 
 def template_args(symbol):
