@@ -16,12 +16,18 @@
 //
 // Usage: waveapp_headless [--n 256] [--frames 600] [--dt 0.0166667] [--freeze A:B]...
 //                         [--edit F:G.field=value]... [--reseed reference|on-edit]
-//                         [--mesh RES (0 = no surface step)] [--dump DIR]
+//                         [--mesh RES (0 = no surface step)] [--probes K] [--dump DIR]
 // Prints one JSON line. --dump DIR writes height_G.npy, disp_G.npy, jac_G.npy (G = 0..2),
 // surface.npy ((RES+1)^2 x 8 floats) and scene.json for the last frame.
+// --probes K (default 0: nothing changes): after the last frame, the water surface above K points on a
+// 30 m circle around the camera (a ring of buoys; SurfaceSampler::Query, 8 iterations, tolerance 0).
+// The JSON line gains "probes" and "probe_max_residual"; --dump adds probes.npy (K x 8) and
+// probe_xz.npy (K x 2).
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -89,14 +95,15 @@ bool write_npy(const std::string& path, const float* data, const std::vector<siz
 void usage()
 {
   std::fprintf(stderr, "usage: waveapp_headless [--n N] [--frames K] [--dt S] [--freeze A:B]... "
-                       "[--edit F:G.field=value]... [--reseed reference|on-edit] [--mesh RES] [--dump DIR]\n");
+                       "[--edit F:G.field=value]... [--reseed reference|on-edit] [--mesh RES] [--probes K] "
+                       "[--dump DIR]\n");
 }
 
 }  // namespace
 
 int main(int argc, char** argv)
 {
-  int n = 256, frames = 600, mesh = 1024;
+  int n = 256, frames = 600, mesh = 1024, probes = 0;
   float dt = 1.0f / 60.0f;
   bool reseed_every_frame = true;
   std::string dump;
@@ -115,6 +122,7 @@ int main(int argc, char** argv)
     else if (a == "--frames") frames = std::atoi(v);
     else if (a == "--dt") dt = std::strtof(v, nullptr);
     else if (a == "--mesh") mesh = std::atoi(v);
+    else if (a == "--probes") probes = std::atoi(v);
     else if (a == "--dump") dump = v;
     else if (a == "--reseed") reseed_every_frame = std::string(v) != "on-edit";
     else if (a == "--freeze")
@@ -145,6 +153,11 @@ int main(int argc, char** argv)
       return 2;
     }
     i++;
+  }
+  if (probes < 0)
+  {
+    usage();
+    return 2;
   }
 
   try
@@ -212,6 +225,35 @@ int main(int argc, char** argv)
     }
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 
+    // the ring of buoys: which water is above each of them now (not part of the timed frames)
+    std::vector<float> probeXZ, probeOut;
+    float probeMaxResidual = 0.0f;
+    if (probes > 0)
+    {
+      probeXZ.resize((size_t)probes * 2);
+      probeOut.resize((size_t)probes * 8);
+      for (int k = 0; k < probes; k++)
+      {
+        const double a = 2.0 * 3.14159265358979323846 * k / probes;
+        probeXZ[2 * k] = (float)(camera[0] + 30.0 * std::cos(a));
+        probeXZ[2 * k + 1] = (float)(camera[2] + 30.0 * std::sin(a));
+      }
+      float* xzDevice = nullptr;
+      if (hipMalloc(reinterpret_cast<void**>(&xzDevice), probeXZ.size() * sizeof(float)) != hipSuccess ||
+          hipMemcpy(xzDevice, probeXZ.data(), probeXZ.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+      {
+        std::fprintf(stderr, "waveapp_headless: cannot upload the probe positions\n");
+        return 1;
+      }
+      device.BeginCommandBuffer();
+      const Vision::ID q = sampler.Query(generators, xzDevice, probes, 8, 0.0f);
+      device.SubmitCommandBuffer();
+      device.GetTexture2DDataRaw(q, probeOut.data());
+      (void)hipFree(xzDevice);
+      for (int k = 0; k < probes; k++)
+        probeMaxResidual = std::max(probeMaxResidual, probeOut[8 * k + 7]);
+    }
+
     if (!dump.empty())
     {
       const size_t texels = (size_t)n * n;
@@ -238,6 +280,12 @@ int main(int argc, char** argv)
         device.GetTexture2DDataRaw(surface, v.data());
         write_npy(dump + "/surface.npy", v.data(), {pts, 8});
       }
+      if (probes > 0 && !(write_npy(dump + "/probes.npy", probeOut.data(), {(size_t)probes, 8}) &&
+                          write_npy(dump + "/probe_xz.npy", probeXZ.data(), {(size_t)probes, 2})))
+      {
+        std::fprintf(stderr, "cannot write %s\n", dump.c_str());
+        return 1;
+      }
       FILE* js = std::fopen((dump + "/scene.json").c_str(), "w");
       if (js)
       {
@@ -253,14 +301,21 @@ int main(int argc, char** argv)
         std::fclose(js);
       }
     }
+    std::string probeJson;
+    if (probes > 0)
+    {
+      char b[96];
+      std::snprintf(b, sizeof b, ", \"probes\": %d, \"probe_max_residual\": %.9g", probes, probeMaxResidual);
+      probeJson = b;
+    }
     std::printf("{\"app\": \"waveapp_headless\", \"n\": %d, \"cascades\": 3, \"frames\": %d, \"frozen_frames\": %d, "
                 "\"reseeded_frames\": %d, \"reseed\": \"%s\", \"mesh_vertices\": %lld, \"seconds\": %.6f, "
                 "\"ms_per_frame\": %.6f, \"frames_per_s\": %.3f, \"height_field_points_per_s\": %.6e, "
-                "\"final_time\": [%.9g, %.9g, %.9g]}\n",
+                "\"final_time\": [%.9g, %.9g, %.9g]%s}\n",
                 n, frames, frozen, reseeds, reseed_every_frame ? "reference (every frame)" : "on-edit",
                 mesh > 0 ? (long long)(mesh + 1) * (mesh + 1) : 0LL, secs, 1e3 * secs / frames, frames / secs,
                 3.0 * n * n * frames / secs, generators[0]->GetOceanSettings().time,
-                generators[1]->GetOceanSettings().time, generators[2]->GetOceanSettings().time);
+                generators[1]->GetOceanSettings().time, generators[2]->GetOceanSettings().time, probeJson.c_str());
     for (auto* g : generators)
       delete g;
   }

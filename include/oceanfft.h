@@ -356,6 +356,34 @@ int ocean_surface_sample(ocean_generator* const* gens, const int* cascades, int 
  * camera = {viewInverse[3].x, .y, .z, forward.x, forward.z} with forward = -viewInverse[0]. */
 int ocean_surface_sample_plane(ocean_generator* const* gens, const int* cascades, int count, const float camera[5],
                                int res, float* out);
+/* The opposite direction: the water surface above world positions. ocean_surface_sample carries a
+ * base point p to V(p) = (p.x + sum scale*Dx, sum h, p.z + sum scale*Dz, ...)
+ * (waveShader.glsl:101-110); a floating body asks which p lands on its q = (x, z), i.e. inverts the horizontal displacement.
+ * Per point, with V(p) the 8 floats ocean_surface_sample returns for base position p, all in
+ * unfused fp32:
+ *     p = q
+ *     repeat at most `iterations` times:
+ *         r = q - (V(p)[0], V(p)[2])
+ *         if max(|r.x|, |r.z|) <= tolerance: stop
+ *         p = p + r
+ *     V = V(p)
+ *     out = (p.x, V[1], p.z, V[3],  V[4], V[5], V[6],  max(|q.x - V[0]|, |q.z - V[2]|))
+ * Slots 0, 2: the recovered base point; 1: the water height above q; 3 and 4-6: the Jacobian
+ * average and the slope normal at the displaced position (the fragment stage, :127-144, unchanged);
+ * 7: the residual in metres (ocean_surface_sample leaves this slot 0). iterations == 0 is the
+ * forward sample at q with the residual filled in. This is the plain fixed point: it converges
+ * where the displacement is a contraction (roughly, where the Jacobian stays well above 0) and does
+ * not converge on folded crests, where it oscillates. The call does not fail there: the residual
+ * tells the caller, point by point. xz: points x 2 floats, out: points x 8 floats, device memory;
+ * (generator, cascade) rules and stream as ocean_surface_sample; the same atlas, which pays
+ * sooner here (up to iterations + 1 samplings per point): from 16384 points and one point per 48
+ * map texels at 2 or more iterations, from 65536 and one per 24 below. The same bits either way.
+ * OCEAN_ERR_INVALID, before any device call: null gens / cascades, iterations outside 0..64, a
+ * negative or non-finite tolerance, negative points, null xz / out with points > 0. points == 0
+ * launches nothing.
+ * No reference counterpart. */
+int ocean_surface_query(ocean_generator* const* gens, const int* cascades, int count, const float* xz,
+                        int64_t points, int iterations, float tolerance, float* out);
 
 #ifdef __cplusplus
 }

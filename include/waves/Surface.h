@@ -6,6 +6,7 @@
 // vertices instead of textures.
 #pragma once
 
+#include <cstdint>
 #include <vector>
 
 #include "oceanfft.h"
@@ -30,10 +31,22 @@ public:
   // Enqueued on the device's stream; the texture is owned by the sampler and reused.
   Vision::ID Sample(const std::vector<Generator*>& generators, const float camera[5], int res);
 
+  // The opposite direction (ocean_surface_query, oceanfft.h): the water surface above `points` world
+  // positions xzDevice (x, z pairs in device memory), for floating bodies, buoys and shoreline probes.
+  // The fixed point p <- p + (q - V(p).xz) runs at most `iterations` (0..64) steps per point and stops
+  // once the residual is <= tolerance metres. Returns a buffer texture of 2*points x 1 RGBA32F texels:
+  // per point (base x, water height, base z, jacobian), (nx, ny, nz, residual). The iteration does not
+  // converge on folded crests; the residual says so, the call does not fail. Enqueued on the device's
+  // stream; the texture is owned by the sampler and reused while `points` stays the same.
+  Vision::ID Query(const std::vector<Generator*>& generators, const float* xzDevice, int64_t points, int iterations,
+                   float tolerance);
+
 private:
   Vision::RenderDevice* renderDevice = nullptr;
   Vision::ID vertices = 0;
   int verticesRes = 0;
+  Vision::ID queried = 0;
+  int64_t queriedPoints = 0;
 };
 
 }  // namespace Waves

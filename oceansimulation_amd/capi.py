@@ -89,6 +89,7 @@ SIGNATURES = {
     "ocean_debug_copy": (_i, [_vp, _vp, _sz, _i, _vp]),
     "ocean_surface_sample": (_i, [_vp, _vp, _i, _vp, ctypes.c_int64, _vp]),
     "ocean_surface_sample_plane": (_i, [_vp, _vp, _i, _vp, _i, _vp]),
+    "ocean_surface_query": (_i, [_vp, _vp, _i, _vp, ctypes.c_int64, _i, ctypes.c_float, _vp]),
     "ocean_generator_set_half_spectrum": (_i, [_vp, _i]),
     "ocean_generator_set_four_step": (_i, [_vp, _i]),
     "ocean_generator_set_h0_memo": (_i, [_vp, _i]),

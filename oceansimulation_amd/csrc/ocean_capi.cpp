@@ -2218,11 +2218,11 @@ static int surface_params(ocean_generator* const* gens, const int* cascades, int
   return OCEAN_OK;
 }
 
-// The surface atlas of a request (surface_use_atlas), owned by the plan whose stream runs the request:
-// requests on one plan are stream-ordered, so one buffer serves them all.
-static int surface_atlas(ocean_fft* fft, SurfaceParams& p, int64_t points, const char* who)
+// The surface atlas of a request that uses one (surface_use_atlas / surface_query_use_atlas), owned by the
+// plan whose stream runs the request: requests on one plan are stream-ordered, so one buffer serves them all.
+static int surface_atlas(ocean_fft* fft, SurfaceParams& p, bool use, const char* who)
 {
-  if (!surface_use_atlas(p, points))
+  if (!use)
     return OCEAN_OK;
   const size_t texels = surface_atlas_texels(p);
   if (fft->surf_atlas_texels < texels)
@@ -2251,12 +2251,35 @@ int ocean_surface_sample(ocean_generator* const* gens, const int* cascades, int 
     return rc;
   if (points < 0 || (points > 0 && (!xz || !out)))
     return fail(OCEAN_ERR_INVALID, "ocean_surface_sample: null positions/output or negative count");
-  rc = surface_atlas(fft, p, points, "ocean_surface_sample");
+  rc = surface_atlas(fft, p, surface_use_atlas(p, points), "ocean_surface_sample");
   if (rc != OCEAN_OK)
     return rc;
   HIP_TRY(launch_surface(p, SurfacePlane{}, reinterpret_cast<const float2*>(xz), points, reinterpret_cast<float4*>(out),
                          fft->stream, fft->cus),
           "ocean_surface_sample");
+  return OCEAN_OK;
+}
+
+int ocean_surface_query(ocean_generator* const* gens, const int* cascades, int count, const float* xz, int64_t points,
+                        int iterations, float tolerance, float* out)
+{
+  SurfaceParams p;
+  ocean_fft* fft;
+  int rc = surface_params(gens, cascades, count, p, fft, "ocean_surface_query");
+  if (rc != OCEAN_OK)
+    return rc;
+  if (iterations < 0 || iterations > 64)
+    return fail(OCEAN_ERR_INVALID, "ocean_surface_query: iterations outside 0..64");
+  if (!(tolerance >= 0.0f) || !std::isfinite(tolerance))
+    return fail(OCEAN_ERR_INVALID, "ocean_surface_query: tolerance must be finite and >= 0");
+  if (points < 0 || (points > 0 && (!xz || !out)))
+    return fail(OCEAN_ERR_INVALID, "ocean_surface_query: null positions/output or negative count");
+  rc = surface_atlas(fft, p, surface_query_use_atlas(p, points, iterations), "ocean_surface_query");
+  if (rc != OCEAN_OK)
+    return rc;
+  HIP_TRY(launch_surface_query(p, reinterpret_cast<const float2*>(xz), points, iterations, tolerance,
+                               reinterpret_cast<float4*>(out), fft->stream, fft->cus),
+          "ocean_surface_query");
   return OCEAN_OK;
 }
 
@@ -2274,7 +2297,7 @@ int ocean_surface_sample_plane(ocean_generator* const* gens, const int* cascades
     return fail(OCEAN_ERR_INVALID, "ocean_surface_sample_plane: camera forward has no horizontal component");
   const SurfacePlane plane{res, camera[0], camera[1], camera[2], camera[3], camera[4]};
   const int64_t pts = (int64_t)(res + 1) * (res + 1);
-  rc = surface_atlas(fft, p, pts, "ocean_surface_sample_plane");
+  rc = surface_atlas(fft, p, surface_use_atlas(p, pts), "ocean_surface_sample_plane");
   if (rc != OCEAN_OK)
     return rc;
   HIP_TRY(launch_surface(p, plane, nullptr, pts, reinterpret_cast<float4*>(out), fft->stream, fft->cus),

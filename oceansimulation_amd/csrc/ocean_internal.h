@@ -264,8 +264,13 @@ hipError_t launch_ifft_pre(int logn, int n_images, float4* images, float4* work,
 // from it; bit-identical to the direct path.
 hipError_t launch_surface(const SurfaceParams& p, const SurfacePlane& plane, const float2* xz, int64_t count,
                           float4* out, hipStream_t stream, int cus);
+// ocean_surface_query: the fixed point p <- p + (q - V(p).xz) on the vertex stage, then the fragment stage
+// at the last V(p); the atlas as in launch_surface.
+hipError_t launch_surface_query(const SurfaceParams& p, const float2* xz, int64_t count, int iterations,
+                                float tolerance, float4* out, hipStream_t stream, int cus);
 size_t surface_atlas_texels(const SurfaceParams& p);
 bool surface_use_atlas(const SurfaceParams& p, int64_t points);
+bool surface_query_use_atlas(const SurfaceParams& p, int64_t points, int iterations);
 hipError_t launch_hash(const uint32_t* xy, int count, uint32_t* raw, float2* uv, hipStream_t stream);
 hipError_t launch_debug_copy(void* dst, const void* src, size_t bytes, int workgroups, hipStream_t stream);
 // Generator frame: pass 1 (evolve + y iFFT, destination-block-ordered output), pass 2 (x iFFT +

@@ -304,6 +304,81 @@ __global__ __launch_bounds__(256) void k_surface_atlas(SurfaceParams p)
   }
 }
 
+// Vertex stage (waveShader.glsl:101-110): cascade c samples at the position cascades < c displaced and
+// adds (scale * Dx, h, scale * Dz). (px, pz) enters as the base position, py as 0.
+template <bool ATLAS>
+__device__ __forceinline__ void surface_vertex_stage(const SurfaceParams& p, float& px, float& py, float& pz)
+{
+#pragma clang fp contract(off)
+  const int nn = p.n * p.n;
+  for (int c = 0; c < p.count; c++)
+  {
+    const float u = px / p.c[c].plane, v = pz / p.c[c].plane;
+    const LinearTaps k = linear_repeat_taps(p.n, u, v);
+    float h, dx, dz;
+    if constexpr (ATLAS)
+    {
+      const float4 a = linear_texel(p.atlas + (size_t)(2 * c) * nn, k);
+      h = a.x;
+      dx = a.y;
+      dz = a.z;
+    }
+    else
+    {
+      const float* hm = reinterpret_cast<const float*>(p.c[c].height);
+      const float* dm = reinterpret_cast<const float*>(p.c[c].disp);
+      h = linear_channel<4>(hm, k, 0);
+      dx = linear_channel<4>(hm, k, 3);
+      dz = linear_channel<4>(dm, k, 0);
+    }
+    px += p.c[c].scale * dx;
+    py += h;
+    pz += p.c[c].scale * dz;
+  }
+}
+
+// Fragment stage at the displaced position (waveShader.glsl:127-144): (nx, ny, nz, averaged Jacobian)
+template <bool ATLAS>
+__device__ __forceinline__ float4 surface_fragment_stage(const SurfaceParams& p, float px, float pz)
+{
+#pragma clang fp contract(off)
+  const int nn = p.n * p.n;
+  float d[4] = {0.0f, 0.0f, 0.0f, 0.0f}, jac = 0.0f;
+  for (int c = 0; c < p.count; c++)
+  {
+    const float u = px / p.c[c].plane, v = pz / p.c[c].plane;
+    const LinearTaps k = linear_repeat_taps(p.n, u, v);
+    float hx, dxx, hz, dzz;
+    if constexpr (ATLAS)
+    {
+      const float4 b = linear_texel(p.atlas + (size_t)(2 * c + 1) * nn, k);
+      hx = b.x;
+      hz = b.y;
+      dxx = b.z;
+      dzz = b.w;
+    }
+    else
+    {
+      const float* hm = reinterpret_cast<const float*>(p.c[c].height);
+      const float* dm = reinterpret_cast<const float*>(p.c[c].disp);
+      hx = linear_channel<4>(hm, k, 1);
+      dxx = linear_channel<4>(dm, k, 1);
+      hz = linear_channel<4>(hm, k, 2);
+      dzz = linear_channel<4>(dm, k, 2);
+    }
+    jac += linear_channel<1>(p.c[c].jac, k, 0) / (float)p.count;
+    const float f = p.c[c].scale;
+    d[0] += hx;        // dh/dx
+    d[1] += dxx * f;   // dDx/dx
+    d[2] += hz;        // dh/dz
+    d[3] += dzz * f;   // dDz/dz
+  }
+  const float sx = d[0] / (1.0f + d[1]), sz = d[2] / (1.0f + d[3]);
+  const float nx = -sx, ny = 1.0f, nz = -sz;
+  const float len = sqrtf(nx * nx + ny * ny + nz * nz);
+  return make_float4(nx / len, ny / len, nz / len, jac);
+}
+
 template <bool ATLAS>
 __global__ __launch_bounds__(256) void k_surface(SurfaceParams p, SurfacePlane plane, const float2* __restrict__ xz,
                                                  int64_t count, float4* __restrict__ out)
@@ -343,66 +418,48 @@ __global__ __launch_bounds__(256) void k_surface(SurfaceParams p, SurfacePlane p
       pz = q.y;
     }
     float py = 0.0f;
-    const int nn = p.n * p.n;
-    for (int c = 0; c < p.count; c++)
+    surface_vertex_stage<ATLAS>(p, px, py, pz);
+    const float4 f = surface_fragment_stage<ATLAS>(p, px, pz);
+    out[2 * idx] = make_float4(px, py, pz, f.w);
+    out[2 * idx + 1] = make_float4(f.x, f.y, f.z, 0.0f);
+  }
+}
+
+// The inverse direction (ocean_surface_query, include/oceanfft.h): the base point p whose displaced
+// position V(p).xz is the query q, by the plain fixed point p <- p + (q - V(p).xz), at most `iterations`
+// steps, a lane stopping once max|q - V(p).xz| <= tolerance. Only the vertex stage is iterated (one
+// 16-B load per tap and cascade from the atlas, three dwords from the maps); the fragment stage runs
+// once, at the last V(p). Lanes of a wave stop at different steps: the wave runs until its last lane
+// is done. |a| > tolerance is written as !(|a| <= tolerance), so a NaN residual keeps iterating and
+// reaches slot 7 instead of passing for converged.
+template <bool ATLAS>
+__global__ __launch_bounds__(256) void k_surface_query(SurfaceParams p, const float2* __restrict__ xz, int64_t count,
+                                                       int iterations, float tolerance, float4* __restrict__ out)
+{
+#pragma clang fp contract(off)
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < count;
+       idx += (int64_t)gridDim.x * blockDim.x)
+  {
+    const float2 q = xz[idx];
+    float bx = q.x, bz = q.y;  // the base point p
+    float vx = bx, vy = 0.0f, vz = bz;
+    surface_vertex_stage<ATLAS>(p, vx, vy, vz);
+    for (int it = 0; it < iterations; it++)
     {
-      const float u = px / p.c[c].plane, v = pz / p.c[c].plane;
-      const LinearTaps k = linear_repeat_taps(p.n, u, v);
-      float h, dx, dz;
-      if constexpr (ATLAS)
-      {
-        const float4 a = linear_texel(p.atlas + (size_t)(2 * c) * nn, k);
-        h = a.x;
-        dx = a.y;
-        dz = a.z;
-      }
-      else
-      {
-        const float* hm = reinterpret_cast<const float*>(p.c[c].height);
-        const float* dm = reinterpret_cast<const float*>(p.c[c].disp);
-        h = linear_channel<4>(hm, k, 0);
-        dx = linear_channel<4>(hm, k, 3);
-        dz = linear_channel<4>(dm, k, 0);
-      }
-      px += p.c[c].scale * dx;
-      py += h;
-      pz += p.c[c].scale * dz;
+      const float rx = q.x - vx, rz = q.y - vz;
+      if (fabsf(rx) <= tolerance && fabsf(rz) <= tolerance)
+        break;
+      bx += rx;
+      bz += rz;
+      vx = bx;
+      vy = 0.0f;
+      vz = bz;
+      surface_vertex_stage<ATLAS>(p, vx, vy, vz);
     }
-    float d[4] = {0.0f, 0.0f, 0.0f, 0.0f}, jac = 0.0f;
-    for (int c = 0; c < p.count; c++)
-    {
-      const float u = px / p.c[c].plane, v = pz / p.c[c].plane;
-      const LinearTaps k = linear_repeat_taps(p.n, u, v);
-      float hx, dxx, hz, dzz;
-      if constexpr (ATLAS)
-      {
-        const float4 b = linear_texel(p.atlas + (size_t)(2 * c + 1) * nn, k);
-        hx = b.x;
-        hz = b.y;
-        dxx = b.z;
-        dzz = b.w;
-      }
-      else
-      {
-        const float* hm = reinterpret_cast<const float*>(p.c[c].height);
-        const float* dm = reinterpret_cast<const float*>(p.c[c].disp);
-        hx = linear_channel<4>(hm, k, 1);
-        dxx = linear_channel<4>(dm, k, 1);
-        hz = linear_channel<4>(hm, k, 2);
-        dzz = linear_channel<4>(dm, k, 2);
-      }
-      jac += linear_channel<1>(p.c[c].jac, k, 0) / (float)p.count;
-      const float f = p.c[c].scale;
-      d[0] += hx;        // dh/dx
-      d[1] += dxx * f;   // dDx/dx
-      d[2] += hz;        // dh/dz
-      d[3] += dzz * f;   // dDz/dz
-    }
-    const float sx = d[0] / (1.0f + d[1]), sz = d[2] / (1.0f + d[3]);
-    const float nx = -sx, ny = 1.0f, nz = -sz;
-    const float len = sqrtf(nx * nx + ny * ny + nz * nz);
-    out[2 * idx] = make_float4(px, py, pz, jac);
-    out[2 * idx + 1] = make_float4(nx / len, ny / len, nz / len, 0.0f);
+    const float4 f = surface_fragment_stage<ATLAS>(p, vx, vz);
+    const float ex = fabsf(q.x - vx), ez = fabsf(q.y - vz);
+    out[2 * idx] = make_float4(bx, vy, bz, f.w);
+    out[2 * idx + 1] = make_float4(f.x, f.y, f.z, (ex >= ez || ex != ex) ? ex : ez);
   }
 }
 
@@ -472,6 +529,31 @@ hipError_t launch_surface(const SurfaceParams& p, const SurfacePlane& plane, con
   return hipGetLastError();
 }
 
+hipError_t launch_surface_query(const SurfaceParams& p, const float2* xz, int64_t count, int iterations,
+                                float tolerance, float4* out, hipStream_t stream, int cus)
+{
+  if (count <= 0)
+    return hipSuccess;
+  long blocks = (long)((count + 255) / 256);
+  const long cap = (long)cus * 8;
+  if (blocks > cap)
+    blocks = cap;
+  if (p.atlas)
+  {
+    const long texels = (long)p.count * p.n * p.n;
+    long ab = (texels + 255) / 256;
+    if (ab > (long)cus * 4)
+      ab = (long)cus * 4;
+    hipLaunchKernelGGL(k_surface_atlas, dim3((unsigned)ab), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(k_surface_query<true>, dim3((unsigned)blocks), dim3(256), 0, stream, p, xz, count, iterations,
+                       tolerance, out);
+  }
+  else
+    hipLaunchKernelGGL(k_surface_query<false>, dim3((unsigned)blocks), dim3(256), 0, stream, p, xz, count, iterations,
+                       tolerance, out);
+  return hipGetLastError();
+}
+
 size_t surface_atlas_texels(const SurfaceParams& p) { return (size_t)2 * p.count * p.n * p.n; }
 
 // The repack reads 36 B and writes 32 B per map texel and launches one more kernel; sampling from the
@@ -481,6 +563,22 @@ bool surface_use_atlas(const SurfaceParams& p, int64_t points)
 {
   const size_t texels = surface_atlas_texels(p);
   return points >= 65536 && (uint64_t)points >= 2 * (uint64_t)texels && texels * 16 <= ((size_t)256 << 20);
+}
+
+// A query samples the vertex stage up to iterations + 1 times per point, so the repack pays much sooner
+// than for a forward sample: measured on 3 x 256^2 and 3 x 1024^2 maps with each path forced at 4 Ki ..
+// 1 Mi points and 0 / 1 / 2 / 4 / 8 / 16 iterations (tools/surface_query_bench.py,
+// profiles/surface_query_bench.log), the atlas wins from 16 Ki points (256^2) and 64 Ki points (1024^2) at
+// 2 or more iterations, and from 64 Ki and 128 Ki points at 0 or 1: e.g. 8 iterations on 64 Ki points of
+// the 256^2 scene 56 -> 29 us, on 1025^2 points 900 -> 339 us. The repack costs ~6 us at 256^2 and ~31 us
+// at 1024^2, hence a floor and a share of the atlas texels (2 per map texel and cascade).
+bool surface_query_use_atlas(const SurfaceParams& p, int64_t points, int iterations)
+{
+  const size_t texels = surface_atlas_texels(p);
+  const int64_t floor_points = iterations >= 2 ? 16384 : 65536;
+  const uint64_t per_point = iterations >= 2 ? 96 : 48;  // atlas texels one point pays for
+  return points >= floor_points && (uint64_t)points * per_point >= (uint64_t)texels &&
+         texels * 16 <= ((size_t)256 << 20);
 }
 
 // A plain 16-B copy on a fixed number of 256-thread workgroups (ocean_debug_copy): bench.py paces the

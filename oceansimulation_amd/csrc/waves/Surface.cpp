@@ -1,4 +1,4 @@
-// Waves::SurfaceSampler over ocean_surface_sample_plane (include/oceanfft.h).
+// Waves::SurfaceSampler over ocean_surface_sample_plane / ocean_surface_query (include/oceanfft.h).
 #include "waves/Surface.h"
 
 #include <stdexcept>
@@ -11,6 +11,8 @@ SurfaceSampler::~SurfaceSampler()
 {
   if (vertices)
     renderDevice->DestroyTexture2D(vertices);
+  if (queried)
+    renderDevice->DestroyTexture2D(queried);
 }
 
 Vision::ID SurfaceSampler::Sample(const std::vector<Generator*>& generators, const float camera[5], int res)
@@ -38,6 +40,37 @@ Vision::ID SurfaceSampler::Sample(const std::vector<Generator*>& generators, con
   if (rc != OCEAN_OK)
     throw std::runtime_error(std::string("SurfaceSampler::Sample: ") + ocean_last_error());
   return vertices;
+}
+
+Vision::ID SurfaceSampler::Query(const std::vector<Generator*>& generators, const float* xzDevice, int64_t points,
+                                 int iterations, float tolerance)
+{
+  if (points < 1)
+    throw std::runtime_error("SurfaceSampler::Query: need at least one point");
+  if (!queried || queriedPoints != points)
+  {
+    if (queried)
+      renderDevice->DestroyTexture2D(queried);
+    queried = 0;
+    Vision::Texture2DDesc desc;
+    desc.Width = 2 * (std::size_t)points;
+    desc.Height = 1;
+    desc.PixelType = Vision::PixelType::RGBA32Float;
+    queried = renderDevice->CreateTexture2D(desc);
+    queriedPoints = points;
+  }
+  std::vector<ocean_generator*> gens;
+  std::vector<int> cascades;
+  for (auto* g : generators)
+  {
+    gens.push_back(g->GetHandle());
+    cascades.push_back(0);
+  }
+  const int rc = ocean_surface_query(gens.data(), cascades.data(), (int)gens.size(), xzDevice, points, iterations,
+                                     tolerance, static_cast<float*>(renderDevice->GetTexturePointer(queried)));
+  if (rc != OCEAN_OK)
+    throw std::runtime_error(std::string("SurfaceSampler::Query: ") + ocean_last_error());
+  return queried;
 }
 
 }  // namespace Waves

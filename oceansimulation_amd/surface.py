@@ -1,6 +1,7 @@
 """Surface consumer of the generator maps: resources/waveShader.glsl's vertex
 displacement (:101-110) and fragment slope normal / Jacobian (:127-144), per mesh vertex, through
-ocean_surface_sample / ocean_surface_sample_plane (include/oceanfft.h)."""
+ocean_surface_sample / ocean_surface_sample_plane, and the opposite direction, the water surface above
+world positions, through ocean_surface_query (include/oceanfft.h)."""
 from __future__ import annotations
 
 import ctypes
@@ -11,7 +12,7 @@ from . import hip
 from .capi import check, lib
 from .hip import DeviceBuffer
 
-FLOATS_PER_VERTEX = 8  # x, y, z, jacobian, nx, ny, nz, 0
+FLOATS_PER_VERTEX = 8  # x, y, z, jacobian, nx, ny, nz, 0 (query: base x, height, base z, ..., residual)
 
 
 class SurfaceSampler:
@@ -33,6 +34,11 @@ class SurfaceSampler:
         check(lib().ocean_surface_sample_plane(self._gens, self._cas, len(self.pairs), cam, int(res),
                                                ctypes.c_void_p(out_ptr)), "ocean_surface_sample_plane")
 
+    def query(self, xz_ptr: int, points: int, iterations: int, tolerance: float, out_ptr: int) -> None:
+        check(lib().ocean_surface_query(self._gens, self._cas, len(self.pairs), ctypes.c_void_p(xz_ptr),
+                                        ctypes.c_int64(points), int(iterations), ctypes.c_float(tolerance),
+                                        ctypes.c_void_p(out_ptr)), "ocean_surface_query")
+
     def sample_host(self, xz: np.ndarray) -> np.ndarray:
         xz = np.ascontiguousarray(xz, np.float32)
         pts = xz.shape[0]
@@ -41,6 +47,16 @@ class SurfaceSampler:
         self.sample(src.ptr, pts, out.ptr)
         self.fft.synchronize()
         return out.to_host((pts, FLOATS_PER_VERTEX))
+
+    def query_host(self, xz: np.ndarray, iterations: int = 8, tolerance: float = 0.0) -> np.ndarray:
+        """Per world position (x, z): (base x, water height, base z, jacobian, nx, ny, nz, residual in m)."""
+        xz = np.ascontiguousarray(xz, np.float32).reshape(-1, 2)
+        pts = xz.shape[0]
+        src = DeviceBuffer.from_array(xz) if pts else None
+        out = DeviceBuffer(pts * FLOATS_PER_VERTEX * 4) if pts else None
+        self.query(src.ptr if pts else 0, pts, iterations, tolerance, out.ptr if pts else 0)
+        self.fft.synchronize()
+        return out.to_host((pts, FLOATS_PER_VERTEX)) if pts else np.zeros((0, FLOATS_PER_VERTEX), np.float32)
 
     def plane_host(self, camera, res: int) -> np.ndarray:
         pts = (res + 1) * (res + 1)
