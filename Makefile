@@ -23,13 +23,13 @@ all: $(LIB) $(WAVES) $(ORACLE) $(CPPTEST) $(APP)
 
 DEVICE_H := $(wildcard $(CSRC)/device/*.h) $(CSRC)/ocean_internal.h $(CSRC)/launch_common.h
 # one translation unit per frame path, compiled in parallel
-KERNEL_TUS := ocean_kernels launch_half launch_slab launch_fft
+KERNEL_TUS := ocean_kernels launch_half launch_slab launch_fft launch_mips
 KERNEL_OBJS := $(KERNEL_TUS:%=$(CSRC)/build/%.o)
 $(CSRC)/build/%.o: $(CSRC)/%.hip $(DEVICE_H)
 	@mkdir -p $(CSRC)/build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(CSRC)/build/ocean_capi.o: $(CSRC)/ocean_capi.cpp $(CSRC)/ocean_internal.h include/oceanfft.h
+$(CSRC)/build/ocean_capi.o: $(CSRC)/ocean_capi.cpp $(CSRC)/ocean_internal.h $(CSRC)/device/mip_index.h include/oceanfft.h
 	@mkdir -p $(CSRC)/build
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 

@@ -16,13 +16,17 @@
 //
 // Usage: waveapp_headless [--n 256] [--frames 600] [--dt 0.0166667] [--freeze A:B]...
 //                         [--edit F:G.field=value]... [--reseed reference|on-edit]
-//                         [--mesh RES (0 = no surface step)] [--probes K] [--dump DIR]
+//                         [--mesh RES (0 = no surface step)] [--probes K] [--mips] [--dump DIR]
 // Prints one JSON line. --dump DIR writes height_G.npy, disp_G.npy, jac_G.npy (G = 0..2),
 // surface.npy ((RES+1)^2 x 8 floats) and scene.json for the last frame.
 // --probes K (default 0: nothing changes): after the last frame, the water surface above K points on a
 // 30 m circle around the camera (a ring of buoys; SurfaceSampler::Query, 8 iterations, tolerance 0).
 // The JSON line gains "probes" and "probe_max_residual"; --dump adds probes.npy (K x 8) and
 // probe_xz.npy (K x 2).
+// --mips (default off: nothing changes): after the last frame, every generator's mip pyramid is built
+// (Generator::GenerateMips) and the mesh step runs once more through SurfaceSampler::SampleLod, which
+// samples each vertex at the level its spacing asks for. The JSON line gains "mips" (levels per map);
+// --dump adds height_G_mipL.npy for L = 1 and the top level, and mesh_lod.npy ((RES+1)^2 x 8).
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -96,7 +100,7 @@ void usage()
 {
   std::fprintf(stderr, "usage: waveapp_headless [--n N] [--frames K] [--dt S] [--freeze A:B]... "
                        "[--edit F:G.field=value]... [--reseed reference|on-edit] [--mesh RES] [--probes K] "
-                       "[--dump DIR]\n");
+                       "[--mips] [--dump DIR]\n");
 }
 
 }  // namespace
@@ -105,13 +109,18 @@ int main(int argc, char** argv)
 {
   int n = 256, frames = 600, mesh = 1024, probes = 0;
   float dt = 1.0f / 60.0f;
-  bool reseed_every_frame = true;
+  bool reseed_every_frame = true, mips = false;
   std::string dump;
   std::vector<std::pair<int, int>> freezes;
   std::vector<Edit> edits;
   for (int i = 1; i < argc; i++)
   {
     const std::string a = argv[i];
+    if (a == "--mips")  // the one switch without a value
+    {
+      mips = true;
+      continue;
+    }
     const char* v = i + 1 < argc ? argv[i + 1] : nullptr;
     if (!v)
     {
@@ -254,6 +263,20 @@ int main(int argc, char** argv)
         probeMaxResidual = std::max(probeMaxResidual, probeOut[8 * k + 7]);
     }
 
+    // the pyramids of the last frame's maps and the mesh sampled through them (not part of the timed frames)
+    int mipLevels = 0;
+    Vision::ID surfaceLod = 0;
+    if (mips)
+    {
+      device.BeginCommandBuffer();
+      for (auto* g : generators)
+        g->GenerateMips();
+      if (mesh > 0)
+        surfaceLod = sampler.SampleLod(generators, camera, mesh);
+      device.SubmitCommandBuffer();
+      mipLevels = generators[0]->GetMipLevels();
+    }
+
     if (!dump.empty())
     {
       const size_t texels = (size_t)n * n;
@@ -279,6 +302,31 @@ int main(int argc, char** argv)
         std::vector<float> v(pts * 8);
         device.GetTexture2DDataRaw(surface, v.data());
         write_npy(dump + "/surface.npy", v.data(), {pts, 8});
+      }
+      if (mips)
+      {
+        bool ok = true;
+        for (int i = 0; i < 3; i++)
+          for (int level : {1, mipLevels - 1})
+          {
+            const size_t side = (size_t)n >> level;
+            std::vector<float> m(side * side * 4);
+            device.GetTexture2DDataRaw(generators[i]->GetHeightMip(level), m.data());
+            ok = ok && write_npy(dump + "/height_" + std::to_string(i) + "_mip" + std::to_string(level) + ".npy",
+                                 m.data(), {side, side, 4});
+          }
+        if (mesh > 0)
+        {
+          const size_t pts = (size_t)(mesh + 1) * (mesh + 1);
+          std::vector<float> v(pts * 8);
+          device.GetTexture2DDataRaw(surfaceLod, v.data());
+          ok = ok && write_npy(dump + "/mesh_lod.npy", v.data(), {pts, 8});
+        }
+        if (!ok)
+        {
+          std::fprintf(stderr, "cannot write %s\n", dump.c_str());
+          return 1;
+        }
       }
       if (probes > 0 && !(write_npy(dump + "/probes.npy", probeOut.data(), {(size_t)probes, 8}) &&
                           write_npy(dump + "/probe_xz.npy", probeXZ.data(), {(size_t)probes, 2})))
@@ -308,6 +356,8 @@ int main(int argc, char** argv)
       std::snprintf(b, sizeof b, ", \"probes\": %d, \"probe_max_residual\": %.9g", probes, probeMaxResidual);
       probeJson = b;
     }
+    if (mips)
+      probeJson += ", \"mips\": " + std::to_string(mipLevels);
     std::printf("{\"app\": \"waveapp_headless\", \"n\": %d, \"cascades\": 3, \"frames\": %d, \"frozen_frames\": %d, "
                 "\"reseeded_frames\": %d, \"reseed\": \"%s\", \"mesh_vertices\": %lld, \"seconds\": %.6f, "
                 "\"ms_per_frame\": %.6f, \"frames_per_s\": %.3f, \"height_field_points_per_s\": %.6e, "

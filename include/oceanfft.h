@@ -385,6 +385,61 @@ int ocean_surface_sample_plane(ocean_generator* const* gens, const int* cascades
 int ocean_surface_query(ocean_generator* const* gens, const int* cascades, int count, const float* xz,
                         int64_t points, int iterations, float tolerance, float* out);
 
+/* ---- Mip pyramids of the maps and footprint-aware sampling ----------------------------------
+ * The calls above sample level 0 with GL_LINEAR, like the reference (src/Generator.cpp:116-119 builds
+ * no mip chain). That is right while neighbouring samples sit about a texel apart; the reference's own
+ * mesh (waveShader.glsl:95 stretches the plane by pow(len, 1.2) * camY * 0.04) puts them tens to
+ * thousands of texels apart, where point samples of the maps alias and shimmer from frame to frame.
+ * These calls build the box-filter pyramid of glGenerateMipmap and sample it by a per-point footprint.
+ *
+ * The pyramid, per map of a cascade (heightMap, displacementMap: RGBA32F; jacobian: R32F) and per
+ * channel, in fp32: level 0 is the map, level l + 1 has side N >> (l + 1) and
+ *     L[l+1](x, y) = 0.25f * ((L[l](2x, 2y) + L[l](2x+1, 2y)) + (L[l](2x, 2y+1) + L[l](2x+1, 2y+1)))
+ * from the rounded level below, down to 1 x 1: log2(N) + 1 levels. The sum order is part of the
+ * contract (the result is bit for bit this formula however the levels are fused). */
+/* log2(N) + 1; 0 for a null generator. */
+int ocean_generator_mip_levels(const ocean_generator* gen);
+/* Enqueue, on the generator's stream, the rebuild of the levels >= 1 of all three maps of every
+ * cascade from the current maps: ceil(log2(N) / 6) kernel launches, 36 B read and 12 B written per
+ * point. The storage (a third of the maps', about 12 B per point) is allocated on the first call
+ * (OCEAN_ERR_OOM when that fails) and freed by ocean_generator_destroy. Whole-grid generators only:
+ * a slab generator gets OCEAN_ERR_INVALID before any device call. The pyramid is fresh until the next
+ * call that rewrites the maps (ocean_generator_calculate and the other frame calls); the library
+ * tracks that on the host. No reference counterpart. */
+int ocean_generator_build_mips(ocean_generator* gen);
+/* Level `level` of a cascade's map: level 0 is the map itself (ocean_generator_height_map, ...), a
+ * level >= 1 a row-major image of side N >> level in the pyramid's storage, valid until the generator
+ * is destroyed and holding what the last ocean_generator_build_mips wrote. Null, with
+ * ocean_last_error set, for a null generator, a cascade or level out of range, or a level >= 1 of a
+ * pyramid that was never built. */
+float* ocean_generator_height_mip(ocean_generator* gen, int cascade, int level);
+float* ocean_generator_displacement_mip(ocean_generator* gen, int cascade, int level);
+float* ocean_generator_jacobian_mip(ocean_generator* gen, int cascade, int level);
+/* ocean_surface_sample with a footprint per point: xzf holds points x 3 floats (x, z, footprint) in
+ * device memory, the footprint being the spacing in metres between this sample and its neighbours.
+ * Per point and cascade c, in unfused fp32, with top = log2(N):
+ *     r = (footprint * (float)N) / planeSize_c
+ *     if   !(r >= 1.0f)           : l = 0,   f = 0        (also NaN, negative, 0)
+ *     elif r >= (float)(1 << top) : l = top, f = 0        (also +inf)
+ *     else l = floor(log2 r) (r's exponent), f = r * 2^-l - 1.0f     (exact, in [0, 1))
+ *     value = A when f == 0, else A + f * (B - A)
+ * A: the GL_LINEAR + GL_REPEAT sample of level l (side N >> l), B: of level l + 1. The blend is linear
+ * in the footprint and continuous across levels. The vertex stage reads h, Dx, Dz with cascade c's
+ * (l, f); the fragment stage reads the four slopes and the Jacobian with the same (l, f) at the
+ * displaced position; accumulation, normal and Jacobian average are those of ocean_surface_sample, so
+ * footprint 0 gives its bits. Output: its 8 floats with slot 7 = the footprint as given.
+ * Argument rules, (generator, cascade) rules and stream as ocean_surface_sample; no atlas. Every
+ * generator's pyramid must be built and fresh: otherwise OCEAN_ERR_INVALID, naming the index of the
+ * generator in `gens`, before any device call. No reference counterpart. */
+int ocean_surface_sample_lod(ocean_generator* const* gens, const int* cascades, int count, const float* xzf,
+                             int64_t points, float* out);
+/* ocean_surface_sample_plane with the footprint the warp gives each vertex: the plane's quad size
+ * times the vertex's warp factor, footprint = k * (40.0f / (float)res) with
+ * k = powf(max(len, 1), 1.2f) * max(camera.y, 10) * 0.04f as the warp computes it. Slot 7 = that
+ * footprint. */
+int ocean_surface_sample_plane_lod(ocean_generator* const* gens, const int* cascades, int count,
+                                   const float camera[5], int res, float* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <type_traits>
 #include <utility>
+#include <vector>
 
 #include "oceanfft.h"
 #include "vision/RenderDevice.h"
@@ -92,6 +93,18 @@ public:
   // such as ocean_surface_sample_plane (waves/Surface.h).
   ocean_generator* GetHandle() const { return gen; }
 
+  // Extension (no reference counterpart; the reference builds no mip chain, src/Generator.cpp:116-119):
+  // the box-filter pyramid of the three maps (ocean_generator_build_mips, oceanfft.h), what
+  // glGenerateMipmap would give. GenerateMips enqueues the rebuild of levels 1 .. GetMipLevels() - 1
+  // from the current maps on the device's stream; call it after CalculateOcean and before
+  // SurfaceSampler::SampleLod. Level 0 of a getter is the map itself, level l an image of side N >> l;
+  // the getters throw before the first GenerateMips and for a level out of range.
+  void GenerateMips();
+  int GetMipLevels() const { return ocean_generator_mip_levels(gen); }
+  Vision::ID GetHeightMip(int level) const { return Mip(heightMips, heightMap, level); }
+  Vision::ID GetDisplacementMip(int level) const { return Mip(displacementMips, displacementMap, level); }
+  Vision::ID GetJacobianMip(int level) const { return Mip(jacobianMips, jacobian, level); }
+
 private:
   Vision::RenderDevice* renderDevice = nullptr;
   FFTCalculator* fftCalc = nullptr;
@@ -100,6 +113,9 @@ private:
   Vision::ID heightMap = 0;
   Vision::ID displacementMap = 0;
   Vision::ID jacobian = 0;
+  // levels >= 1 (index level - 1), registered by the first GenerateMips
+  std::vector<Vision::ID> heightMips, displacementMips, jacobianMips;
+  Vision::ID Mip(const std::vector<Vision::ID>& mips, Vision::ID map, int level) const;
 };
 
 }  // namespace Waves

@@ -41,12 +41,21 @@ public:
   Vision::ID Query(const std::vector<Generator*>& generators, const float* xzDevice, int64_t points, int iterations,
                    float tolerance);
 
+  // Sample with the footprint the camera warp gives each vertex (ocean_surface_sample_plane_lod,
+  // oceanfft.h): two levels of each generator's mip pyramid, blended, instead of level 0, so far vertices
+  // no longer point-sample maps they step across by many texels. Every generator needs
+  // Generator::GenerateMips() since its last CalculateOcean. Same texture layout as Sample, with the
+  // footprint in metres in the last float of each vertex; its own texture, reused at the same res.
+  Vision::ID SampleLod(const std::vector<Generator*>& generators, const float camera[5], int res);
+
 private:
   Vision::RenderDevice* renderDevice = nullptr;
   Vision::ID vertices = 0;
   int verticesRes = 0;
   Vision::ID queried = 0;
   int64_t queriedPoints = 0;
+  Vision::ID verticesLod = 0;
+  int verticesLodRes = 0;
 };
 
 }  // namespace Waves

@@ -90,6 +90,13 @@ SIGNATURES = {
     "ocean_surface_sample": (_i, [_vp, _vp, _i, _vp, ctypes.c_int64, _vp]),
     "ocean_surface_sample_plane": (_i, [_vp, _vp, _i, _vp, _i, _vp]),
     "ocean_surface_query": (_i, [_vp, _vp, _i, _vp, ctypes.c_int64, _i, ctypes.c_float, _vp]),
+    "ocean_generator_mip_levels": (_i, [_vp]),
+    "ocean_generator_build_mips": (_i, [_vp]),
+    "ocean_generator_height_mip": (_vp, [_vp, _i, _i]),
+    "ocean_generator_displacement_mip": (_vp, [_vp, _i, _i]),
+    "ocean_generator_jacobian_mip": (_vp, [_vp, _i, _i]),
+    "ocean_surface_sample_lod": (_i, [_vp, _vp, _i, _vp, ctypes.c_int64, _vp]),
+    "ocean_surface_sample_plane_lod": (_i, [_vp, _vp, _i, _vp, _i, _vp]),
     "ocean_generator_set_half_spectrum": (_i, [_vp, _i]),
     "ocean_generator_set_four_step": (_i, [_vp, _i]),
     "ocean_generator_set_h0_memo": (_i, [_vp, _i]),

@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "device/mip_index.h"
 #include "ocean_internal.h"
 
 using namespace oceanfft;
@@ -164,6 +165,10 @@ struct ocean_generator
   bool orows_valid[2] = {false, false};
   int oslot = 0;
   bool h0_dirty = false;  // h0 (or the fused re-seed constants) written on the generator's stream since the side stream last waited
+  // the mip pyramid of the maps (ocean_generator_build_mips): [cascade][heightMap | displacementMap |
+  // jacobian chains], allocated on first use; fresh until the next call that rewrites the maps
+  float* mips = nullptr;
+  bool mips_fresh = false;
   bool profiling = false;
   std::vector<EventPair> pending;
   std::vector<hipEvent_t> pool;
@@ -696,7 +701,7 @@ int ocean_generator_destroy(ocean_generator* g)
     if (p)
       (void)hipFree(p);
   for (void* p : {(void*)g->gab, (void*)g->gcd, (void*)g->ge, (void*)g->spec, (void*)g->hs, (void*)g->h0row, g->seedc,
-                  (void*)g->rm_ab, (void*)g->rm_de, (void*)g->rm_c, (void*)g->parts, (void*)g->xbuf})
+                  (void*)g->rm_ab, (void*)g->rm_de, (void*)g->rm_c, (void*)g->parts, (void*)g->xbuf, (void*)g->mips})
     if (p)
       (void)hipFree(p);
   delete g;
@@ -1020,6 +1025,7 @@ static int generator_rows(ocean_generator* g, const float4* in, const FoamParams
                           hipStream_t row_stream = nullptr, int row_cus = 0)
 {
   ocean_fft* f = g->fft;
+  g->mips_fresh = false;  // every frame path's maps are written here
   const int rcus = row_cus > 0 && row_cus < f->cus ? row_cus : f->cus;
   const FoamParams foam = frame_foam ? *frame_foam : current_foam(g);
   if (uses_gen4(g))
@@ -2302,6 +2308,133 @@ int ocean_surface_sample_plane(ocean_generator* const* gens, const int* cascades
     return rc;
   HIP_TRY(launch_surface(p, plane, nullptr, pts, reinterpret_cast<float4*>(out), fft->stream, fft->cus),
           "ocean_surface_sample_plane");
+  return OCEAN_OK;
+}
+
+// ---- mip pyramid and footprint-aware sampling ----
+int ocean_generator_mip_levels(const ocean_generator* g) { return g ? g->fft->logn + 1 : 0; }
+
+int ocean_generator_build_mips(ocean_generator* g)
+{
+  if (!g)
+    return fail(OCEAN_ERR_INVALID, "ocean_generator_build_mips: null generator");
+  if (g->slab || g->ranks != 1)
+    return fail(OCEAN_ERR_INVALID, "ocean_generator_build_mips: slab generators hold row slabs, not whole maps");
+  ocean_fft* f = g->fft;
+  if (!g->mips)
+  {
+    const hipError_t e = hipMalloc(&g->mips, (size_t)g->cascades * mip_cascade_floats(f->n) * sizeof(float));
+    if (e != hipSuccess)
+    {
+      g->mips = nullptr;
+      return fail(e == hipErrorOutOfMemory ? OCEAN_ERR_OOM : OCEAN_ERR_HIP,
+                  std::string("ocean_generator_build_mips: ") + hipGetErrorString(e));
+    }
+  }
+  g->mips_fresh = false;
+  HIP_TRY(launch_build_mips(f->n, g->cascades, g->maps, g->jac, g->mips, f->stream), "ocean_generator_build_mips");
+  g->mips_fresh = true;
+  return OCEAN_OK;
+}
+
+// Level `level` of map `map` (0 heightMap, 1 displacementMap, 2 jacobian) of cascade c
+static float* generator_mip(ocean_generator* g, int c, int level, int map, const char* who)
+{
+  if (!g || c < 0 || c >= g->cascades)
+  {
+    fail(OCEAN_ERR_INVALID, std::string(who) + ": null generator or cascade out of range");
+    return nullptr;
+  }
+  if (level < 0 || level > g->fft->logn)
+  {
+    fail(OCEAN_ERR_INVALID, std::string(who) + ": level outside 0..log2(N)");
+    return nullptr;
+  }
+  if (level == 0)
+    return map == 0 ? ocean_generator_height_map(g, c)
+                    : (map == 1 ? ocean_generator_displacement_map(g, c) : ocean_generator_jacobian_map(g, c));
+  if (!g->mips)
+  {
+    fail(OCEAN_ERR_INVALID, std::string(who) + ": the pyramid was never built (ocean_generator_build_mips)");
+    return nullptr;
+  }
+  const int n = g->fft->n;
+  const size_t chain = mip_chain_texels(n), off = mip_level_offset(n, level);
+  float* base = g->mips + (size_t)c * mip_cascade_floats(n);
+  return map == 2 ? base + 8 * chain + off : base + (size_t)map * 4 * chain + 4 * off;
+}
+
+float* ocean_generator_height_mip(ocean_generator* g, int c, int level)
+{
+  return generator_mip(g, c, level, 0, "ocean_generator_height_mip");
+}
+
+float* ocean_generator_displacement_mip(ocean_generator* g, int c, int level)
+{
+  return generator_mip(g, c, level, 1, "ocean_generator_displacement_mip");
+}
+
+float* ocean_generator_jacobian_mip(ocean_generator* g, int c, int level)
+{
+  return generator_mip(g, c, level, 2, "ocean_generator_jacobian_mip");
+}
+
+// surface_params of a LOD call: also the chains, which must be built and not older than the maps
+static int surface_params_lod(ocean_generator* const* gens, const int* cascades, int count, SurfaceParams& p,
+                              ocean_fft*& fft, const char* who)
+{
+  const int rc = surface_params(gens, cascades, count, p, fft, who);
+  if (rc != OCEAN_OK)
+    return rc;
+  for (int i = 0; i < count; i++)
+  {
+    ocean_generator* g = gens[i];
+    if (!g->mips || !g->mips_fresh)
+      return fail(OCEAN_ERR_INVALID, std::string(who) + ": generator " + std::to_string(i) +
+                                         (g->mips ? " has a stale mip pyramid (its maps were rewritten since"
+                                                  : " has no mip pyramid (call") +
+                                         " ocean_generator_build_mips)");
+    const size_t chain = mip_chain_texels(fft->n);
+    const float* base = g->mips + (size_t)cascades[i] * mip_cascade_floats(fft->n);
+    p.c[i].height_mip = reinterpret_cast<const float4*>(base);
+    p.c[i].disp_mip = reinterpret_cast<const float4*>(base + 4 * chain);
+    p.c[i].jac_mip = base + 8 * chain;
+  }
+  return OCEAN_OK;
+}
+
+int ocean_surface_sample_lod(ocean_generator* const* gens, const int* cascades, int count, const float* xzf,
+                             int64_t points, float* out)
+{
+  SurfaceParams p;
+  ocean_fft* fft;
+  const int rc = surface_params_lod(gens, cascades, count, p, fft, "ocean_surface_sample_lod");
+  if (rc != OCEAN_OK)
+    return rc;
+  if (points < 0 || (points > 0 && (!xzf || !out)))
+    return fail(OCEAN_ERR_INVALID, "ocean_surface_sample_lod: null positions/output or negative count");
+  HIP_TRY(launch_surface_lod(p, SurfacePlane{}, xzf, points, reinterpret_cast<float4*>(out), fft->stream, fft->cus),
+          "ocean_surface_sample_lod");
+  return OCEAN_OK;
+}
+
+int ocean_surface_sample_plane_lod(ocean_generator* const* gens, const int* cascades, int count, const float camera[5],
+                                   int res, float* out)
+{
+  SurfaceParams p;
+  ocean_fft* fft;
+  const int rc = surface_params_lod(gens, cascades, count, p, fft, "ocean_surface_sample_plane_lod");
+  if (rc != OCEAN_OK)
+    return rc;
+  if (!camera || !out || res < 1 || res > 46340)
+    return fail(OCEAN_ERR_INVALID,
+                "ocean_surface_sample_plane_lod: null camera/output or resolution outside 1..46340");
+  if (camera[3] == 0.0f && camera[4] == 0.0f)
+    return fail(OCEAN_ERR_INVALID, "ocean_surface_sample_plane_lod: camera forward has no horizontal component");
+  const SurfacePlane plane{res, camera[0], camera[1], camera[2], camera[3], camera[4]};
+  const int64_t pts = (int64_t)(res + 1) * (res + 1);
+  HIP_TRY(launch_surface_lod(p, plane, nullptr, pts, reinterpret_cast<float4*>(out), fft->stream, fft->cus),
+          "ocean_surface_sample_plane_lod");
   return OCEAN_OK;
 }
 

@@ -41,6 +41,11 @@ struct SurfaceCascade
   const float* jac;
   float plane;
   float scale;
+  // the LOD calls only (else null): the maps' mip chains, level l >= 1 at mip_level_offset(n, l) texels
+  // (device/mip_index.h)
+  const float4* height_mip;
+  const float4* disp_mip;
+  const float* jac_mip;
 };
 struct SurfaceParams
 {
@@ -268,6 +273,15 @@ hipError_t launch_surface(const SurfaceParams& p, const SurfacePlane& plane, con
 // at the last V(p); the atlas as in launch_surface.
 hipError_t launch_surface_query(const SurfaceParams& p, const float2* xz, int64_t count, int iterations,
                                 float tolerance, float4* out, hipStream_t stream, int cus);
+// ocean_surface_sample_lod / _plane_lod: per point a footprint in metres (xzf: x, z, footprint; the plane
+// mesh derives it from its warp) selects two mip levels per cascade that are blended; p.c[i].*_mip set.
+hipError_t launch_surface_lod(const SurfaceParams& p, const SurfacePlane& plane, const float* xzf, int64_t count,
+                              float4* out, hipStream_t stream, int cus);
+// The mip pyramid of a whole-grid generator's maps (device/k_mips.h): levels 1 .. log2 n of the three
+// maps of every cascade into mips (cascades * mip_cascade_floats(n) floats), ceil(log2 n / 6) launches.
+size_t mip_cascade_floats(int n);
+hipError_t launch_build_mips(int n, int cascades, const float4* maps, const float* jac, float* mips,
+                             hipStream_t stream);
 size_t surface_atlas_texels(const SurfaceParams& p);
 bool surface_use_atlas(const SurfaceParams& p, int64_t points);
 bool surface_query_use_atlas(const SurfaceParams& p, int64_t points, int iterations);

@@ -31,6 +31,9 @@ Generator::~Generator()
   renderDevice->DestroyTexture2D(heightMap);
   renderDevice->DestroyTexture2D(displacementMap);
   renderDevice->DestroyTexture2D(jacobian);
+  for (const auto* mips : {&heightMips, &displacementMips, &jacobianMips})
+    for (Vision::ID id : *mips)
+      renderDevice->DestroyTexture2D(id);
   ocean_generator_destroy(gen);
 }
 
@@ -43,6 +46,35 @@ void Generator::CalculateOcean(float timestep, bool updateOcean)
 {
   if (ocean_generator_calculate(gen, timestep, updateOcean ? 1 : 0) != OCEAN_OK)
     throw std::runtime_error(std::string("Waves::Generator::CalculateOcean: ") + ocean_last_error());
+}
+
+void Generator::GenerateMips()
+{
+  if (ocean_generator_build_mips(gen) != OCEAN_OK)
+    throw std::runtime_error(std::string("Waves::Generator::GenerateMips: ") + ocean_last_error());
+  if (!heightMips.empty())
+    return;
+  for (int level = 1; level < GetMipLevels(); level++)
+  {
+    const std::size_t side = textureSize >> level;
+    heightMips.push_back(renderDevice->RegisterTexture2D(ocean_generator_height_mip(gen, 0, level), side, side,
+                                                         Vision::PixelType::RGBA32Float));
+    displacementMips.push_back(renderDevice->RegisterTexture2D(ocean_generator_displacement_mip(gen, 0, level), side,
+                                                               side, Vision::PixelType::RGBA32Float));
+    jacobianMips.push_back(renderDevice->RegisterTexture2D(ocean_generator_jacobian_mip(gen, 0, level), side, side,
+                                                           Vision::PixelType::R32Float));
+  }
+}
+
+Vision::ID Generator::Mip(const std::vector<Vision::ID>& mips, Vision::ID map, int level) const
+{
+  if (level == 0)
+    return map;
+  if (level < 0 || level >= GetMipLevels())
+    throw std::runtime_error("Waves::Generator: mip level outside 0..log2(N)");
+  if (mips.empty())
+    throw std::runtime_error("Waves::Generator: the mip pyramid was never built (GenerateMips)");
+  return mips[(std::size_t)level - 1];
 }
 
 void Generator::LoadShaders(bool) {}

@@ -1,4 +1,5 @@
-// Waves::SurfaceSampler over ocean_surface_sample_plane / ocean_surface_query (include/oceanfft.h).
+// Waves::SurfaceSampler over ocean_surface_sample_plane / ocean_surface_query /
+// ocean_surface_sample_plane_lod (include/oceanfft.h).
 #include "waves/Surface.h"
 
 #include <stdexcept>
@@ -13,6 +14,8 @@ SurfaceSampler::~SurfaceSampler()
     renderDevice->DestroyTexture2D(vertices);
   if (queried)
     renderDevice->DestroyTexture2D(queried);
+  if (verticesLod)
+    renderDevice->DestroyTexture2D(verticesLod);
 }
 
 Vision::ID SurfaceSampler::Sample(const std::vector<Generator*>& generators, const float camera[5], int res)
@@ -40,6 +43,34 @@ Vision::ID SurfaceSampler::Sample(const std::vector<Generator*>& generators, con
   if (rc != OCEAN_OK)
     throw std::runtime_error(std::string("SurfaceSampler::Sample: ") + ocean_last_error());
   return vertices;
+}
+
+Vision::ID SurfaceSampler::SampleLod(const std::vector<Generator*>& generators, const float camera[5], int res)
+{
+  if (!verticesLod || verticesLodRes != res)
+  {
+    if (verticesLod)
+      renderDevice->DestroyTexture2D(verticesLod);
+    verticesLod = 0;
+    Vision::Texture2DDesc desc;
+    desc.Width = 2 * (res + 1);
+    desc.Height = res + 1;
+    desc.PixelType = Vision::PixelType::RGBA32Float;
+    verticesLod = renderDevice->CreateTexture2D(desc);
+    verticesLodRes = res;
+  }
+  std::vector<ocean_generator*> gens;
+  std::vector<int> cascades;
+  for (auto* g : generators)
+  {
+    gens.push_back(g->GetHandle());
+    cascades.push_back(0);
+  }
+  const int rc = ocean_surface_sample_plane_lod(gens.data(), cascades.data(), (int)gens.size(), camera, res,
+                                                static_cast<float*>(renderDevice->GetTexturePointer(verticesLod)));
+  if (rc != OCEAN_OK)
+    throw std::runtime_error(std::string("SurfaceSampler::SampleLod: ") + ocean_last_error());
+  return verticesLod;
 }
 
 Vision::ID SurfaceSampler::Query(const std::vector<Generator*>& generators, const float* xzDevice, int64_t points,

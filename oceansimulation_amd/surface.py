@@ -58,6 +58,34 @@ class SurfaceSampler:
         self.fft.synchronize()
         return out.to_host((pts, FLOATS_PER_VERTEX)) if pts else np.zeros((0, FLOATS_PER_VERTEX), np.float32)
 
+    # ---- footprint-aware sampling of the mip pyramids (Generator.build_mips first) ----
+    def sample_lod(self, xzf_ptr: int, points: int, out_ptr: int) -> None:
+        check(lib().ocean_surface_sample_lod(self._gens, self._cas, len(self.pairs), ctypes.c_void_p(xzf_ptr),
+                                             ctypes.c_int64(points), ctypes.c_void_p(out_ptr)),
+              "ocean_surface_sample_lod")
+
+    def sample_plane_lod(self, camera, res: int, out_ptr: int) -> None:
+        cam = (ctypes.c_float * 5)(*[float(v) for v in camera])
+        check(lib().ocean_surface_sample_plane_lod(self._gens, self._cas, len(self.pairs), cam, int(res),
+                                                   ctypes.c_void_p(out_ptr)), "ocean_surface_sample_plane_lod")
+
+    def sample_lod_host(self, xzf: np.ndarray) -> np.ndarray:
+        """Per (x, z, footprint in m): ocean_surface_sample's 8 floats, slot 7 = the footprint."""
+        xzf = np.ascontiguousarray(xzf, np.float32).reshape(-1, 3)
+        pts = xzf.shape[0]
+        src = DeviceBuffer.from_array(xzf) if pts else None
+        out = DeviceBuffer(pts * FLOATS_PER_VERTEX * 4) if pts else None
+        self.sample_lod(src.ptr if pts else 0, pts, out.ptr if pts else 0)
+        self.fft.synchronize()
+        return out.to_host((pts, FLOATS_PER_VERTEX)) if pts else np.zeros((0, FLOATS_PER_VERTEX), np.float32)
+
+    def plane_lod_host(self, camera, res: int) -> np.ndarray:
+        pts = (res + 1) * (res + 1)
+        out = DeviceBuffer(pts * FLOATS_PER_VERTEX * 4)
+        self.sample_plane_lod(camera, res, out.ptr)
+        self.fft.synchronize()
+        return out.to_host((pts, FLOATS_PER_VERTEX))
+
     def plane_host(self, camera, res: int) -> np.ndarray:
         pts = (res + 1) * (res + 1)
         out = DeviceBuffer(pts * FLOATS_PER_VERTEX * 4)

@@ -172,6 +172,31 @@ class Generator:
         blocked = hip.to_host(self.GetInitialSpectrum(cascade), (self.n // b, self.n, b, 4))
         return np.ascontiguousarray(blocked.transpose(1, 0, 2, 3).reshape(self.n, self.n, 4))
 
+    # ---- mip pyramid of the maps (ocean_generator_build_mips, include/oceanfft.h) ----
+    def build_mips(self) -> None:
+        """Enqueue the rebuild of levels >= 1 of every cascade's three maps from the current maps."""
+        check(lib().ocean_generator_build_mips(self._h), "ocean_generator_build_mips")
+
+    def mip_levels(self) -> int:
+        return int(lib().ocean_generator_mip_levels(self._h))
+
+    def _mip_host(self, getter: str, cascade: int, level: int, channels: int) -> np.ndarray:
+        ptr = getattr(lib(), getter)(self._h, int(cascade), int(level))
+        if not ptr:
+            raise capi.OceanError(capi.OCEAN_ERR_INVALID, getter)
+        self.fft.synchronize()
+        side = self.n >> level
+        return hip.to_host(int(ptr), (side, side, channels) if channels > 1 else (side, side))
+
+    def height_mip_host(self, cascade: int, level: int) -> np.ndarray:
+        return self._mip_host("ocean_generator_height_mip", cascade, level, 4)
+
+    def displacement_mip_host(self, cascade: int, level: int) -> np.ndarray:
+        return self._mip_host("ocean_generator_displacement_mip", cascade, level, 4)
+
+    def jacobian_mip_host(self, cascade: int, level: int) -> np.ndarray:
+        return self._mip_host("ocean_generator_jacobian_mip", cascade, level, 1)
+
     # ---- instrumentation ----
     def set_profiling(self, enable: bool) -> None:
         check(lib().ocean_generator_set_profiling(self._h, 1 if enable else 0), "ocean_generator_set_profiling")
