@@ -16,13 +16,17 @@
 //
 // Usage: waveapp_headless [--n 256] [--frames 600] [--dt 0.0166667] [--freeze A:B]...
 //                         [--edit F:G.field=value]... [--reseed reference|on-edit]
-//                         [--mesh RES (0 = no surface step)] [--probes K] [--mips] [--dump DIR]
+//                         [--mesh RES (0 = no surface step)] [--probes K] [--velocity] [--mips] [--dump DIR]
 // Prints one JSON line. --dump DIR writes height_G.npy, disp_G.npy, jac_G.npy (G = 0..2),
 // surface.npy ((RES+1)^2 x 8 floats) and scene.json for the last frame.
 // --probes K (default 0: nothing changes): after the last frame, the water surface above K points on a
 // 30 m circle around the camera (a ring of buoys; SurfaceSampler::Query, 8 iterations, tolerance 0).
 // The JSON line gains "probes" and "probe_max_residual"; --dump adds probes.npy (K x 8) and
 // probe_xz.npy (K x 2).
+// --velocity (default off: nothing changes; honoured with --probes K): after the query, every generator's
+// rate maps are calculated (Generator::CalculateRates) and SurfaceSampler::Velocity gives the velocity of the
+// water at the probes' base points (the query's base x, z). The JSON line gains "probe_max_speed" (m/s);
+// --dump adds probe_velocity.npy (K x 8) and height_rate_G.npy / disp_rate_G.npy.
 // --mips (default off: nothing changes): after the last frame, every generator's mip pyramid is built
 // (Generator::GenerateMips) and the mesh step runs once more through SurfaceSampler::SampleLod, which
 // samples each vertex at the level its spacing asks for. The JSON line gains "mips" (levels per map);
@@ -100,7 +104,7 @@ void usage()
 {
   std::fprintf(stderr, "usage: waveapp_headless [--n N] [--frames K] [--dt S] [--freeze A:B]... "
                        "[--edit F:G.field=value]... [--reseed reference|on-edit] [--mesh RES] [--probes K] "
-                       "[--mips] [--dump DIR]\n");
+                       "[--velocity] [--mips] [--dump DIR]\n");
 }
 
 }  // namespace
@@ -109,16 +113,16 @@ int main(int argc, char** argv)
 {
   int n = 256, frames = 600, mesh = 1024, probes = 0;
   float dt = 1.0f / 60.0f;
-  bool reseed_every_frame = true, mips = false;
+  bool reseed_every_frame = true, mips = false, velocity = false;
   std::string dump;
   std::vector<std::pair<int, int>> freezes;
   std::vector<Edit> edits;
   for (int i = 1; i < argc; i++)
   {
     const std::string a = argv[i];
-    if (a == "--mips")  // the one switch without a value
+    if (a == "--mips" || a == "--velocity")  // the switches without a value
     {
-      mips = true;
+      (a == "--mips" ? mips : velocity) = true;
       continue;
     }
     const char* v = i + 1 < argc ? argv[i + 1] : nullptr;
@@ -236,7 +240,9 @@ int main(int argc, char** argv)
 
     // the ring of buoys: which water is above each of them now (not part of the timed frames)
     std::vector<float> probeXZ, probeOut;
-    float probeMaxResidual = 0.0f;
+    std::vector<float> probeVelocity;
+    float probeMaxResidual = 0.0f, probeMaxSpeed = 0.0f;
+    velocity = velocity && probes > 0;
     if (probes > 0)
     {
       probeXZ.resize((size_t)probes * 2);
@@ -258,9 +264,36 @@ int main(int argc, char** argv)
       const Vision::ID q = sampler.Query(generators, xzDevice, probes, 8, 0.0f);
       device.SubmitCommandBuffer();
       device.GetTexture2DDataRaw(q, probeOut.data());
-      (void)hipFree(xzDevice);
       for (int k = 0; k < probes; k++)
         probeMaxResidual = std::max(probeMaxResidual, probeOut[8 * k + 7]);
+      if (velocity)
+      {
+        // how that water moves: the rates of the last frame, sampled at the base points the query found
+        std::vector<float> base((size_t)probes * 2);
+        for (int k = 0; k < probes; k++)
+        {
+          base[2 * k] = probeOut[8 * k];
+          base[2 * k + 1] = probeOut[8 * k + 2];
+        }
+        if (hipMemcpy(xzDevice, base.data(), base.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+        {
+          std::fprintf(stderr, "waveapp_headless: cannot upload the probes' base points\n");
+          return 1;
+        }
+        probeVelocity.resize((size_t)probes * 8);
+        device.BeginCommandBuffer();
+        for (auto* g : generators)
+          g->CalculateRates();
+        const Vision::ID v = sampler.Velocity(generators, xzDevice, probes);
+        device.SubmitCommandBuffer();
+        device.GetTexture2DDataRaw(v, probeVelocity.data());
+        for (int k = 0; k < probes; k++)
+        {
+          const float* u = &probeVelocity[8 * k + 4];
+          probeMaxSpeed = std::max(probeMaxSpeed, std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]));
+        }
+      }
+      (void)hipFree(xzDevice);
     }
 
     // the pyramids of the last frame's maps and the mesh sampled through them (not part of the timed frames)
@@ -328,6 +361,23 @@ int main(int argc, char** argv)
           return 1;
         }
       }
+      if (velocity)
+      {
+        bool ok = write_npy(dump + "/probe_velocity.npy", probeVelocity.data(), {(size_t)probes, 8});
+        for (int i = 0; i < 3; i++)
+        {
+          const std::string s = std::to_string(i);
+          device.GetTexture2DDataRaw(generators[i]->GetHeightRateMap(), buf.data());
+          ok = ok && write_npy(dump + "/height_rate_" + s + ".npy", buf.data(), {(size_t)n, (size_t)n, 4});
+          device.GetTexture2DDataRaw(generators[i]->GetDisplacementRateMap(), buf.data());
+          ok = ok && write_npy(dump + "/disp_rate_" + s + ".npy", buf.data(), {(size_t)n, (size_t)n, 4});
+        }
+        if (!ok)
+        {
+          std::fprintf(stderr, "cannot write %s\n", dump.c_str());
+          return 1;
+        }
+      }
       if (probes > 0 && !(write_npy(dump + "/probes.npy", probeOut.data(), {(size_t)probes, 8}) &&
                           write_npy(dump + "/probe_xz.npy", probeXZ.data(), {(size_t)probes, 2})))
       {
@@ -355,6 +405,12 @@ int main(int argc, char** argv)
       char b[96];
       std::snprintf(b, sizeof b, ", \"probes\": %d, \"probe_max_residual\": %.9g", probes, probeMaxResidual);
       probeJson = b;
+    }
+    if (velocity)
+    {
+      char b[64];
+      std::snprintf(b, sizeof b, ", \"probe_max_speed\": %.9g", probeMaxSpeed);
+      probeJson += b;
     }
     if (mips)
       probeJson += ", \"mips\": " + std::to_string(mipLevels);

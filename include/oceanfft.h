@@ -440,6 +440,56 @@ int ocean_surface_sample_lod(ocean_generator* const* gens, const int* cascades, 
 int ocean_surface_sample_plane_lod(ocean_generator* const* gens, const int* cascades, int count,
                                    const float camera[5], int res, float* out);
 
+/* ---- Time derivative of the maps and the velocity of water particles --------------------------
+ * The calls above say where the water is; these say how it moves (drag and added mass on a floating
+ * body's hull points, motion vectors, spray). Differencing two extra frames at t +- delta costs two
+ * frames and fails at large t, where the phase w * t is rounded to fp32 and the maps are not smooth in
+ * t. The derivative is analytic where the frame evolves the spectrum: with (a, b) the h0 texel,
+ *     H(k, t) = a e^{iwt} + b e^{-iwt},     dH/dt = i w (a e^{iwt} - b e^{-iwt}),
+ * and everything after H is linear and independent of t.
+ *
+ * Contract, per cascade and texel (x, y), in fp32: a = the h0 texel, k = |kvec(x, y)| + 1e-6,
+ * w = dispersion(k), (s, c) = sin / cos of w * time, with dk, time, g and h the values the last column
+ * pass used (so w and the phase have the frame's bits);
+ *     D  = a.xy * (c + i s) - a.zw * (c - i s),     Hd = i w D = (-w D.y, w D.x).
+ * The two images are prepareFFT's packing (spectrum.compute:236-237) with H replaced by Hd, each run
+ * through EncodeIFFT. Because the packing is the frame's own, Nyquist-row defect included, the result is
+ * the exact time derivative of all eight channels of the maps as the library shows them:
+ *     height-rate       = d/dt (h, dh/dx, dh/dz, Dx)
+ *     displacement-rate = d/dt (Dz, dDx/dx, dDz/dz, dDx/dz)
+ * Enqueued on the generator's stream: one packing kernel (16 B read, 32 B written per point) and one
+ * batched EncodeIFFT over the 2 * cascades images, about twice a frame's traffic. The storage
+ * (32 B per point and cascade) is allocated on the first call (OCEAN_ERR_OOM when that fails) and freed
+ * by ocean_generator_destroy. Whole-grid generators only, every N in 16 .. 16384: a slab generator gets
+ * OCEAN_ERR_INVALID before any device call, and so does a generator that has calculated no frame yet.
+ * The rates are fresh until the next frame call (its column pass moves the time); the library tracks
+ * that on the host. No reference counterpart. */
+int ocean_generator_calculate_rates(ocean_generator* gen);
+/* RGBA32F N*N, row-major, valid until the generator is destroyed and holding what the last
+ * ocean_generator_calculate_rates wrote. Null, with ocean_last_error set, for a null generator, a
+ * cascade out of range, or rates that were never calculated. */
+float* ocean_generator_height_rate_map(ocean_generator* gen, int cascade);
+float* ocean_generator_displacement_rate_map(ocean_generator* gen, int cascade);
+/* The velocity of the water particle whose rest position is p: d/dt of ocean_surface_sample's V(p),
+ * including the motion of the later cascades' sampling positions. xz holds points x 2 floats of base
+ * points in device memory (for water above a world position: slots 0 and 2 of ocean_surface_query's
+ * output). Per point, in unfused fp32, with GL_LINEAR + GL_REPEAT taps:
+ *     px, pz = p;  py = 0;  ux = uy = uz = 0
+ *     for c in cascades:           taps at (px / planeSize_c, pz / planeSize_c); s = displacement_c
+ *         H, Dm = heightMap, displacementMap sample;  RH, RD = the two rate maps' samples
+ *         vx = s * (RH.w + (Dm.y * ux + Dm.w * uz))       dDx/dt + grad Dx . u   (dDx/dz = Dm.w)
+ *         vy =      RH.x + (H.y  * ux + H.z  * uz)        dh/dt  + grad h  . u
+ *         vz = s * (RD.x + (Dm.w * ux + Dm.z * uz))       dDz/dt + grad Dz . u   (dDz/dx = dDx/dz)
+ *         px += s * H.w;  py += H.x;  pz += s * Dm.x      exactly the vertex stage
+ *         ux += vx;  uy += vy;  uz += vz
+ *     out = (px, py, pz, 0,  ux, uy, uz, 0)
+ * so slots 0-2 are ocean_surface_sample's bits; velocities in m/s. Argument rules, (generator,
+ * cascade) rules and stream as ocean_surface_sample; no atlas. Every generator's rates must be
+ * calculated and fresh: otherwise OCEAN_ERR_INVALID, naming the index of the generator in `gens`,
+ * before any device call. points == 0 launches nothing. No reference counterpart. */
+int ocean_surface_velocity(ocean_generator* const* gens, const int* cascades, int count, const float* xz,
+                           int64_t points, float* out);
+
 #ifdef __cplusplus
 }
 #endif

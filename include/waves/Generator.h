@@ -105,6 +105,15 @@ public:
   Vision::ID GetDisplacementMip(int level) const { return Mip(displacementMips, displacementMap, level); }
   Vision::ID GetJacobianMip(int level) const { return Mip(jacobianMips, jacobian, level); }
 
+  // Extension (no reference counterpart): the time derivative of heightMap and displacementMap at the
+  // time of the last CalculateOcean (ocean_generator_calculate_rates, oceanfft.h), channel for channel:
+  // d/dt (h, dh/dx, dh/dz, Dx) and d/dt (Dz, dDx/dx, dDz/dz, dDx/dz). CalculateRates enqueues it on the
+  // device's stream; call it after CalculateOcean and before SurfaceSampler::Velocity. The getters throw
+  // before the first CalculateRates.
+  void CalculateRates();
+  Vision::ID GetHeightRateMap() const { return Rate(heightRateMap); }
+  Vision::ID GetDisplacementRateMap() const { return Rate(displacementRateMap); }
+
 private:
   Vision::RenderDevice* renderDevice = nullptr;
   FFTCalculator* fftCalc = nullptr;
@@ -116,6 +125,9 @@ private:
   // levels >= 1 (index level - 1), registered by the first GenerateMips
   std::vector<Vision::ID> heightMips, displacementMips, jacobianMips;
   Vision::ID Mip(const std::vector<Vision::ID>& mips, Vision::ID map, int level) const;
+  // registered by the first CalculateRates
+  Vision::ID heightRateMap = 0, displacementRateMap = 0;
+  Vision::ID Rate(Vision::ID map) const;
 };
 
 }  // namespace Waves

@@ -48,6 +48,15 @@ public:
   // footprint in metres in the last float of each vertex; its own texture, reused at the same res.
   Vision::ID SampleLod(const std::vector<Generator*>& generators, const float camera[5], int res);
 
+  // How the water moves (ocean_surface_velocity, oceanfft.h): the velocity of the water particles whose
+  // rest positions are the `points` base points xzDevice (x, z pairs in device memory; for the water
+  // above a world position, the base x and z that Query returns), for drag on hull points, motion
+  // vectors and spray. Every generator needs Generator::CalculateRates() since its last CalculateOcean.
+  // Returns a buffer texture of 2*points x 1 RGBA32F texels: per point (displaced x, y, z, 0),
+  // (velocity x, y, z in m/s, 0). Enqueued on the device's stream; its own texture, reused while
+  // `points` stays the same.
+  Vision::ID Velocity(const std::vector<Generator*>& generators, const float* xzDevice, int64_t points);
+
 private:
   Vision::RenderDevice* renderDevice = nullptr;
   Vision::ID vertices = 0;
@@ -56,6 +65,8 @@ private:
   int64_t queriedPoints = 0;
   Vision::ID verticesLod = 0;
   int verticesLodRes = 0;
+  Vision::ID velocities = 0;
+  int64_t velocityPoints = 0;
 };
 
 }  // namespace Waves

@@ -97,6 +97,10 @@ SIGNATURES = {
     "ocean_generator_jacobian_mip": (_vp, [_vp, _i, _i]),
     "ocean_surface_sample_lod": (_i, [_vp, _vp, _i, _vp, ctypes.c_int64, _vp]),
     "ocean_surface_sample_plane_lod": (_i, [_vp, _vp, _i, _vp, _i, _vp]),
+    "ocean_generator_calculate_rates": (_i, [_vp]),
+    "ocean_generator_height_rate_map": (_vp, [_vp, _i]),
+    "ocean_generator_displacement_rate_map": (_vp, [_vp, _i]),
+    "ocean_surface_velocity": (_i, [_vp, _vp, _i, _vp, ctypes.c_int64, _vp]),
     "ocean_generator_set_half_spectrum": (_i, [_vp, _i]),
     "ocean_generator_set_four_step": (_i, [_vp, _i]),
     "ocean_generator_set_h0_memo": (_i, [_vp, _i]),

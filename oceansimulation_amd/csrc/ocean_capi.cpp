@@ -169,6 +169,10 @@ struct ocean_generator
   // jacobian chains], allocated on first use; fresh until the next call that rewrites the maps
   float* mips = nullptr;
   bool mips_fresh = false;
+  // the time derivative of the maps (ocean_generator_calculate_rates): [cascade][height-rate |
+  // displacement-rate][N * N], allocated on first use; fresh until the next column pass
+  float4* rates = nullptr;
+  bool rates_fresh = false;
   bool profiling = false;
   std::vector<EventPair> pending;
   std::vector<hipEvent_t> pool;
@@ -701,7 +705,8 @@ int ocean_generator_destroy(ocean_generator* g)
     if (p)
       (void)hipFree(p);
   for (void* p : {(void*)g->gab, (void*)g->gcd, (void*)g->ge, (void*)g->spec, (void*)g->hs, (void*)g->h0row, g->seedc,
-                  (void*)g->rm_ab, (void*)g->rm_de, (void*)g->rm_c, (void*)g->parts, (void*)g->xbuf, (void*)g->mips})
+                  (void*)g->rm_ab, (void*)g->rm_de, (void*)g->rm_c, (void*)g->parts, (void*)g->xbuf, (void*)g->mips,
+                  (void*)g->rates})
     if (p)
       (void)hipFree(p);
   delete g;
@@ -837,6 +842,7 @@ static int generator_columns(ocean_generator* g, float timestep, int update_spec
                              const Gen4Put* put = nullptr, hipStream_t col_stream = nullptr)
 {
   ocean_fft* f = g->fft;
+  g->rates_fresh = false;  // the rates belong to the time and h0 of the column pass before this one
   for (auto& s : g->settings)
     s.time += timestep;
   const void* seed = nullptr;
@@ -2435,6 +2441,97 @@ int ocean_surface_sample_plane_lod(ocean_generator* const* gens, const int* casc
   const int64_t pts = (int64_t)(res + 1) * (res + 1);
   HIP_TRY(launch_surface_lod(p, plane, nullptr, pts, reinterpret_cast<float4*>(out), fft->stream, fft->cus),
           "ocean_surface_sample_plane_lod");
+  return OCEAN_OK;
+}
+
+// ---- time derivative of the maps and the velocity of water particles ----
+int ocean_generator_calculate_rates(ocean_generator* g)
+{
+  if (!g)
+    return fail(OCEAN_ERR_INVALID, "ocean_generator_calculate_rates: null generator");
+  if (g->slab || g->ranks != 1)
+    return fail(OCEAN_ERR_INVALID, "ocean_generator_calculate_rates: slab generators hold row slabs, not whole maps");
+  if (g->frame.cascades != g->cascades)
+    return fail(OCEAN_ERR_INVALID, "ocean_generator_calculate_rates: no frame calculated yet (ocean_generator_calculate)");
+  ocean_fft* f = g->fft;
+  const size_t nn = (size_t)f->n * f->n;
+  if (!g->rates)
+  {
+    const hipError_t e = hipMalloc(&g->rates, (size_t)g->cascades * 2 * nn * sizeof(float4));
+    if (e != hipSuccess)
+    {
+      g->rates = nullptr;
+      return fail(e == hipErrorOutOfMemory ? OCEAN_ERR_OOM : OCEAN_ERR_HIP,
+                  std::string("ocean_generator_calculate_rates: ") + hipGetErrorString(e));
+    }
+  }
+  g->rates_fresh = false;
+  // after fused re-seed frames the h0 image is still to be written: on the generator's stream, so with
+  // frame overlap the next column pass waits for it (h0_dirty, set by the write); the memo keeps its inputs
+  int rc = materialise_h0(g);
+  if (rc != OCEAN_OK)
+    return rc;
+  HIP_TRY(launch_rates_pack(f->logn, g->frame, g->h0_block, g->h0, g->rates, f->stream, f->cus),
+          "ocean_generator_calculate_rates");
+  rc = ocean_fft_encode_ifft_batch(f, reinterpret_cast<float*>(g->rates), 2 * g->cascades);
+  if (rc != OCEAN_OK)
+    return rc;
+  g->rates_fresh = true;
+  return OCEAN_OK;
+}
+
+// Image `image` (0 height-rate, 1 displacement-rate) of cascade c
+static float* generator_rate_map(ocean_generator* g, int c, int image, const char* who)
+{
+  if (!g || c < 0 || c >= g->cascades)
+  {
+    fail(OCEAN_ERR_INVALID, std::string(who) + ": null generator or cascade out of range");
+    return nullptr;
+  }
+  if (!g->rates)
+  {
+    fail(OCEAN_ERR_INVALID, std::string(who) + ": the rates were never calculated (ocean_generator_calculate_rates)");
+    return nullptr;
+  }
+  return reinterpret_cast<float*>(g->rates + (size_t)g->fft->n * g->fft->n * (2 * c + image));
+}
+
+float* ocean_generator_height_rate_map(ocean_generator* g, int c)
+{
+  return generator_rate_map(g, c, 0, "ocean_generator_height_rate_map");
+}
+
+float* ocean_generator_displacement_rate_map(ocean_generator* g, int c)
+{
+  return generator_rate_map(g, c, 1, "ocean_generator_displacement_rate_map");
+}
+
+int ocean_surface_velocity(ocean_generator* const* gens, const int* cascades, int count, const float* xz,
+                           int64_t points, float* out)
+{
+  SurfaceParams p;
+  ocean_fft* fft;
+  const int rc = surface_params(gens, cascades, count, p, fft, "ocean_surface_velocity");
+  if (rc != OCEAN_OK)
+    return rc;
+  SurfaceRates r{};
+  for (int i = 0; i < count; i++)
+  {
+    ocean_generator* g = gens[i];
+    if (!g->rates || !g->rates_fresh)
+      return fail(OCEAN_ERR_INVALID, std::string("ocean_surface_velocity: generator ") + std::to_string(i) +
+                                         (g->rates ? " has stale rates (a frame was calculated since"
+                                                   : " has no rates (call") +
+                                         " ocean_generator_calculate_rates)");
+    const size_t nn = (size_t)fft->n * fft->n;
+    r.height[i] = g->rates + nn * (2 * cascades[i]);
+    r.disp[i] = g->rates + nn * (2 * cascades[i] + 1);
+  }
+  if (points < 0 || (points > 0 && (!xz || !out)))
+    return fail(OCEAN_ERR_INVALID, "ocean_surface_velocity: null positions/output or negative count");
+  HIP_TRY(launch_surface_velocity(p, r, reinterpret_cast<const float2*>(xz), points, reinterpret_cast<float4*>(out),
+                                  fft->stream, fft->cus),
+          "ocean_surface_velocity");
   return OCEAN_OK;
 }
 

@@ -282,6 +282,21 @@ hipError_t launch_surface_lod(const SurfaceParams& p, const SurfacePlane& plane,
 size_t mip_cascade_floats(int n);
 hipError_t launch_build_mips(int n, int cascades, const float4* maps, const float* jac, float* mips,
                              hipStream_t stream);
+// The packed time-derivative images of a whole-grid generator (device/k_rates.h): per cascade of fp the
+// height-rate and the displacement-rate image, row-major and still in k space, into rates
+// [cascade][2][N * N]; h0 is every cascade's N * N image blocked h0_blk columns wide (any power of two
+// up to N). The batched EncodeIFFT over the 2 * cascades images follows (the caller's).
+hipError_t launch_rates_pack(int logn, const FrameParams& fp, int h0_blk, const float4* h0, float4* rates,
+                             hipStream_t stream, int cus);
+// ocean_surface_velocity: the cascades' rate maps beside SurfaceParams' maps (same order), and the
+// sampler: per base point the displaced position and the velocity of its water particle.
+struct SurfaceRates
+{
+  const float4* height[kMaxSurfaceCascades];
+  const float4* disp[kMaxSurfaceCascades];
+};
+hipError_t launch_surface_velocity(const SurfaceParams& p, const SurfaceRates& r, const float2* xz, int64_t count,
+                                   float4* out, hipStream_t stream, int cus);
 size_t surface_atlas_texels(const SurfaceParams& p);
 bool surface_use_atlas(const SurfaceParams& p, int64_t points);
 bool surface_query_use_atlas(const SurfaceParams& p, int64_t points, int iterations);

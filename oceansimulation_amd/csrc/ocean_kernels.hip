@@ -464,6 +464,47 @@ __global__ __launch_bounds__(256) void k_surface_query(SurfaceParams p, const fl
   }
 }
 
+// The velocity of the water particle whose rest position is the base point (ocean_surface_velocity,
+// include/oceanfft.h): d/dt of the vertex stage V(p). Cascade c samples at the position the earlier
+// cascades displaced, which itself moves with the velocity u accumulated so far, so its share is the
+// rate maps' sample plus grad(field) . u, the gradients being map channels (dDx/dz = dDz/dx). The
+// position advances exactly as in surface_vertex_stage (same taps, weights and sums), so slots 0-2 are
+// ocean_surface_sample's bits. Per cascade and tap two 16-B loads (the maps) and three dwords (the rates).
+__global__ __launch_bounds__(256) void k_surface_velocity(SurfaceParams p, SurfaceRates r, const float2* __restrict__ xz,
+                                                          int64_t count, float4* __restrict__ out)
+{
+#pragma clang fp contract(off)
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < count;
+       idx += (int64_t)gridDim.x * blockDim.x)
+  {
+    const float2 q = xz[idx];
+    float px = q.x, py = 0.0f, pz = q.y;
+    float ux = 0.0f, uy = 0.0f, uz = 0.0f;
+    for (int c = 0; c < p.count; c++)
+    {
+      const float u = px / p.c[c].plane, v = pz / p.c[c].plane;
+      const LinearTaps k = linear_repeat_taps(p.n, u, v);
+      const float4 h = linear_texel(p.c[c].height, k), d = linear_texel(p.c[c].disp, k);
+      const float* rh = reinterpret_cast<const float*>(r.height[c]);
+      const float* rd = reinterpret_cast<const float*>(r.disp[c]);
+      const float rh_h = linear_channel<4>(rh, k, 0), rh_dx = linear_channel<4>(rh, k, 3);
+      const float rd_dz = linear_channel<4>(rd, k, 0);
+      const float s = p.c[c].scale;
+      const float vx = s * (rh_dx + (d.y * ux + d.w * uz));  // dDx/dt + grad Dx . u
+      const float vy = rh_h + (h.y * ux + h.z * uz);         // dh/dt + grad h . u
+      const float vz = s * (rd_dz + (d.w * ux + d.z * uz));  // dDz/dt + grad Dz . u
+      px += s * h.w;
+      py += h.x;
+      pz += s * d.x;
+      ux += vx;
+      uy += vy;
+      uz += vz;
+    }
+    out[2 * idx] = make_float4(px, py, pz, 0.0f);
+    out[2 * idx + 1] = make_float4(ux, uy, uz, 0.0f);
+  }
+}
+
 // Footprint-aware sampling (ocean_surface_sample_lod, include/oceanfft.h): a sample whose neighbours sit
 // `footprint` metres away covers r = footprint * N / planeSize texels of cascade c's level 0, so it reads
 // level l = floor(log2 r) and level l + 1 of the mip pyramid (device/k_mips.h) and blends them by
@@ -706,6 +747,19 @@ hipError_t launch_surface_query(const SurfaceParams& p, const float2* xz, int64_
   else
     hipLaunchKernelGGL(k_surface_query<false>, dim3((unsigned)blocks), dim3(256), 0, stream, p, xz, count, iterations,
                        tolerance, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_surface_velocity(const SurfaceParams& p, const SurfaceRates& r, const float2* xz, int64_t count,
+                                   float4* out, hipStream_t stream, int cus)
+{
+  if (count <= 0)
+    return hipSuccess;
+  long blocks = (long)((count + 255) / 256);
+  const long cap = (long)cus * 8;
+  if (blocks > cap)
+    blocks = cap;
+  hipLaunchKernelGGL(k_surface_velocity, dim3((unsigned)blocks), dim3(256), 0, stream, p, r, xz, count, out);
   return hipGetLastError();
 }
 

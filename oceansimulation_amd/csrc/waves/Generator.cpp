@@ -34,6 +34,9 @@ Generator::~Generator()
   for (const auto* mips : {&heightMips, &displacementMips, &jacobianMips})
     for (Vision::ID id : *mips)
       renderDevice->DestroyTexture2D(id);
+  for (Vision::ID id : {heightRateMap, displacementRateMap})
+    if (id)
+      renderDevice->DestroyTexture2D(id);
   ocean_generator_destroy(gen);
 }
 
@@ -75,6 +78,26 @@ Vision::ID Generator::Mip(const std::vector<Vision::ID>& mips, Vision::ID map, i
   if (mips.empty())
     throw std::runtime_error("Waves::Generator: the mip pyramid was never built (GenerateMips)");
   return mips[(std::size_t)level - 1];
+}
+
+void Generator::CalculateRates()
+{
+  if (ocean_generator_calculate_rates(gen) != OCEAN_OK)
+    throw std::runtime_error(std::string("Waves::Generator::CalculateRates: ") + ocean_last_error());
+  if (heightRateMap)
+    return;
+  const std::size_t n = textureSize;
+  heightRateMap = renderDevice->RegisterTexture2D(ocean_generator_height_rate_map(gen, 0), n, n,
+                                                  Vision::PixelType::RGBA32Float);
+  displacementRateMap = renderDevice->RegisterTexture2D(ocean_generator_displacement_rate_map(gen, 0), n, n,
+                                                        Vision::PixelType::RGBA32Float);
+}
+
+Vision::ID Generator::Rate(Vision::ID map) const
+{
+  if (!map)
+    throw std::runtime_error("Waves::Generator: the rates were never calculated (CalculateRates)");
+  return map;
 }
 
 void Generator::LoadShaders(bool) {}

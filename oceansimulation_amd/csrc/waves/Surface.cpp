@@ -1,5 +1,5 @@
 // Waves::SurfaceSampler over ocean_surface_sample_plane / ocean_surface_query /
-// ocean_surface_sample_plane_lod (include/oceanfft.h).
+// ocean_surface_sample_plane_lod / ocean_surface_velocity (include/oceanfft.h).
 #include "waves/Surface.h"
 
 #include <stdexcept>
@@ -16,6 +16,8 @@ SurfaceSampler::~SurfaceSampler()
     renderDevice->DestroyTexture2D(queried);
   if (verticesLod)
     renderDevice->DestroyTexture2D(verticesLod);
+  if (velocities)
+    renderDevice->DestroyTexture2D(velocities);
 }
 
 Vision::ID SurfaceSampler::Sample(const std::vector<Generator*>& generators, const float camera[5], int res)
@@ -102,6 +104,36 @@ Vision::ID SurfaceSampler::Query(const std::vector<Generator*>& generators, cons
   if (rc != OCEAN_OK)
     throw std::runtime_error(std::string("SurfaceSampler::Query: ") + ocean_last_error());
   return queried;
+}
+
+Vision::ID SurfaceSampler::Velocity(const std::vector<Generator*>& generators, const float* xzDevice, int64_t points)
+{
+  if (points < 1)
+    throw std::runtime_error("SurfaceSampler::Velocity: need at least one point");
+  if (!velocities || velocityPoints != points)
+  {
+    if (velocities)
+      renderDevice->DestroyTexture2D(velocities);
+    velocities = 0;
+    Vision::Texture2DDesc desc;
+    desc.Width = 2 * (std::size_t)points;
+    desc.Height = 1;
+    desc.PixelType = Vision::PixelType::RGBA32Float;
+    velocities = renderDevice->CreateTexture2D(desc);
+    velocityPoints = points;
+  }
+  std::vector<ocean_generator*> gens;
+  std::vector<int> cascades;
+  for (auto* g : generators)
+  {
+    gens.push_back(g->GetHandle());
+    cascades.push_back(0);
+  }
+  const int rc = ocean_surface_velocity(gens.data(), cascades.data(), (int)gens.size(), xzDevice, points,
+                                        static_cast<float*>(renderDevice->GetTexturePointer(velocities)));
+  if (rc != OCEAN_OK)
+    throw std::runtime_error(std::string("SurfaceSampler::Velocity: ") + ocean_last_error());
+  return velocities;
 }
 
 }  // namespace Waves

@@ -86,6 +86,21 @@ class SurfaceSampler:
         self.fft.synchronize()
         return out.to_host((pts, FLOATS_PER_VERTEX))
 
+    # ---- velocity of water particles (Generator.calculate_rates first) ----
+    def velocity(self, xz_ptr: int, points: int, out_ptr: int) -> None:
+        check(lib().ocean_surface_velocity(self._gens, self._cas, len(self.pairs), ctypes.c_void_p(xz_ptr),
+                                           ctypes.c_int64(points), ctypes.c_void_p(out_ptr)), "ocean_surface_velocity")
+
+    def velocity_host(self, xz: np.ndarray) -> np.ndarray:
+        """Per base point (x, z): (displaced x, y, z, 0, velocity x, y, z in m/s, 0)."""
+        xz = np.ascontiguousarray(xz, np.float32).reshape(-1, 2)
+        pts = xz.shape[0]
+        src = DeviceBuffer.from_array(xz) if pts else None
+        out = DeviceBuffer(pts * FLOATS_PER_VERTEX * 4) if pts else None
+        self.velocity(src.ptr if pts else 0, pts, out.ptr if pts else 0)
+        self.fft.synchronize()
+        return out.to_host((pts, FLOATS_PER_VERTEX)) if pts else np.zeros((0, FLOATS_PER_VERTEX), np.float32)
+
     def plane_host(self, camera, res: int) -> np.ndarray:
         pts = (res + 1) * (res + 1)
         out = DeviceBuffer(pts * FLOATS_PER_VERTEX * 4)

@@ -197,6 +197,26 @@ class Generator:
     def jacobian_mip_host(self, cascade: int, level: int) -> np.ndarray:
         return self._mip_host("ocean_generator_jacobian_mip", cascade, level, 1)
 
+    # ---- time derivative of the maps (ocean_generator_calculate_rates, include/oceanfft.h) ----
+    def calculate_rates(self) -> None:
+        """Enqueue d/dt of every cascade's heightMap and displacementMap at the time of the last frame."""
+        check(lib().ocean_generator_calculate_rates(self._h), "ocean_generator_calculate_rates")
+
+    def _rate_host(self, getter: str, cascade: int) -> np.ndarray:
+        ptr = getattr(lib(), getter)(self._h, int(cascade))
+        if not ptr:
+            raise capi.OceanError(capi.OCEAN_ERR_INVALID, getter)
+        self.fft.synchronize()
+        return hip.to_host(int(ptr), (self.n, self.n, 4))
+
+    def height_rate_map_host(self, cascade: int = 0) -> np.ndarray:
+        """d/dt (h, dh/dx, dh/dz, Dx)"""
+        return self._rate_host("ocean_generator_height_rate_map", cascade)
+
+    def displacement_rate_map_host(self, cascade: int = 0) -> np.ndarray:
+        """d/dt (Dz, dDx/dx, dDz/dz, dDx/dz)"""
+        return self._rate_host("ocean_generator_displacement_rate_map", cascade)
+
     # ---- instrumentation ----
     def set_profiling(self, enable: bool) -> None:
         check(lib().ocean_generator_set_profiling(self._h, 1 if enable else 0), "ocean_generator_set_profiling")
