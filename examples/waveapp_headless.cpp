@@ -16,7 +16,8 @@
 //
 // Usage: waveapp_headless [--n 256] [--frames 600] [--dt 0.0166667] [--freeze A:B]...
 //                         [--edit F:G.field=value]... [--reseed reference|on-edit]
-//                         [--mesh RES (0 = no surface step)] [--probes K] [--velocity] [--mips] [--dump DIR]
+//                         [--mesh RES (0 = no surface step)] [--probes K] [--velocity] [--mips] [--bodies K]
+//                         [--dump DIR]
 // Prints one JSON line. --dump DIR writes height_G.npy, disp_G.npy, jac_G.npy (G = 0..2),
 // surface.npy ((RES+1)^2 x 8 floats) and scene.json for the last frame.
 // --probes K (default 0: nothing changes): after the last frame, the water surface above K points on a
@@ -31,6 +32,12 @@
 // (Generator::GenerateMips) and the mesh step runs once more through SurfaceSampler::SampleLod, which
 // samples each vertex at the level its spacing asks for. The JSON line gains "mips" (levels per map);
 // --dump adds height_G_mipL.npy for L = 1 and the top level, and mesh_lod.npy ((RES+1)^2 x 8).
+// --bodies K (default 0: nothing changes): K floating bodies, instances of one 4 x 4 x 4-point box hull
+// (2 m x 1 m x 4 m), on a 30 m circle around the camera in fixed tilted poses, moving along the circle at
+// 1 m/s. Every frame calculates the generators' rate maps and the loads on all bodies (Waves::HullSet::Loads:
+// 8 iterations, tolerance 0, water velocity on). The JSON line gains "bodies" and "body_max_residual"; --dump
+// adds hull_points.npy (64 x 8), hull_ranges.npy (K x 2, int32), body_poses.npy (K x 20), body_loads.npy
+// (K x 8), body_points.npy (64 K x 8) and height_rate_G.npy / disp_rate_G.npy of the last frame.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -73,8 +80,8 @@ bool set_field(Waves::GeneratorSettings& s, const std::string& f, float v)
   return true;
 }
 
-// numpy .npy v1.0, little-endian float32, C order
-bool write_npy(const std::string& path, const float* data, const std::vector<size_t>& shape)
+// numpy .npy v1.0, little-endian float32 (or another 4-byte type: descr), C order
+bool write_npy(const std::string& path, const void* data, const std::vector<size_t>& shape, const char* descr = "<f4")
 {
   std::string dims;
   size_t count = 1;
@@ -85,7 +92,7 @@ bool write_npy(const std::string& path, const float* data, const std::vector<siz
   }
   if (shape.size() > 1)
     dims.pop_back();
-  std::string header = "{'descr': '<f4', 'fortran_order': False, 'shape': (" + dims + "), }";
+  std::string header = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': (" + dims + "), }";
   const size_t total = 10 + header.size() + 1;
   header.append((64 - total % 64) % 64, ' ');
   header += '\n';
@@ -104,14 +111,14 @@ void usage()
 {
   std::fprintf(stderr, "usage: waveapp_headless [--n N] [--frames K] [--dt S] [--freeze A:B]... "
                        "[--edit F:G.field=value]... [--reseed reference|on-edit] [--mesh RES] [--probes K] "
-                       "[--velocity] [--mips] [--dump DIR]\n");
+                       "[--velocity] [--mips] [--bodies K] [--dump DIR]\n");
 }
 
 }  // namespace
 
 int main(int argc, char** argv)
 {
-  int n = 256, frames = 600, mesh = 1024, probes = 0;
+  int n = 256, frames = 600, mesh = 1024, probes = 0, bodies = 0;
   float dt = 1.0f / 60.0f;
   bool reseed_every_frame = true, mips = false, velocity = false;
   std::string dump;
@@ -136,6 +143,7 @@ int main(int argc, char** argv)
     else if (a == "--dt") dt = std::strtof(v, nullptr);
     else if (a == "--mesh") mesh = std::atoi(v);
     else if (a == "--probes") probes = std::atoi(v);
+    else if (a == "--bodies") bodies = std::atoi(v);
     else if (a == "--dump") dump = v;
     else if (a == "--reseed") reseed_every_frame = std::string(v) != "on-edit";
     else if (a == "--freeze")
@@ -167,7 +175,7 @@ int main(int argc, char** argv)
     }
     i++;
   }
-  if (probes < 0)
+  if (probes < 0 || bodies < 0)
   {
     usage();
     return 2;
@@ -193,6 +201,46 @@ int main(int argc, char** argv)
     const float camera[5] = {0.0f, 5.0f, 0.0f, -0.70711f, 0.70711f};  // src/Renderer.cpp:15-16
     bool updateSpectrum = true;  // src/Waves.h:31
     Vision::ID surface = 0;
+
+    // the floating bodies: one box hull, `bodies` poses on the ring
+    const float rhoG = 9810.0f;
+    std::vector<float> hullPoints, bodyPoses;
+    std::vector<int32_t> hullRanges;
+    Waves::HullSet* hulls = nullptr;
+    float* posesDevice = nullptr;
+    Vision::ID bodyLoads = 0;
+    if (bodies > 0)
+    {
+      for (int k = 0; k < 4; k++)      // z
+        for (int j = 0; j < 4; j++)    // y
+          for (int i = 0; i < 4; i++)  // x fastest
+            for (float f : {(i + 0.5f) * 0.5f - 1.0f, (j + 0.5f) * 0.25f - 0.5f, (k + 0.5f) * 1.0f - 2.0f,
+                            0.5f * 0.25f * 1.0f, 0.125f, 40.0f, 15.0f, 0.0f})
+              hullPoints.push_back(f);
+      for (int b = 0; b < bodies; b++)
+      {
+        const double a = 2.0 * 3.14159265358979323846 * b / bodies;
+        const double roll = 0.2 * std::cos(2.0 * a), pitch = 0.15 * std::sin(3.0 * a);  // about z, then about x
+        const double cr = std::cos(roll), sr = std::sin(roll), cp = std::cos(pitch), sp = std::sin(pitch);
+        // Rx(pitch) * Rz(roll), row-major
+        const double R[9] = {cr, -sr, 0.0, cp * sr, cp * cr, -sp, sp * sr, sp * cr, cp};
+        for (double r : R)
+          bodyPoses.push_back((float)r);
+        for (double c : {camera[0] + 30.0 * std::cos(a), 0.1 * std::cos(5.0 * a) - 0.1, camera[2] + 30.0 * std::sin(a),
+                         -std::sin(a), 0.0, std::cos(a),  // 1 m/s along the ring
+                         0.0, 0.2, 0.0, 0.0, 0.0})        // yawing at 0.2 rad/s
+          bodyPoses.push_back((float)c);
+        hullRanges.push_back(0);
+        hullRanges.push_back(64);
+      }
+      hulls = new Waves::HullSet(&device, &fft, hullPoints.data(), 64, hullRanges.data(), bodies);
+      if (hipMalloc(reinterpret_cast<void**>(&posesDevice), bodyPoses.size() * sizeof(float)) != hipSuccess ||
+          hipMemcpy(posesDevice, bodyPoses.data(), bodyPoses.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+      {
+        std::fprintf(stderr, "waveapp_headless: cannot upload the body poses\n");
+        return 1;
+      }
+    }
 
     device.BeginCommandBuffer();
     device.SubmitCommandBuffer();
@@ -234,9 +282,27 @@ int main(int argc, char** argv)
         updateSpectrum = false;
       if (mesh > 0)
         surface = sampler.Sample(generators, camera, mesh);
+      if (bodies > 0)
+      {
+        for (auto* g : generators)
+          g->CalculateRates();
+        bodyLoads = hulls->Loads(generators, posesDevice, rhoG, 8, 0.0f, true, true);
+      }
       device.SubmitCommandBuffer();
     }
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+
+    std::vector<float> bodyLoadsHost, bodyPointsHost;
+    float bodyMaxResidual = 0.0f;
+    if (bodies > 0 && frames > 0)
+    {
+      bodyLoadsHost.resize((size_t)bodies * 8);
+      bodyPointsHost.resize((size_t)bodies * 64 * 8);
+      device.GetTexture2DDataRaw(bodyLoads, bodyLoadsHost.data());
+      device.GetTexture2DDataRaw(hulls->GetPointOutput(), bodyPointsHost.data());
+      for (size_t k = 0; k < (size_t)bodies * 64; k++)
+        bodyMaxResidual = std::max(bodyMaxResidual, bodyPointsHost[8 * k + 3]);
+    }
 
     // the ring of buoys: which water is above each of them now (not part of the timed frames)
     std::vector<float> probeXZ, probeOut;
@@ -361,9 +427,9 @@ int main(int argc, char** argv)
           return 1;
         }
       }
-      if (velocity)
+      if (velocity || !bodyLoadsHost.empty())
       {
-        bool ok = write_npy(dump + "/probe_velocity.npy", probeVelocity.data(), {(size_t)probes, 8});
+        bool ok = !velocity || write_npy(dump + "/probe_velocity.npy", probeVelocity.data(), {(size_t)probes, 8});
         for (int i = 0; i < 3; i++)
         {
           const std::string s = std::to_string(i);
@@ -377,6 +443,16 @@ int main(int argc, char** argv)
           std::fprintf(stderr, "cannot write %s\n", dump.c_str());
           return 1;
         }
+      }
+      if (!bodyLoadsHost.empty() &&
+          !(write_npy(dump + "/hull_points.npy", hullPoints.data(), {64, 8}) &&
+            write_npy(dump + "/hull_ranges.npy", hullRanges.data(), {(size_t)bodies, 2}, "<i4") &&
+            write_npy(dump + "/body_poses.npy", bodyPoses.data(), {(size_t)bodies, 20}) &&
+            write_npy(dump + "/body_loads.npy", bodyLoadsHost.data(), {(size_t)bodies, 8}) &&
+            write_npy(dump + "/body_points.npy", bodyPointsHost.data(), {(size_t)bodies * 64, 8})))
+      {
+        std::fprintf(stderr, "cannot write %s\n", dump.c_str());
+        return 1;
       }
       if (probes > 0 && !(write_npy(dump + "/probes.npy", probeOut.data(), {(size_t)probes, 8}) &&
                           write_npy(dump + "/probe_xz.npy", probeXZ.data(), {(size_t)probes, 2})))
@@ -395,7 +471,11 @@ int main(int argc, char** argv)
           std::fprintf(js, "%s{\"planeSize\": %.9g, \"time\": %.9g, \"U_10\": %.9g, \"displacement\": %.9g}",
                        i ? ", " : "", s.planeSize, s.time, s.U_10, s.displacement);
         }
-        std::fprintf(js, "]}\n");
+        std::fprintf(js, "]");
+        if (bodies > 0)
+          std::fprintf(js, ", \"bodies\": {\"count\": %d, \"rho_g\": %.9g, \"iterations\": 8, \"tolerance\": 0}", bodies,
+                       rhoG);
+        std::fprintf(js, "}\n");
         std::fclose(js);
       }
     }
@@ -414,6 +494,12 @@ int main(int argc, char** argv)
     }
     if (mips)
       probeJson += ", \"mips\": " + std::to_string(mipLevels);
+    if (!bodyLoadsHost.empty())
+    {
+      char b[96];
+      std::snprintf(b, sizeof b, ", \"bodies\": %d, \"body_max_residual\": %.9g", bodies, bodyMaxResidual);
+      probeJson += b;
+    }
     std::printf("{\"app\": \"waveapp_headless\", \"n\": %d, \"cascades\": 3, \"frames\": %d, \"frozen_frames\": %d, "
                 "\"reseeded_frames\": %d, \"reseed\": \"%s\", \"mesh_vertices\": %lld, \"seconds\": %.6f, "
                 "\"ms_per_frame\": %.6f, \"frames_per_s\": %.3f, \"height_field_points_per_s\": %.6e, "
@@ -422,6 +508,9 @@ int main(int argc, char** argv)
                 mesh > 0 ? (long long)(mesh + 1) * (mesh + 1) : 0LL, secs, 1e3 * secs / frames, frames / secs,
                 3.0 * n * n * frames / secs, generators[0]->GetOceanSettings().time,
                 generators[1]->GetOceanSettings().time, generators[2]->GetOceanSettings().time, probeJson.c_str());
+    delete hulls;
+    if (posesDevice)
+      (void)hipFree(posesDevice);
     for (auto* g : generators)
       delete g;
   }

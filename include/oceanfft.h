@@ -490,6 +490,76 @@ float* ocean_generator_displacement_rate_map(ocean_generator* gen, int cascade);
 int ocean_surface_velocity(ocean_generator* const* gens, const int* cascades, int count, const float* xz,
                            int64_t points, float* out);
 
+/* ---- Hull sets: net wave force and torque on batches of floating bodies -------------------------
+ * The consumer of the three sections above: a floating body is a set of hull points, each carrying a
+ * displaced volume and drag coefficients; per step the caller hands in the bodies' poses and gets one
+ * wrench (force and torque about the body's centre) per body back. One fused pass: pose -> world point ->
+ * ocean_surface_query -> ocean_surface_velocity -> load -> sum per body, with no intermediate in device
+ * memory, and a summation order that is part of the contract, so a step is replayable bit for bit.
+ *
+ * ocean_hulls_create. points: host, n_points x 8 floats (lx, ly, lz, volume, half_height, drag_lin,
+ * drag_quad, 0) in the body frame. ranges: host, bodies x 2 int32 (first, count) into points; bodies may
+ * share or overlap ranges (instances of one hull). Both are copied to the device of `fft` (the current
+ * device); later calls run on its stream. Also built here: the table of work items (64-point tiles of one
+ * body) and the scratch for the partial sums of bodies of more than 64 points.
+ * OCEAN_ERR_INVALID, before any device call: null out / fft / points / ranges; bodies outside
+ * 1 .. 1048576; a count outside 1 .. 262144 or a range that leaves points; a non-finite point field;
+ * volume < 0, half_height <= 0 or a negative drag coefficient. */
+typedef struct ocean_hulls ocean_hulls;
+int ocean_hulls_create(ocean_hulls** out, ocean_fft* fft, const float* points, int64_t n_points,
+                       const int32_t* ranges, int bodies);
+/* Waits for the plan's stream, then frees the set. */
+int ocean_hulls_destroy(ocean_hulls* hulls);
+int ocean_hulls_bodies(const ocean_hulls* hulls);
+int64_t ocean_hulls_instance_points(const ocean_hulls* hulls);   /* sum of the counts */
+/* poses: device, bodies x 20 floats (R[9] row-major body->world, c[3], v[3], w[3], 0, 0): rotation,
+ * centre, linear and angular velocity in the world frame. loads: device, bodies x 8 floats.
+ * point_out: device, instance_points x 8 floats, or null.
+ *
+ * Contract, in unfused fp32. For body b with range (first, cnt) and point i < cnt, L = points[first + i],
+ * and R, c, v, w from poses[b]:
+ *     d   = (R0*L.x + R1*L.y) + R2*L.z,  (R3*L.x + R4*L.y) + R5*L.z,  (R6*L.x + R7*L.y) + R8*L.z
+ *     x   = c + d
+ *     Q   = ocean_surface_query at q = (x.x, x.z) with (iterations, tolerance):
+ *           base p = (Q0, Q2), eta = Q1, res = Q7
+ *     t   = (eta - x.y) / (L.half_height + L.half_height) + 0.5f
+ *     s   = min(max(t, 0), 1), NaN t -> 0                       submerged fraction
+ *     u   = slots 4..6 of ocean_surface_velocity at base p when water_velocity, else 0
+ *     vp  = v + (w.y*d.z - w.z*d.y, w.z*d.x - w.x*d.z, w.x*d.y - w.y*d.x)
+ *     rel = u - vp;   m = sqrtf((rel.x*rel.x + rel.y*rel.y) + rel.z*rel.z)
+ *     k   = s * (L.drag_lin + L.drag_quad * m)
+ *     F   = (k*rel.x,  rho_g * (L.volume * s) + k*rel.y,  k*rel.z)
+ *     T   = (d.y*F.z - d.z*F.y,  d.z*F.x - d.x*F.z,  d.x*F.y - d.y*F.x)      torque about c
+ *     a_i = (F.x, F.y, F.z, L.volume*s,  T.x, T.y, T.z, s > 0 ? 1 : 0)
+ *     point_out[offset_b + i] = (p.x, eta, p.z, res,  F.x, F.y, F.z, s)      offset_b = sum of earlier counts
+ * Only the query's vertex stage is evaluated (the normal and the Jacobian are not used). So loads[b] is
+ * (force, submerged volume, torque about the centre, number of wet points): the sum of a_i, component by
+ * component, in this fixed order, which is part of the contract:
+ *     fold64(a): pad a (len <= 64) with +0.0f to 64; for h in 32,16,8,4,2,1: a = a[:h] + a[h:]; return a[0]
+ *     sum(a):    len <= 64 -> fold64(a); else sum([fold64(a[j:j+64]) for j in 0,64,128,...])
+ * a radix-64 tree over consecutive points. No float atomics: the same poses on the same maps give the same
+ * bits on every run and for every split of the bodies over calls. One freedom is taken: consecutive bodies
+ * of at most 32 points share a wave in aligned power-of-two segments and skip the fold steps that would add
+ * the +0.0f padding, so a sum that is zero may carry either sign.
+ *
+ * At most two kernel launches on the plan's stream (the second only when a body has more than 64 points),
+ * plus the atlas repack where ocean_surface_query's rule would use it for instance_points points (the same
+ * bits either way; the plan's atlas grows on first use as there). No host synchronisation, and no other
+ * allocation after create.
+ * OCEAN_ERR_INVALID, before any device call: a null hull set; the argument rules of ocean_surface_query
+ * (iterations 0..64, tolerance finite and >= 0, its (generator, cascade) rules); a non-finite or negative
+ * rho_g; null poses or loads; gens[0] on a plan other than the hull set's; water_velocity other than 0 or
+ * 1; water_velocity == 1 with rates that were never calculated or are stale (the rule of
+ * ocean_surface_velocity, naming the index in `gens`). With water_velocity == 0 the water is taken at
+ * rest and rates are not needed. No reference counterpart. */
+int ocean_hulls_loads(ocean_hulls* hulls, ocean_generator* const* gens, const int* cascades, int count,
+                      const float* poses, float rho_g, int iterations, float tolerance, int water_velocity,
+                      float* loads, float* point_out);
+
+/* Debug: hull sets created after enable = 0 give every body its own waves; by default consecutive bodies
+ * of at most 32 points share a wave (the same bits either way; tools/hulls_bench.py times both). */
+int ocean_debug_hulls_packing(int enable);
+
 #ifdef __cplusplus
 }
 #endif

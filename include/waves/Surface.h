@@ -11,6 +11,7 @@
 
 #include "oceanfft.h"
 #include "vision/RenderDevice.h"
+#include "waves/FFTCalculator.h"
 #include "waves/Generator.h"
 
 namespace Waves
@@ -67,6 +68,43 @@ private:
   int verticesLodRes = 0;
   Vision::ID velocities = 0;
   int64_t velocityPoints = 0;
+};
+
+// Floating bodies as sets of hull points (ocean_hulls, oceanfft.h): per step, the bodies' poses in and one
+// wrench per body out, in one fused pass over the query, the water velocity, the load model and a sum per
+// body whose order is fixed, so a step is replayable bit for bit.
+class HullSet
+{
+public:
+  // points: nPoints x 8 host floats (lx, ly, lz, volume, half_height, drag_lin, drag_quad, 0) in the body
+  // frame; ranges: bodies x 2 host int32 (first, count) into points, which bodies may share (instances of one
+  // hull). Copied to the device; throws std::runtime_error on invalid arguments.
+  HullSet(Vision::RenderDevice* device, FFTCalculator* fft, const float* points, int64_t nPoints, const int32_t* ranges,
+          int bodies);
+  ~HullSet();
+  HullSet(const HullSet&) = delete;
+  HullSet& operator=(const HullSet&) = delete;
+
+  int GetBodies() const { return ocean_hulls_bodies(hulls); }
+  int64_t GetInstancePoints() const { return ocean_hulls_instance_points(hulls); }
+  ocean_hulls* GetHandle() const { return hulls; }
+
+  // posesDevice: bodies x 20 floats in device memory (R[9] row-major body->world, centre, velocity, angular
+  // velocity, 0, 0). Returns a buffer texture of 2*bodies x 1 RGBA32F texels: per body (Fx, Fy, Fz, submerged
+  // volume), (Tx, Ty, Tz about the centre, wet points). waterVelocity needs Generator::CalculateRates() since
+  // each generator's last CalculateOcean; without it the water is taken at rest. With pointOutput the
+  // per-point rows (base x, water height, base z, residual), (Fx, Fy, Fz, submerged fraction) land in
+  // GetPointOutput() (2*instancePoints x 1 texels). Enqueued on the device's stream; both textures are owned
+  // by the set and reused.
+  Vision::ID Loads(const std::vector<Generator*>& generators, const float* posesDevice, float rhoG, int iterations,
+                   float tolerance, bool waterVelocity, bool pointOutput = false);
+  Vision::ID GetPointOutput() const { return pointRows; }
+
+private:
+  Vision::RenderDevice* renderDevice = nullptr;
+  ocean_hulls* hulls = nullptr;
+  Vision::ID loads = 0;
+  Vision::ID pointRows = 0;
 };
 
 }  // namespace Waves

@@ -101,6 +101,12 @@ SIGNATURES = {
     "ocean_generator_height_rate_map": (_vp, [_vp, _i]),
     "ocean_generator_displacement_rate_map": (_vp, [_vp, _i]),
     "ocean_surface_velocity": (_i, [_vp, _vp, _i, _vp, ctypes.c_int64, _vp]),
+    "ocean_hulls_create": (_i, [ctypes.POINTER(_vp), _vp, _vp, ctypes.c_int64, _vp, _i]),
+    "ocean_hulls_destroy": (_i, [_vp]),
+    "ocean_hulls_bodies": (_i, [_vp]),
+    "ocean_hulls_instance_points": (ctypes.c_int64, [_vp]),
+    "ocean_debug_hulls_packing": (_i, [_i]),
+    "ocean_hulls_loads": (_i, [_vp, _vp, _vp, _i, _vp, _f, _i, _f, _i, _vp, _vp]),
     "ocean_generator_set_half_spectrum": (_i, [_vp, _i]),
     "ocean_generator_set_four_step": (_i, [_vp, _i]),
     "ocean_generator_set_h0_memo": (_i, [_vp, _i]),

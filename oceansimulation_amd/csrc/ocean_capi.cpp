@@ -2506,20 +2506,16 @@ float* ocean_generator_displacement_rate_map(ocean_generator* g, int c)
   return generator_rate_map(g, c, 1, "ocean_generator_displacement_rate_map");
 }
 
-int ocean_surface_velocity(ocean_generator* const* gens, const int* cascades, int count, const float* xz,
-                           int64_t points, float* out)
+// The rate maps of a request's cascades, which must be calculated and not older than the maps
+static int surface_rates(ocean_generator* const* gens, const int* cascades, int count, const ocean_fft* fft,
+                         SurfaceRates& r, const char* who)
 {
-  SurfaceParams p;
-  ocean_fft* fft;
-  const int rc = surface_params(gens, cascades, count, p, fft, "ocean_surface_velocity");
-  if (rc != OCEAN_OK)
-    return rc;
-  SurfaceRates r{};
+  r = SurfaceRates{};
   for (int i = 0; i < count; i++)
   {
     ocean_generator* g = gens[i];
     if (!g->rates || !g->rates_fresh)
-      return fail(OCEAN_ERR_INVALID, std::string("ocean_surface_velocity: generator ") + std::to_string(i) +
+      return fail(OCEAN_ERR_INVALID, std::string(who) + ": generator " + std::to_string(i) +
                                          (g->rates ? " has stale rates (a frame was calculated since"
                                                    : " has no rates (call") +
                                          " ocean_generator_calculate_rates)");
@@ -2527,11 +2523,237 @@ int ocean_surface_velocity(ocean_generator* const* gens, const int* cascades, in
     r.height[i] = g->rates + nn * (2 * cascades[i]);
     r.disp[i] = g->rates + nn * (2 * cascades[i] + 1);
   }
+  return OCEAN_OK;
+}
+
+int ocean_surface_velocity(ocean_generator* const* gens, const int* cascades, int count, const float* xz,
+                           int64_t points, float* out)
+{
+  SurfaceParams p;
+  ocean_fft* fft;
+  int rc = surface_params(gens, cascades, count, p, fft, "ocean_surface_velocity");
+  if (rc != OCEAN_OK)
+    return rc;
+  SurfaceRates r;
+  rc = surface_rates(gens, cascades, count, fft, r, "ocean_surface_velocity");
+  if (rc != OCEAN_OK)
+    return rc;
   if (points < 0 || (points > 0 && (!xz || !out)))
     return fail(OCEAN_ERR_INVALID, "ocean_surface_velocity: null positions/output or negative count");
   HIP_TRY(launch_surface_velocity(p, r, reinterpret_cast<const float2*>(xz), points, reinterpret_cast<float4*>(out),
                                   fft->stream, fft->cus),
           "ocean_surface_velocity");
+  return OCEAN_OK;
+}
+
+// ---- hull sets: net wave force and torque on batches of floating bodies ----
+// Consecutive bodies of at most 32 points share a wave (tools/hulls_bench.py times both)
+static bool g_hulls_pack = true;
+
+int ocean_debug_hulls_packing(int enable)
+{
+  g_hulls_pack = enable != 0;
+  return OCEAN_OK;
+}
+
+struct ocean_hulls
+{
+  ocean_fft* fft = nullptr;
+  int bodies = 0;
+  int64_t instance_points = 0;
+  int items = 0;    // 64-point tiles
+  int n_folds = 0;  // bodies of more than one tile
+  float4* points = nullptr;
+  HullTile* tiles = nullptr;
+  HullBody* body_table = nullptr;
+  HullFold* folds = nullptr;
+  float4* partial = nullptr;  // one 8-float partial per tile of a body in `folds`
+};
+
+int ocean_hulls_destroy(ocean_hulls* h)
+{
+  if (!h)
+    return OCEAN_OK;
+  if (h->fft)
+    (void)hipStreamSynchronize(h->fft->stream);
+  for (void* p : {(void*)h->points, (void*)h->tiles, (void*)h->body_table, (void*)h->folds, (void*)h->partial})
+    if (p)
+      (void)hipFree(p);
+  delete h;
+  return OCEAN_OK;
+}
+
+int ocean_hulls_create(ocean_hulls** out, ocean_fft* fft, const float* points, int64_t n_points, const int32_t* ranges,
+                       int bodies)
+{
+  if (!out || !fft || !points || !ranges)
+    return fail(OCEAN_ERR_INVALID, "ocean_hulls_create: null argument");
+  *out = nullptr;
+  if (bodies < 1 || bodies > 1048576)
+    return fail(OCEAN_ERR_INVALID, "ocean_hulls_create: bodies outside 1..1048576");
+  if (n_points < 1)
+    return fail(OCEAN_ERR_INVALID, "ocean_hulls_create: no points");
+  int64_t n_tiles = 0, instance_points = 0;
+  for (int b = 0; b < bodies; b++)
+  {
+    const int64_t first = ranges[2 * b], count = ranges[2 * b + 1];
+    if (count < 1 || count > 262144)
+      return fail(OCEAN_ERR_INVALID, "ocean_hulls_create: body " + std::to_string(b) + " has a count outside 1..262144");
+    if (first < 0 || first + count > n_points)
+      return fail(OCEAN_ERR_INVALID, "ocean_hulls_create: the range of body " + std::to_string(b) + " leaves the points");
+    n_tiles += (count + kHullTilePoints - 1) / kHullTilePoints;
+    instance_points += count;
+  }
+  for (int64_t i = 0; i < n_points; i++)
+  {
+    const float* l = points + 8 * i;
+    for (int k = 0; k < 8; k++)
+      if (!std::isfinite(l[k]))
+        return fail(OCEAN_ERR_INVALID, "ocean_hulls_create: point " + std::to_string(i) + " has a non-finite field");
+    if (l[3] < 0.0f || !(l[4] > 0.0f) || l[5] < 0.0f || l[6] < 0.0f)
+      return fail(OCEAN_ERR_INVALID, "ocean_hulls_create: point " + std::to_string(i) +
+                                         " needs volume >= 0, half_height > 0 and drag coefficients >= 0");
+  }
+  if (n_tiles > INT32_MAX)
+    return fail(OCEAN_ERR_OOM, "ocean_hulls_create: more than 2^31 - 1 tiles of 64 points");
+
+  // the work items, in the order of the bodies: a body's 64-point tiles, or one packed tile for a run of
+  // consecutive small bodies with one segment size; point_out rows in the order of the bodies
+  std::vector<HullTile> tiles;
+  std::vector<HullBody> table((size_t)bodies);
+  std::vector<HullFold> folds;
+  tiles.reserve((size_t)n_tiles);
+  int slot = 0;
+  auto segment = [&](int b) {  // the power of two body b's points fit in
+    int seg = 1;
+    while (seg < ranges[2 * b + 1])
+      seg *= 2;
+    return seg;
+  };
+  int64_t rows = 0;
+  for (int b = 0; b < bodies; b++)
+  {
+    table[b] = HullBody{rows, ranges[2 * b], ranges[2 * b + 1]};
+    rows += ranges[2 * b + 1];
+  }
+  for (int b = 0; b < bodies; b++)
+  {
+    const int first = ranges[2 * b], count = ranges[2 * b + 1];
+    const int seg = segment(b);
+    int run = 1;  // consecutive bodies with this segment size, as many as fit a wave
+    while (g_hulls_pack && seg <= kHullTilePoints / 2 && run < kHullTilePoints / seg && b + run < bodies &&
+           segment(b + run) == seg)
+      run++;
+    if (run > 1)
+    {
+      HullTile t{};
+      t.count = run;
+      t.body = b;
+      t.slot = -1;
+      t.seg = seg;
+      tiles.push_back(t);
+      b += run - 1;
+      continue;
+    }
+    const int64_t offset = table[b].offset;
+    const int nt = (count + kHullTilePoints - 1) / kHullTilePoints;
+    if (nt > 1)
+      folds.push_back(HullFold{b, slot, nt, 0});
+    for (int j = 0; j < nt; j++)
+      tiles.push_back(HullTile{offset + (int64_t)j * kHullTilePoints, first + j * kHullTilePoints,
+                               std::min(kHullTilePoints, count - j * kHullTilePoints), b, nt > 1 ? slot + j : -1});
+    if (nt > 1)
+      slot += nt;
+  }
+
+  auto* h = new ocean_hulls();
+  h->fft = fft;
+  h->bodies = bodies;
+  h->instance_points = instance_points;
+  h->items = (int)tiles.size();
+  h->n_folds = (int)folds.size();
+  hipError_t e = hipMalloc(&h->points, (size_t)n_points * 2 * sizeof(float4));
+  if (e == hipSuccess)
+    e = hipMalloc(&h->tiles, tiles.size() * sizeof(HullTile));
+  if (e == hipSuccess)
+    e = hipMalloc(&h->body_table, table.size() * sizeof(HullBody));
+  if (e == hipSuccess && !folds.empty())
+    e = hipMalloc(&h->folds, folds.size() * sizeof(HullFold));
+  if (e == hipSuccess && slot > 0)
+    e = hipMalloc(&h->partial, (size_t)slot * 2 * sizeof(float4));
+  // synchronous copies from the caller's and these pageable buffers: complete on return
+  if (e == hipSuccess)
+    e = hipMemcpy(h->points, points, (size_t)n_points * 2 * sizeof(float4), hipMemcpyHostToDevice);
+  if (e == hipSuccess)
+    e = hipMemcpy(h->tiles, tiles.data(), tiles.size() * sizeof(HullTile), hipMemcpyHostToDevice);
+  if (e == hipSuccess)
+    e = hipMemcpy(h->body_table, table.data(), table.size() * sizeof(HullBody), hipMemcpyHostToDevice);
+  if (e == hipSuccess && !folds.empty())
+    e = hipMemcpy(h->folds, folds.data(), folds.size() * sizeof(HullFold), hipMemcpyHostToDevice);
+  if (e != hipSuccess)
+  {
+    h->fft = nullptr;
+    ocean_hulls_destroy(h);
+    return fail(e == hipErrorOutOfMemory ? OCEAN_ERR_OOM : OCEAN_ERR_HIP,
+                std::string("ocean_hulls_create: ") + hipGetErrorString(e));
+  }
+  *out = h;
+  return OCEAN_OK;
+}
+
+int ocean_hulls_bodies(const ocean_hulls* h) { return h ? h->bodies : 0; }
+
+int64_t ocean_hulls_instance_points(const ocean_hulls* h) { return h ? h->instance_points : 0; }
+
+int ocean_hulls_loads(ocean_hulls* h, ocean_generator* const* gens, const int* cascades, int count, const float* poses,
+                      float rho_g, int iterations, float tolerance, int water_velocity, float* loads, float* point_out)
+{
+  if (!h)
+    return fail(OCEAN_ERR_INVALID, "ocean_hulls_loads: null hull set");
+  SurfaceParams p;
+  ocean_fft* fft;
+  int rc = surface_params(gens, cascades, count, p, fft, "ocean_hulls_loads");
+  if (rc != OCEAN_OK)
+    return rc;
+  if (gens[0]->fft != h->fft)
+    return fail(OCEAN_ERR_INVALID, "ocean_hulls_loads: the first generator is on another plan than the hull set");
+  if (iterations < 0 || iterations > 64)
+    return fail(OCEAN_ERR_INVALID, "ocean_hulls_loads: iterations outside 0..64");
+  if (!(tolerance >= 0.0f) || !std::isfinite(tolerance))
+    return fail(OCEAN_ERR_INVALID, "ocean_hulls_loads: tolerance must be finite and >= 0");
+  if (!(rho_g >= 0.0f) || !std::isfinite(rho_g))
+    return fail(OCEAN_ERR_INVALID, "ocean_hulls_loads: rho_g must be finite and >= 0");
+  if (water_velocity != 0 && water_velocity != 1)
+    return fail(OCEAN_ERR_INVALID, "ocean_hulls_loads: water_velocity must be 0 or 1");
+  if (!poses || !loads)
+    return fail(OCEAN_ERR_INVALID, "ocean_hulls_loads: null poses/loads");
+  SurfaceRates r{};
+  if (water_velocity)
+  {
+    rc = surface_rates(gens, cascades, count, fft, r, "ocean_hulls_loads");
+    if (rc != OCEAN_OK)
+      return rc;
+  }
+  const bool atlas = surface_query_use_atlas(p, h->instance_points, iterations);
+  rc = surface_atlas(fft, p, atlas, "ocean_hulls_loads");
+  if (rc != OCEAN_OK)
+    return rc;
+  if (atlas)
+    launch_surface_atlas(p, fft->stream, fft->cus);
+  HullCall call{};
+  call.points = h->points;
+  call.tiles = h->tiles;
+  call.bodies = h->body_table;
+  call.poses = poses;
+  call.loads = reinterpret_cast<float4*>(loads);
+  call.partial = h->partial;
+  call.point_out = reinterpret_cast<float4*>(point_out);
+  call.items = h->items;
+  call.iterations = iterations;
+  call.tolerance = tolerance;
+  call.rho_g = rho_g;
+  HIP_TRY(launch_hulls_loads(p, r, water_velocity != 0, call, h->folds, h->n_folds, fft->stream, fft->cus),
+          "ocean_hulls_loads");
   return OCEAN_OK;
 }
 

@@ -297,6 +297,51 @@ struct SurfaceRates
 };
 hipError_t launch_surface_velocity(const SurfaceParams& p, const SurfaceRates& r, const float2* xz, int64_t count,
                                    float4* out, hipStream_t stream, int cus);
+// ocean_hulls (include/oceanfft.h, device/k_hulls.h): the tables ocean_hulls_create builds and one call
+constexpr int kHullTilePoints = 64;  // points per work item: the lanes of one wave
+// One tile of one body: points [first, first + count) of the hull set's points, point_out rows from
+// `offset`, the fold into loads[body] (slot < 0) or partial[slot].
+// seg > 0: a packed tile instead, `count` consecutive small bodies from `body` on, body + j on lanes
+// [j * seg, j * seg + seg), its points and rows from HullBody (first, offset unused, slot < 0).
+struct HullTile
+{
+  int64_t offset;
+  int first, count, body, slot;
+  int seg, pad;
+};
+
+// A body's range and its first point_out row (packed tiles look their bodies up)
+struct HullBody
+{
+  int64_t offset;
+  int first, count;
+};
+
+// A body of more than one tile: its partials [slot, slot + tiles) fold into loads[body]
+struct HullFold
+{
+  int body, slot, tiles, pad;
+};
+
+struct HullCall
+{
+  const float4* points;  // [n_points][2]: (lx, ly, lz, volume), (half_height, drag_lin, drag_quad, 0)
+  const HullTile* tiles;
+  const HullBody* bodies;  // [bodies]
+  const float* poses;    // [bodies][20]
+  float4* loads;         // [bodies][2]
+  float4* partial;       // [multi-tile bodies' tiles][2]
+  float4* point_out;     // [instance points][2] or null
+  int items;
+  int iterations;
+  float tolerance, rho_g;
+};
+
+// At most two launches: the tiles (a wave each), then the bodies of more than one tile (folds / n_folds).
+// p.atlas non-null: sampled from the atlas, which the caller has repacked (launch_surface_atlas).
+hipError_t launch_hulls_loads(const SurfaceParams& p, const SurfaceRates& r, bool velocity, const HullCall& h,
+                              const HullFold* folds, int n_folds, hipStream_t stream, int cus);
+void launch_surface_atlas(const SurfaceParams& p, hipStream_t stream, int cus);
 size_t surface_atlas_texels(const SurfaceParams& p);
 bool surface_use_atlas(const SurfaceParams& p, int64_t points);
 bool surface_query_use_atlas(const SurfaceParams& p, int64_t points, int iterations);

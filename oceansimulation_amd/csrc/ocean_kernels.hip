@@ -29,6 +29,7 @@
 #include "device/memory.h"
 #include "device/mip_index.h"
 #include "device/spectrum.h"
+#include "device/surface_sample.h"
 
 namespace oceanfft
 {
@@ -246,51 +247,8 @@ hipError_t launch_peer_wait(const PeerWait& w, hipStream_t stream)
 // the oracle restatement (oracle_surface_vertex) is matched bit for bit. Memory: the maps of a
 // scene (3 x 256^2 x 36 B) live in L2; per vertex 32 B are written.
 // ------------------------------------------------------------------------------------------------
-// The four taps and weights of one sample: the texel indices of (i0, j0), (i1, j0), (i0, j1), (i1, j1).
-struct LinearTaps
-{
-  int o00, o10, o01, o11;
-  float w00, w10, w01, w11;
-};
-
-__device__ __forceinline__ LinearTaps linear_repeat_taps(int n, float u, float v)
-{
-#pragma clang fp contract(off)
-  const float s = u * (float)n - 0.5f, t = v * (float)n - 0.5f;
-  const float fs = floorf(s), ft = floorf(t);
-  const float a = s - fs, b = t - ft;
-  const int m = n - 1;  // n is a power of two: & m is the repeat wrap, also for negative indices
-  const int i0 = (int)fs & m, j0 = (int)ft & m, i1 = (i0 + 1) & m, j1 = (j0 + 1) & m;
-  return LinearTaps{j0 * n + i0, j0 * n + i1, j1 * n + i0, j1 * n + i1, (1.0f - a) * (1.0f - b), a * (1.0f - b),
-                    (1.0f - a) * b, a * b};
-}
-
-// Channel ch of a map of CH floats per texel, filtered: each stage loads only the channels it uses, one
-// dword per tap (the vertex stage 3 of 8, the normal stage 5 of 9): 2.95 -> 2.49 ms for the 4096^2-quad
-// mesh, bit-identical (tools/microbench/surfbench, profiles/r06_surfbench.log). A sampling wave's taps
-// are scattered (the camera warp spreads far vertices ~10 texels apart on a 5 m cascade), so the cost
-// is per load instruction: ATLAS repacks the channels each stage uses into one 16-B texel (one load per
-// tap and stage, plus the Jacobian's dword): 2.47 -> 1.35 ms with the repack included, 0.212 -> 0.121 ms
-// for the 1024^2-quad mesh, bit-identical (profiles/r06_surfbench2.log).
-template <int CH>
-__device__ __forceinline__ float linear_channel(const float* __restrict__ tex, const LinearTaps& k, int ch)
-{
-#pragma clang fp contract(off)
-  const float q00 = tex[k.o00 * CH + ch], q10 = tex[k.o10 * CH + ch], q01 = tex[k.o01 * CH + ch],
-              q11 = tex[k.o11 * CH + ch];
-  return k.w00 * q00 + k.w10 * q10 + k.w01 * q01 + k.w11 * q11;
-}
-
-// The bilinear sum of the four taps' lanes x, y, z, w (each as linear_channel's sum)
-__device__ __forceinline__ float4 linear_texel(const float4* __restrict__ tex, const LinearTaps& k)
-{
-#pragma clang fp contract(off)
-  const float4 q00 = tex[k.o00], q10 = tex[k.o10], q01 = tex[k.o01], q11 = tex[k.o11];
-  return make_float4(k.w00 * q00.x + k.w10 * q10.x + k.w01 * q01.x + k.w11 * q11.x,
-                     k.w00 * q00.y + k.w10 * q10.y + k.w01 * q01.y + k.w11 * q11.y,
-                     k.w00 * q00.z + k.w10 * q10.z + k.w01 * q01.z + k.w11 * q11.z,
-                     k.w00 * q00.w + k.w10 * q10.w + k.w01 * q01.w + k.w11 * q11.w);
-}
+// The taps, the filtered channel / texel and the vertex stage are in device/surface_sample.h (shared with
+// the hull loads, device/k_hulls.h).
 
 // the surface atlas of the cascades' maps (SurfaceParams::atlas)
 __global__ __launch_bounds__(256) void k_surface_atlas(SurfaceParams p)
@@ -302,39 +260,6 @@ __global__ __launch_bounds__(256) void k_surface_atlas(SurfaceParams p)
     const float4 h = p.c[c].height[t], d = p.c[c].disp[t];
     p.atlas[(size_t)(2 * c) * nn + t] = make_float4(h.x, h.w, d.x, 0.0f);
     p.atlas[(size_t)(2 * c + 1) * nn + t] = make_float4(h.y, h.z, d.y, d.z);
-  }
-}
-
-// Vertex stage (waveShader.glsl:101-110): cascade c samples at the position cascades < c displaced and
-// adds (scale * Dx, h, scale * Dz). (px, pz) enters as the base position, py as 0.
-template <bool ATLAS>
-__device__ __forceinline__ void surface_vertex_stage(const SurfaceParams& p, float& px, float& py, float& pz)
-{
-#pragma clang fp contract(off)
-  const int nn = p.n * p.n;
-  for (int c = 0; c < p.count; c++)
-  {
-    const float u = px / p.c[c].plane, v = pz / p.c[c].plane;
-    const LinearTaps k = linear_repeat_taps(p.n, u, v);
-    float h, dx, dz;
-    if constexpr (ATLAS)
-    {
-      const float4 a = linear_texel(p.atlas + (size_t)(2 * c) * nn, k);
-      h = a.x;
-      dx = a.y;
-      dz = a.z;
-    }
-    else
-    {
-      const float* hm = reinterpret_cast<const float*>(p.c[c].height);
-      const float* dm = reinterpret_cast<const float*>(p.c[c].disp);
-      h = linear_channel<4>(hm, k, 0);
-      dx = linear_channel<4>(hm, k, 3);
-      dz = linear_channel<4>(dm, k, 0);
-    }
-    px += p.c[c].scale * dx;
-    py += h;
-    pz += p.c[c].scale * dz;
   }
 }
 
@@ -480,26 +405,7 @@ __global__ __launch_bounds__(256) void k_surface_velocity(SurfaceParams p, Surfa
     const float2 q = xz[idx];
     float px = q.x, py = 0.0f, pz = q.y;
     float ux = 0.0f, uy = 0.0f, uz = 0.0f;
-    for (int c = 0; c < p.count; c++)
-    {
-      const float u = px / p.c[c].plane, v = pz / p.c[c].plane;
-      const LinearTaps k = linear_repeat_taps(p.n, u, v);
-      const float4 h = linear_texel(p.c[c].height, k), d = linear_texel(p.c[c].disp, k);
-      const float* rh = reinterpret_cast<const float*>(r.height[c]);
-      const float* rd = reinterpret_cast<const float*>(r.disp[c]);
-      const float rh_h = linear_channel<4>(rh, k, 0), rh_dx = linear_channel<4>(rh, k, 3);
-      const float rd_dz = linear_channel<4>(rd, k, 0);
-      const float s = p.c[c].scale;
-      const float vx = s * (rh_dx + (d.y * ux + d.w * uz));  // dDx/dt + grad Dx . u
-      const float vy = rh_h + (h.y * ux + h.z * uz);         // dh/dt + grad h . u
-      const float vz = s * (rd_dz + (d.w * ux + d.z * uz));  // dDz/dt + grad Dz . u
-      px += s * h.w;
-      py += h.x;
-      pz += s * d.x;
-      ux += vx;
-      uy += vy;
-      uz += vz;
-    }
+    surface_particle_velocity(p, r, px, py, pz, ux, uy, uz);
     out[2 * idx] = make_float4(px, py, pz, 0.0f);
     out[2 * idx + 1] = make_float4(ux, uy, uz, 0.0f);
   }
@@ -702,6 +608,16 @@ hipError_t launch_generate_spectrum(const OceanSettings& s, int n, float4* h0, h
   return hipGetLastError();
 }
 
+// the repack of the cascades' maps into p.atlas (k_surface_atlas), ahead of a request that samples it
+void launch_surface_atlas(const SurfaceParams& p, hipStream_t stream, int cus)
+{
+  const long texels = (long)p.count * p.n * p.n;
+  long ab = (texels + 255) / 256;
+  if (ab > (long)cus * 4)
+    ab = (long)cus * 4;
+  hipLaunchKernelGGL(k_surface_atlas, dim3((unsigned)ab), dim3(256), 0, stream, p);
+}
+
 hipError_t launch_surface(const SurfaceParams& p, const SurfacePlane& plane, const float2* xz, int64_t count,
                           float4* out, hipStream_t stream, int cus)
 {
@@ -713,11 +629,7 @@ hipError_t launch_surface(const SurfaceParams& p, const SurfacePlane& plane, con
     blocks = cap;
   if (p.atlas)
   {
-    const long texels = (long)p.count * p.n * p.n;
-    long ab = (texels + 255) / 256;
-    if (ab > (long)cus * 4)
-      ab = (long)cus * 4;
-    hipLaunchKernelGGL(k_surface_atlas, dim3((unsigned)ab), dim3(256), 0, stream, p);
+    launch_surface_atlas(p, stream, cus);
     hipLaunchKernelGGL(k_surface<true>, dim3((unsigned)blocks), dim3(256), 0, stream, p, plane, xz, count, out);
   }
   else
@@ -736,11 +648,7 @@ hipError_t launch_surface_query(const SurfaceParams& p, const float2* xz, int64_
     blocks = cap;
   if (p.atlas)
   {
-    const long texels = (long)p.count * p.n * p.n;
-    long ab = (texels + 255) / 256;
-    if (ab > (long)cus * 4)
-      ab = (long)cus * 4;
-    hipLaunchKernelGGL(k_surface_atlas, dim3((unsigned)ab), dim3(256), 0, stream, p);
+    launch_surface_atlas(p, stream, cus);
     hipLaunchKernelGGL(k_surface_query<true>, dim3((unsigned)blocks), dim3(256), 0, stream, p, xz, count, iterations,
                        tolerance, out);
   }

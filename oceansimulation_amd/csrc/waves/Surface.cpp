@@ -1,5 +1,6 @@
 // Waves::SurfaceSampler over ocean_surface_sample_plane / ocean_surface_query /
-// ocean_surface_sample_plane_lod / ocean_surface_velocity (include/oceanfft.h).
+// ocean_surface_sample_plane_lod / ocean_surface_velocity, and Waves::HullSet over ocean_hulls
+// (include/oceanfft.h).
 #include "waves/Surface.h"
 
 #include <stdexcept>
@@ -134,6 +135,55 @@ Vision::ID SurfaceSampler::Velocity(const std::vector<Generator*>& generators, c
   if (rc != OCEAN_OK)
     throw std::runtime_error(std::string("SurfaceSampler::Velocity: ") + ocean_last_error());
   return velocities;
+}
+
+HullSet::HullSet(Vision::RenderDevice* device, FFTCalculator* fft, const float* points, int64_t nPoints,
+                 const int32_t* ranges, int bodies)
+    : renderDevice(device)
+{
+  if (ocean_hulls_create(&hulls, fft ? fft->GetPlan() : nullptr, points, nPoints, ranges, bodies) != OCEAN_OK)
+    throw std::runtime_error(std::string("HullSet: ") + ocean_last_error());
+  Vision::Texture2DDesc desc;
+  desc.Width = 2 * (std::size_t)bodies;
+  desc.Height = 1;
+  desc.PixelType = Vision::PixelType::RGBA32Float;
+  loads = renderDevice->CreateTexture2D(desc);
+}
+
+HullSet::~HullSet()
+{
+  ocean_hulls_destroy(hulls);
+  if (loads)
+    renderDevice->DestroyTexture2D(loads);
+  if (pointRows)
+    renderDevice->DestroyTexture2D(pointRows);
+}
+
+Vision::ID HullSet::Loads(const std::vector<Generator*>& generators, const float* posesDevice, float rhoG,
+                          int iterations, float tolerance, bool waterVelocity, bool pointOutput)
+{
+  if (pointOutput && !pointRows)
+  {
+    Vision::Texture2DDesc desc;
+    desc.Width = 2 * (std::size_t)GetInstancePoints();
+    desc.Height = 1;
+    desc.PixelType = Vision::PixelType::RGBA32Float;
+    pointRows = renderDevice->CreateTexture2D(desc);
+  }
+  std::vector<ocean_generator*> gens;
+  std::vector<int> cascades;
+  for (auto* g : generators)
+  {
+    gens.push_back(g->GetHandle());
+    cascades.push_back(0);
+  }
+  const int rc = ocean_hulls_loads(hulls, gens.data(), cascades.data(), (int)gens.size(), posesDevice, rhoG, iterations,
+                                   tolerance, waterVelocity ? 1 : 0,
+                                   static_cast<float*>(renderDevice->GetTexturePointer(loads)),
+                                   pointOutput ? static_cast<float*>(renderDevice->GetTexturePointer(pointRows)) : nullptr);
+  if (rc != OCEAN_OK)
+    throw std::runtime_error(std::string("HullSet::Loads: ") + ocean_last_error());
+  return loads;
 }
 
 }  // namespace Waves

@@ -1,7 +1,8 @@
 """Surface consumer of the generator maps: resources/waveShader.glsl's vertex
 displacement (:101-110) and fragment slope normal / Jacobian (:127-144), per mesh vertex, through
 ocean_surface_sample / ocean_surface_sample_plane, and the opposite direction, the water surface above
-world positions, through ocean_surface_query (include/oceanfft.h)."""
+world positions, through ocean_surface_query, and the loads on floating bodies built on both,
+ocean_hulls_loads (include/oceanfft.h)."""
 from __future__ import annotations
 
 import ctypes
@@ -109,6 +110,59 @@ class SurfaceSampler:
         return out.to_host((pts, FLOATS_PER_VERTEX))
 
 
+class HullSet:
+    """Floating bodies as sets of hull points (ocean_hulls, include/oceanfft.h). points: (P, 8) float32
+    (lx, ly, lz, volume, half_height, drag_lin, drag_quad, 0) in the body frame; ranges: (bodies, 2) int32
+    (first, count) into points, which bodies may share."""
+
+    def __init__(self, fft, points: np.ndarray, ranges: np.ndarray):
+        self._points = np.ascontiguousarray(points, np.float32).reshape(-1, FLOATS_PER_VERTEX)
+        self._ranges = np.ascontiguousarray(ranges, np.int32).reshape(-1, 2)
+        self.fft = fft
+        h = ctypes.c_void_p()
+        check(lib().ocean_hulls_create(ctypes.byref(h), fft.handle, self._points.ctypes.data,
+                                       ctypes.c_int64(self._points.shape[0]), self._ranges.ctypes.data,
+                                       self._ranges.shape[0]), "ocean_hulls_create")
+        self._h = h
+        self.bodies = int(lib().ocean_hulls_bodies(h))
+        self.instance_points = int(lib().ocean_hulls_instance_points(h))
+
+    @property
+    def handle(self):
+        return self._h
+
+    def loads(self, sampler: SurfaceSampler, poses_ptr: int, loads_ptr: int, point_out_ptr: int = 0,
+              rho_g: float = 9810.0, iterations: int = 8, tolerance: float = 0.0, water_velocity: bool = False) -> None:
+        """Enqueue one step on the plan's stream: device poses (bodies, 20) -> device loads (bodies, 8) and,
+        with point_out_ptr, the per-point rows (instance_points, 8)."""
+        check(lib().ocean_hulls_loads(self._h, sampler._gens, sampler._cas, len(sampler.pairs),
+                                      ctypes.c_void_p(poses_ptr), ctypes.c_float(rho_g), int(iterations),
+                                      ctypes.c_float(tolerance), int(water_velocity), ctypes.c_void_p(loads_ptr),
+                                      ctypes.c_void_p(point_out_ptr)), "ocean_hulls_loads")
+
+    def loads_host(self, sampler: SurfaceSampler, poses: np.ndarray, rho_g: float = 9810.0, iterations: int = 8,
+                   tolerance: float = 0.0, water_velocity: bool = False):
+        """(loads (bodies, 8), point_out (instance_points, 8)) of host poses (bodies, 20)."""
+        poses = np.ascontiguousarray(poses, np.float32).reshape(self.bodies, 20)
+        src = DeviceBuffer.from_array(poses)
+        out = DeviceBuffer(self.bodies * FLOATS_PER_VERTEX * 4)
+        pts = DeviceBuffer(self.instance_points * FLOATS_PER_VERTEX * 4)
+        self.loads(sampler, src.ptr, out.ptr, pts.ptr, rho_g, iterations, tolerance, water_velocity)
+        self.fft.synchronize()
+        return out.to_host((self.bodies, FLOATS_PER_VERTEX)), pts.to_host((self.instance_points, FLOATS_PER_VERTEX))
+
+    def close(self) -> None:
+        if self._h:
+            lib().ocean_hulls_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def host_cascades(pairs):
     """[(height, disp, jac, planeSize, displacement)] host copies, for the CPU oracle."""
     out = []
@@ -119,4 +173,4 @@ def host_cascades(pairs):
     return out
 
 
-__all__ = ["SurfaceSampler", "host_cascades", "FLOATS_PER_VERTEX", "hip"]
+__all__ = ["SurfaceSampler", "HullSet", "host_cascades", "FLOATS_PER_VERTEX", "hip"]
