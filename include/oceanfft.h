@@ -335,6 +335,12 @@ int ocean_debug_hash(const uint32_t* xy, int count, uint32_t* raw, float* uv, vo
  * workgroups on hip_stream: a rate-limited HBM read + write stream (bench.py prices a slab rank's
  * exchange traffic with it on one GPU). No reference counterpart. */
 int ocean_debug_copy(void* dst, const void* src, size_t bytes, int workgroups, void* hip_stream);
+/* Cap the EncodeIFFT work image / work slab of this plan at `bytes`: the plan never allocates or keeps
+ * one larger than that. An allocation above the cap is not attempted and counts as failed, so the
+ * transform takes the documented fallback (with no work image at all: the in-place row and column
+ * passes); a work image already held and larger than the cap is freed after the plan's stream drains.
+ * Default: (size_t)-1, no cap. For tests of the in-place fallback; no other effect. */
+int ocean_debug_fft_work_limit(ocean_fft* fft, size_t bytes);
 
 /* ---- Surface consumer: the renderer's use of the maps -------------------
  * resources/waveShader.glsl evaluated per mesh vertex on the maps of `count` (generator, cascade)

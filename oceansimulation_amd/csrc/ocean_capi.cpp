@@ -74,6 +74,7 @@ struct ocean_fft
   float4* work = nullptr;      // column-first EncodeIFFT work image (the reference's workImage)
   int work_images = 0;
   size_t work_texels = 0;      // four-step EncodeIFFT (N = 16384): work slab of N x kFourStepSlab texels
+  size_t work_limit = (size_t)-1;  // ocean_debug_fft_work_limit: no work image / slab above this many bytes
   float4* surf_atlas = nullptr;  // the surface consumer's repacked maps (launch_surface), grown on demand
   size_t surf_atlas_texels = 0;
 };
@@ -318,6 +319,22 @@ int ocean_fft_set_cu_budget(ocean_fft* fft, int cus)
   return OCEAN_OK;
 }
 
+int ocean_debug_fft_work_limit(ocean_fft* fft, size_t bytes)
+{
+  if (!fft)
+    return fail(OCEAN_ERR_INVALID, "ocean_debug_fft_work_limit: null plan");
+  fft->work_limit = bytes;
+  if (fft->work && fft->work_texels * sizeof(float4) > bytes)
+  {
+    HIP_TRY(hipStreamSynchronize(fft->stream), "hipStreamSynchronize");  // launches may still read it
+    (void)hipFree(fft->work);
+    fft->work = nullptr;
+    fft->work_images = 0;
+    fft->work_texels = 0;
+  }
+  return OCEAN_OK;
+}
+
 int ocean_fft_encode_ifft_batch(ocean_fft* fft, float* images, int n_images)
 {
   if (!fft || !images || n_images < 1)
@@ -332,7 +349,10 @@ int ocean_fft_encode_ifft_batch(ocean_fft* fft, float* images, int n_images)
     if (fft->work_images < want)
     {
       float4* w = nullptr;
-      if (hipMalloc(&w, (size_t)want * fft->n * fft->n * sizeof(float4)) == hipSuccess)
+      const size_t bytes = (size_t)want * fft->n * fft->n * sizeof(float4);
+      if (bytes > fft->work_limit)
+        ;  // capped (ocean_debug_fft_work_limit): as a failed allocation
+      else if (hipMalloc(&w, bytes) == hipSuccess)
       {
         if (fft->work)
           (void)hipFree(fft->work);
@@ -367,7 +387,9 @@ int ocean_fft_encode_ifft_batch(ocean_fft* fft, float* images, int n_images)
     if (fft->work_texels < want)
     {
       float4* w = nullptr;
-      if (hipMalloc(&w, want * sizeof(float4)) == hipSuccess)
+      if (want * sizeof(float4) > fft->work_limit)
+        ;  // capped (ocean_debug_fft_work_limit): as a failed allocation
+      else if (hipMalloc(&w, want * sizeof(float4)) == hipSuccess)
       {
         if (fft->work)
           (void)hipFree(fft->work);

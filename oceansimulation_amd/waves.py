@@ -67,6 +67,12 @@ class FFTCalculator:
         """Size this plan's persistent grids for `cus` CUs (0 = all); see ocean_fft_set_cu_budget."""
         check(lib().ocean_fft_set_cu_budget(self._h, int(cus)), "ocean_fft_set_cu_budget")
 
+    def debug_work_limit(self, nbytes: int | None) -> None:
+        """Cap EncodeIFFT's work image / slab at `nbytes` (None: no cap); 0 forces the in-place passes.
+        See ocean_debug_fft_work_limit."""
+        cap = ctypes.c_size_t(-1).value if nbytes is None else int(nbytes)
+        check(lib().ocean_debug_fft_work_limit(self._h, cap), "ocean_debug_fft_work_limit")
+
     @property
     def handle(self):
         return self._h

@@ -762,9 +762,11 @@ def test_cu_budget_validation(ocean):
     gen.CalculateOcean(1.0)
     h1 = gen.height_map_host(0)
     fft.set_cu_budget(0)
-    gen2 = ocean.Generator(fft, 1)
+    gen2 = ocean.Generator(fft, 1)  # beside gen, so it cannot inherit gen's buffers with their contents
     gen2.CalculateOcean(1.0)
     assert np.array_equal(h1, gen2.height_map_host(0))
+    assert np.array_equal(gen.displacement_map_host(0), gen2.displacement_map_host(0))
+    assert np.array_equal(gen.jacobian_map_host(0), gen2.jacobian_map_host(0))
 
 
 def test_slab_rejects_too_narrow_slabs(ocean):
