@@ -23,7 +23,8 @@ all: $(LIB) $(WAVES) $(ORACLE) $(CPPTEST) $(APP)
 
 DEVICE_H := $(wildcard $(CSRC)/device/*.h) $(CSRC)/ocean_internal.h $(CSRC)/launch_common.h
 # one translation unit per frame path, compiled in parallel
-KERNEL_TUS := ocean_kernels launch_half launch_slab launch_fft launch_mips launch_rates launch_hulls
+KERNEL_TUS := ocean_kernels launch_half launch_slab launch_fft launch_mips launch_rates launch_hulls launch_bounds \
+              launch_raycast
 KERNEL_OBJS := $(KERNEL_TUS:%=$(CSRC)/build/%.o)
 $(CSRC)/build/%.o: $(CSRC)/%.hip $(DEVICE_H)
 	@mkdir -p $(CSRC)/build

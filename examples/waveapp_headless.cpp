@@ -17,7 +17,7 @@
 // Usage: waveapp_headless [--n 256] [--frames 600] [--dt 0.0166667] [--freeze A:B]...
 //                         [--edit F:G.field=value]... [--reseed reference|on-edit]
 //                         [--mesh RES (0 = no surface step)] [--probes K] [--velocity] [--mips] [--bodies K]
-//                         [--dump DIR]
+//                         [--rays K] [--dump DIR]
 // Prints one JSON line. --dump DIR writes height_G.npy, disp_G.npy, jac_G.npy (G = 0..2),
 // surface.npy ((RES+1)^2 x 8 floats) and scene.json for the last frame.
 // --probes K (default 0: nothing changes): after the last frame, the water surface above K points on a
@@ -38,6 +38,11 @@
 // 8 iterations, tolerance 0, water velocity on). The JSON line gains "bodies" and "body_max_residual"; --dump
 // adds hull_points.npy (64 x 8), hull_ranges.npy (K x 2, int32), body_poses.npy (K x 20), body_loads.npy
 // (K x 8), body_points.npy (64 K x 8) and height_rate_G.npy / disp_rate_G.npy of the last frame.
+// --rays K (default 0: nothing changes): a lidar ring, K rays from a mast at (0, 10, 0), azimuths evenly
+// spaced, 5 degrees below the horizon, tmax 400 m. Every frame builds the generators' bounds
+// (Generator::BuildBounds) and casts the ring (SurfaceSampler::Raycast: step 0.25, 256 steps, 10 bisections,
+// 4 iterations, tolerance 1e-3, fixed steps, pad 0). The JSON line gains "rays" and "ray_hits"; --dump adds
+// rays.npy (K x 8), hits.npy (K x 16) and bounds.npy (3 x 18) of the last frame.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -111,14 +116,14 @@ void usage()
 {
   std::fprintf(stderr, "usage: waveapp_headless [--n N] [--frames K] [--dt S] [--freeze A:B]... "
                        "[--edit F:G.field=value]... [--reseed reference|on-edit] [--mesh RES] [--probes K] "
-                       "[--velocity] [--mips] [--bodies K] [--dump DIR]\n");
+                       "[--velocity] [--mips] [--bodies K] [--rays K] [--dump DIR]\n");
 }
 
 }  // namespace
 
 int main(int argc, char** argv)
 {
-  int n = 256, frames = 600, mesh = 1024, probes = 0, bodies = 0;
+  int n = 256, frames = 600, mesh = 1024, probes = 0, bodies = 0, rays = 0;
   float dt = 1.0f / 60.0f;
   bool reseed_every_frame = true, mips = false, velocity = false;
   std::string dump;
@@ -144,6 +149,7 @@ int main(int argc, char** argv)
     else if (a == "--mesh") mesh = std::atoi(v);
     else if (a == "--probes") probes = std::atoi(v);
     else if (a == "--bodies") bodies = std::atoi(v);
+    else if (a == "--rays") rays = std::atoi(v);
     else if (a == "--dump") dump = v;
     else if (a == "--reseed") reseed_every_frame = std::string(v) != "on-edit";
     else if (a == "--freeze")
@@ -175,7 +181,7 @@ int main(int argc, char** argv)
     }
     i++;
   }
-  if (probes < 0 || bodies < 0)
+  if (probes < 0 || bodies < 0 || rays < 0)
   {
     usage();
     return 2;
@@ -242,6 +248,27 @@ int main(int argc, char** argv)
       }
     }
 
+    // the lidar ring
+    std::vector<float> rayData;
+    float* raysDevice = nullptr;
+    Vision::ID rayHits = 0;
+    if (rays > 0)
+    {
+      const double dep = 5.0 * 3.14159265358979323846 / 180.0;
+      for (int k = 0; k < rays; k++)
+      {
+        const double a = 2.0 * 3.14159265358979323846 * k / rays;
+        for (double c : {0.0, 10.0, 0.0, 0.0, std::cos(dep) * std::cos(a), -std::sin(dep), std::cos(dep) * std::sin(a), 400.0})
+          rayData.push_back((float)c);
+      }
+      if (hipMalloc(reinterpret_cast<void**>(&raysDevice), rayData.size() * sizeof(float)) != hipSuccess ||
+          hipMemcpy(raysDevice, rayData.data(), rayData.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+      {
+        std::fprintf(stderr, "waveapp_headless: cannot upload the rays\n");
+        return 1;
+      }
+    }
+
     device.BeginCommandBuffer();
     device.SubmitCommandBuffer();
     const auto t0 = std::chrono::steady_clock::now();
@@ -288,6 +315,12 @@ int main(int argc, char** argv)
           g->CalculateRates();
         bodyLoads = hulls->Loads(generators, posesDevice, rhoG, 8, 0.0f, true, true);
       }
+      if (rays > 0)
+      {
+        for (auto* g : generators)
+          g->BuildBounds();
+        rayHits = sampler.Raycast(generators, raysDevice, rays, 0.25f, 256, 10, 4, 1e-3f, INFINITY, 0.0f);
+      }
       device.SubmitCommandBuffer();
     }
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -302,6 +335,19 @@ int main(int argc, char** argv)
       device.GetTexture2DDataRaw(hulls->GetPointOutput(), bodyPointsHost.data());
       for (size_t k = 0; k < (size_t)bodies * 64; k++)
         bodyMaxResidual = std::max(bodyMaxResidual, bodyPointsHost[8 * k + 3]);
+    }
+
+    std::vector<float> rayHitsHost, boundsHost;
+    int rayHitCount = 0;
+    if (rays > 0 && frames > 0)
+    {
+      rayHitsHost.resize((size_t)rays * 16);
+      boundsHost.resize(3 * 18);
+      device.GetTexture2DDataRaw(rayHits, rayHitsHost.data());
+      for (int i = 0; i < 3; i++)
+        generators[i]->GetBounds(&boundsHost[18 * (size_t)i]);
+      for (int k = 0; k < rays; k++)
+        rayHitCount += rayHitsHost[16 * (size_t)k + 12] == 0.0f;
     }
 
     // the ring of buoys: which water is above each of them now (not part of the timed frames)
@@ -454,6 +500,13 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "cannot write %s\n", dump.c_str());
         return 1;
       }
+      if (!rayHitsHost.empty() && !(write_npy(dump + "/rays.npy", rayData.data(), {(size_t)rays, 8}) &&
+                                    write_npy(dump + "/hits.npy", rayHitsHost.data(), {(size_t)rays, 16}) &&
+                                    write_npy(dump + "/bounds.npy", boundsHost.data(), {3, 18})))
+      {
+        std::fprintf(stderr, "cannot write %s\n", dump.c_str());
+        return 1;
+      }
       if (probes > 0 && !(write_npy(dump + "/probes.npy", probeOut.data(), {(size_t)probes, 8}) &&
                           write_npy(dump + "/probe_xz.npy", probeXZ.data(), {(size_t)probes, 2})))
       {
@@ -500,6 +553,8 @@ int main(int argc, char** argv)
       std::snprintf(b, sizeof b, ", \"bodies\": %d, \"body_max_residual\": %.9g", bodies, bodyMaxResidual);
       probeJson += b;
     }
+    if (!rayHitsHost.empty())
+      probeJson += ", \"rays\": " + std::to_string(rays) + ", \"ray_hits\": " + std::to_string(rayHitCount);
     std::printf("{\"app\": \"waveapp_headless\", \"n\": %d, \"cascades\": 3, \"frames\": %d, \"frozen_frames\": %d, "
                 "\"reseeded_frames\": %d, \"reseed\": \"%s\", \"mesh_vertices\": %lld, \"seconds\": %.6f, "
                 "\"ms_per_frame\": %.6f, \"frames_per_s\": %.3f, \"height_field_points_per_s\": %.6e, "
@@ -511,6 +566,8 @@ int main(int argc, char** argv)
     delete hulls;
     if (posesDevice)
       (void)hipFree(posesDevice);
+    if (raysDevice)
+      (void)hipFree(raysDevice);
     for (auto* g : generators)
       delete g;
   }

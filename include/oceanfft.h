@@ -496,6 +496,86 @@ float* ocean_generator_displacement_rate_map(ocean_generator* gen, int cascade);
 int ocean_surface_velocity(ocean_generator* const* gens, const int* cascades, int count, const float* xz,
                            int64_t points, float* out);
 
+/* ---- Bounds of the maps and ray casting against the displaced surface --------------------------
+ * The calls above map base points and world positions to the water; these answer the line-of-sight
+ * question, where a ray meets it (lidar / radar / camera sensor models, picking, impacts, "is the camera
+ * under water along this ray"). A march needs the slab the surface lives in, so the bounds come first.
+ *
+ * ocean_generator_build_bounds enqueues, on the generator's stream, the minimum and maximum of every
+ * channel of the current maps: per cascade 18 floats, for channel j of (heightMap.x, .y, .z, .w,
+ * displacementMap.x, .y, .z, .w, jacobian) [2j] is the minimum and [2j + 1] the maximum over the N^2
+ * texels. Exact values (any reduction order gives them; -0 and +0 compare equal); maps holding NaN are
+ * unspecified. Two kernel launches, 36 B read per point, no host synchronisation, no float atomics. The
+ * storage (the table and 72 B per 2048 texels of scratch) is allocated on the first call (OCEAN_ERR_OOM
+ * when that fails) and freed by ocean_generator_destroy. Whole-grid generators only, every N in
+ * 16 .. 16384: a slab generator and a generator that has calculated no frame yet get OCEAN_ERR_INVALID
+ * before any device call. The bounds are fresh until the next call that rewrites the maps
+ * (ocean_generator_calculate and the other frame calls); the library tracks that on the host.
+ * Uses beside the ray march: culling boxes (heightMap.x, heightMap.w and displacementMap.x are h, Dx and
+ * Dz), and min jacobian > 0 as the sign that ocean_surface_query's fixed point converges everywhere.
+ * No reference counterpart. */
+int ocean_generator_build_bounds(ocean_generator* gen);
+/* Host copy of one cascade's 18 floats; synchronises the generator's stream. OCEAN_ERR_INVALID for a null
+ * generator or output, a cascade out of range, and bounds that were never built or are stale. */
+int ocean_generator_bounds(ocean_generator* gen, int cascade, float out[18]);
+/* The table [cascade][18] in device memory, valid until the generator is destroyed. Null, with
+ * ocean_last_error set, for a null generator and for bounds that were never built or are stale. */
+const float* ocean_generator_bounds_device(ocean_generator* gen);
+/* Where rays meet the water. rays: n_rays x 8 floats (ox, oy, oz, tmin, dx, dy, dz, tmax), out: n_rays x 16
+ * floats, both device memory. (generator, cascade) rules and stream as ocean_surface_sample; no atlas.
+ * Every generator's bounds must be built and fresh: otherwise OCEAN_ERR_INVALID, naming the index of the
+ * generator in `gens`, before any device call.
+ *
+ * Contract, per ray, in unfused fp32. V(p) is ocean_surface_sample's vertex stage at base point p, the
+ * fragment stage is its fragment stage; bounds_c is the row of pair c; min and max return NaN when either
+ * operand is NaN.
+ *   slab (read on the device from the bounds tables, no host synchronisation):
+ *     ylo = 0; yhi = 0; for each pair c in order: ylo += bounds_c[0]; yhi += bounds_c[1]
+ *     ylo -= pad; yhi += pad
+ *   clip:
+ *     t0 = tmin; t1 = tmax
+ *     if dy == 0:  if !(ylo <= oy && oy <= yhi): OUTSIDE
+ *     else: a = (ylo - oy) / dy; b = (yhi - oy) / dy; t0 = max(t0, min(a, b)); t1 = min(t1, max(a, b))
+ *     if !(t0 <= t1): OUTSIDE                      (NaN lands here)
+ *   one evaluation E(t), carrying the warm-start offset `off` (initially (0, 0)) from one to the next:
+ *     q = (ox + t*dx, oz + t*dz);  p = q + off;  V = V(p)
+ *     repeat at most `iterations` times:
+ *         r = q - V.xz;  if max(|r.x|, |r.z|) <= tolerance: stop;  p = p + r;  V = V(p)
+ *     off = p - q;  g = (oy + t*dy) - V.y
+ *   march:
+ *     inv = (slope == +inf) ? 0 : 1 / (|dy| + slope * sqrt(dx*dx + dz*dz))
+ *     ta = t0; ga = E(ta); below = (ga <= 0); steps = 0
+ *     loop: if steps == max_steps: STEP_LIMIT
+ *           tb = min(ta + max(step, |ga| * inv), t1); gb = E(tb); steps += 1
+ *           if (gb <= 0) != below: crossing found, leave the loop
+ *           ta = tb; ga = gb; if tb >= t1: EXIT
+ *   refine (crossings only), `refine` times:
+ *     tm = 0.5f * (ta + tb); gm = E(tm); if (gm <= 0) == below: (ta, ga) = (tm, gm) else (tb, gb) = (tm, gm)
+ *     then t = ta + (tb - ta) * (ga / (ga - gb))
+ *   final: one more E(t) (for EXIT and STEP_LIMIT at t = ta), then the fragment stage at its V.xz
+ *   out row 0: (ox + t*dx, oy + t*dy, oz + t*dz, t)
+ *       row 1: (nx, ny, nz, jacobian)
+ *       row 2: (p.x, V.y, p.z, max(|q.x - V.x|, |q.z - V.z|))      ocean_surface_query's slots 0, 1, 2, 7
+ *       row 3: (status, below ? 1 : 0, steps, g of the final evaluation)
+ *   status: 0 HIT, 1 OUTSIDE (rows 0-2 all zero, row 3 = (1, 0, 0, 0)), 2 EXIT, 3 STEP_LIMIT
+ * t is in units of |d| (metres when d is normalised); `step` is the coarsest advance. `slope` is the
+ * caller's bound on the slope of the surface: with it a ray far above the water advances by its clearance
+ * |g| / (|dy| + slope * |d.xz|) instead of by `step`; +inf means fixed steps. The hit is the first sign
+ * change ON THE MARCHED LATTICE: a crest thinner than the advance can be stepped over, and with a finite
+ * slope the lattice depends on the clearances. A ray that starts under water (below = 1) hits from below.
+ * The warm start makes the water height differ, within the tolerance, from composing ocean_surface_query
+ * calls: that is deliberate, it is why an evaluation costs about one vertex stage. Every loop is bounded
+ * by its count: rays with non-finite entries or a zero direction do not make the call fail, they follow
+ * the arithmetic above, whatever it gives.
+ * One kernel launch, one lane per ray; no host synchronisation, no allocation.
+ * OCEAN_ERR_INVALID, before any device call: null gens / cascades; step not finite or <= 0; max_steps
+ * outside 1..65535; refine outside 0..32; iterations outside 0..64; a negative or non-finite tolerance or
+ * pad; slope negative or NaN; negative n_rays; null rays / out with n_rays > 0. n_rays == 0 launches
+ * nothing. No reference counterpart. */
+int ocean_surface_raycast(ocean_generator* const* gens, const int* cascades, int count, const float* rays,
+                          int64_t n_rays, float step, int max_steps, int refine, int iterations, float tolerance,
+                          float slope, float pad, float* out);
+
 /* ---- Hull sets: net wave force and torque on batches of floating bodies -------------------------
  * The consumer of the three sections above: a floating body is a set of hull points, each carrying a
  * displaced volume and drag coefficients; per step the caller hands in the bodies' poses and gets one

@@ -114,6 +114,15 @@ public:
   Vision::ID GetHeightRateMap() const { return Rate(heightRateMap); }
   Vision::ID GetDisplacementRateMap() const { return Rate(displacementRateMap); }
 
+  // Extension (no reference counterpart): the minimum and maximum of the nine map channels
+  // (ocean_generator_build_bounds, oceanfft.h): culling boxes, the slab SurfaceSampler::Raycast clips its
+  // rays to, and min jacobian > 0 as the sign that SurfaceSampler::Query converges everywhere. BuildBounds
+  // enqueues the reduction on the device's stream; call it after CalculateOcean and before Raycast.
+  // GetBounds copies the 18 floats to the host (it waits for the stream): (min, max) of heightMap x, y, z,
+  // w, displacementMap x, y, z, w and the Jacobian; it throws while the bounds are not built or stale.
+  void BuildBounds();
+  void GetBounds(float out[18]) const;
+
 private:
   Vision::RenderDevice* renderDevice = nullptr;
   FFTCalculator* fftCalc = nullptr;

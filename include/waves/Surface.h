@@ -58,7 +58,22 @@ public:
   // `points` stays the same.
   Vision::ID Velocity(const std::vector<Generator*>& generators, const float* xzDevice, int64_t points);
 
+  // Where rays meet the water (ocean_surface_raycast, oceanfft.h): sensor models, picking, impacts.
+  // raysDevice: rays x 8 floats in device memory (ox, oy, oz, tmin, dx, dy, dz, tmax). Each ray is clipped
+  // to the slab of the generators' bounds (+- pad) and marched in advances of at least `step` (with a finite
+  // `slope`, the caller's bound on the surface slope, by its clearance when that is more) for at most
+  // maxSteps steps; a sign change is narrowed by `refine` bisections. Every evaluation is Query's fixed
+  // point (iterations, tolerance) started from the previous one's answer. Every generator needs
+  // Generator::BuildBounds() since its last CalculateOcean. Returns a buffer texture of 4*rays x 1 RGBA32F
+  // texels: per ray (hit x, y, z, t), (nx, ny, nz, jacobian), (base x, water height, base z, residual),
+  // (status 0 hit / 1 outside the slab / 2 left the range / 3 step limit, started below, steps, gap).
+  // Enqueued on the device's stream; its own texture, reused while `rays` stays the same.
+  Vision::ID Raycast(const std::vector<Generator*>& generators, const float* raysDevice, int64_t rays, float step,
+                     int maxSteps, int refine, int iterations, float tolerance, float slope, float pad);
+
 private:
+  Vision::ID rayHits = 0;
+  int64_t rayCount = 0;
   Vision::RenderDevice* renderDevice = nullptr;
   Vision::ID vertices = 0;
   int verticesRes = 0;

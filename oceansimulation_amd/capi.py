@@ -102,7 +102,11 @@ SIGNATURES = {
     "ocean_generator_height_rate_map": (_vp, [_vp, _i]),
     "ocean_generator_displacement_rate_map": (_vp, [_vp, _i]),
     "ocean_surface_velocity": (_i, [_vp, _vp, _i, _vp, ctypes.c_int64, _vp]),
-    "ocean_hulls_create": (_i, [ctypes.POINTER(_vp), _vp, _vp, ctypes.c_int64, _vp, _i]),
+    "ocean_generator_build_bounds": (_i, [_vp]),
+    "ocean_generator_bounds": (_i, [_vp, _i, _fp]),
+    "ocean_generator_bounds_device": (_vp, [_vp]),
+    "ocean_surface_raycast": (_i, [_vp, _vp, _i, _vp, ctypes.c_int64, _f, _i, _i, _i, _f, _f, _f, _vp]),
+    "ocean_hulls_create":(_i, [ctypes.POINTER(_vp), _vp, _vp, ctypes.c_int64, _vp, _i]),
     "ocean_hulls_destroy": (_i, [_vp]),
     "ocean_hulls_bodies": (_i, [_vp]),
     "ocean_hulls_instance_points": (ctypes.c_int64, [_vp]),

@@ -1,6 +1,7 @@
 // device/surface_sample.h — the GL_LINEAR + GL_REPEAT sampling of the generator's maps and the stages
 // built on it that more than one translation unit runs: the vertex stage (ocean_kernels.hip's surface
-// kernels, device/k_hulls.h) and the velocity of a water particle (k_surface_velocity, device/k_hulls.h).
+// kernels, device/k_hulls.h, device/k_raycast.h), the fragment stage (ocean_kernels.hip, device/k_raycast.h)
+// and the velocity of a water particle (k_surface_velocity, device/k_hulls.h).
 // Everything is unfused fp32: the oracle and the numpy references are matched bit for bit.
 #pragma once
 
@@ -88,6 +89,48 @@ __device__ __forceinline__ void surface_vertex_stage(const SurfaceParams& p, flo
     py += h;
     pz += p.c[c].scale * dz;
   }
+}
+
+// Fragment stage at the displaced position (waveShader.glsl:127-144): (nx, ny, nz, averaged Jacobian)
+template <bool ATLAS>
+__device__ __forceinline__ float4 surface_fragment_stage(const SurfaceParams& p, float px, float pz)
+{
+#pragma clang fp contract(off)
+  const int nn = p.n * p.n;
+  float d[4] = {0.0f, 0.0f, 0.0f, 0.0f}, jac = 0.0f;
+  for (int c = 0; c < p.count; c++)
+  {
+    const float u = px / p.c[c].plane, v = pz / p.c[c].plane;
+    const LinearTaps k = linear_repeat_taps(p.n, u, v);
+    float hx, dxx, hz, dzz;
+    if constexpr (ATLAS)
+    {
+      const float4 b = linear_texel(p.atlas + (size_t)(2 * c + 1) * nn, k);
+      hx = b.x;
+      hz = b.y;
+      dxx = b.z;
+      dzz = b.w;
+    }
+    else
+    {
+      const float* hm = reinterpret_cast<const float*>(p.c[c].height);
+      const float* dm = reinterpret_cast<const float*>(p.c[c].disp);
+      hx = linear_channel<4>(hm, k, 1);
+      dxx = linear_channel<4>(dm, k, 1);
+      hz = linear_channel<4>(hm, k, 2);
+      dzz = linear_channel<4>(dm, k, 2);
+    }
+    jac += linear_channel<1>(p.c[c].jac, k, 0) / (float)p.count;
+    const float f = p.c[c].scale;
+    d[0] += hx;        // dh/dx
+    d[1] += dxx * f;   // dDx/dx
+    d[2] += hz;        // dh/dz
+    d[3] += dzz * f;   // dDz/dz
+  }
+  const float sx = d[0] / (1.0f + d[1]), sz = d[2] / (1.0f + d[3]);
+  const float nx = -sx, ny = 1.0f, nz = -sz;
+  const float len = sqrtf(nx * nx + ny * ny + nz * nz);
+  return make_float4(nx / len, ny / len, nz / len, jac);
 }
 
 // ocean_surface_velocity's loop (include/oceanfft.h): (px, pz) enters as the base point, py and u as 0;

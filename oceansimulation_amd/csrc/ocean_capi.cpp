@@ -174,6 +174,10 @@ struct ocean_generator
   // displacement-rate][N * N], allocated on first use; fresh until the next column pass
   float4* rates = nullptr;
   bool rates_fresh = false;
+  // the bounds of the maps (ocean_generator_build_bounds): the table [cascade][18], then stage 1's partial
+  // rows (bounds_floats), allocated on first use; fresh until the next call that rewrites the maps
+  float* bounds = nullptr;
+  bool bounds_fresh = false;
   bool profiling = false;
   std::vector<EventPair> pending;
   std::vector<hipEvent_t> pool;
@@ -728,7 +732,7 @@ int ocean_generator_destroy(ocean_generator* g)
       (void)hipFree(p);
   for (void* p : {(void*)g->gab, (void*)g->gcd, (void*)g->ge, (void*)g->spec, (void*)g->hs, (void*)g->h0row, g->seedc,
                   (void*)g->rm_ab, (void*)g->rm_de, (void*)g->rm_c, (void*)g->parts, (void*)g->xbuf, (void*)g->mips,
-                  (void*)g->rates})
+                  (void*)g->rates, (void*)g->bounds})
     if (p)
       (void)hipFree(p);
   delete g;
@@ -1054,6 +1058,7 @@ static int generator_rows(ocean_generator* g, const float4* in, const FoamParams
 {
   ocean_fft* f = g->fft;
   g->mips_fresh = false;  // every frame path's maps are written here
+  g->bounds_fresh = false;
   const int rcus = row_cus > 0 && row_cus < f->cus ? row_cus : f->cus;
   const FoamParams foam = frame_foam ? *frame_foam : current_foam(g);
   if (uses_gen4(g))
@@ -2565,6 +2570,121 @@ int ocean_surface_velocity(ocean_generator* const* gens, const int* cascades, in
   HIP_TRY(launch_surface_velocity(p, r, reinterpret_cast<const float2*>(xz), points, reinterpret_cast<float4*>(out),
                                   fft->stream, fft->cus),
           "ocean_surface_velocity");
+  return OCEAN_OK;
+}
+
+// ---- bounds of the maps and ray casting against the displaced surface ----
+int ocean_generator_build_bounds(ocean_generator* g)
+{
+  if (!g)
+    return fail(OCEAN_ERR_INVALID, "ocean_generator_build_bounds: null generator");
+  if (g->slab || g->ranks != 1)
+    return fail(OCEAN_ERR_INVALID, "ocean_generator_build_bounds: slab generators hold row slabs, not whole maps");
+  if (g->frame.cascades != g->cascades)
+    return fail(OCEAN_ERR_INVALID, "ocean_generator_build_bounds: no frame calculated yet (ocean_generator_calculate)");
+  ocean_fft* f = g->fft;
+  if (!g->bounds)
+  {
+    const hipError_t e = hipMalloc(&g->bounds, bounds_floats(f->n, g->cascades) * sizeof(float));
+    if (e != hipSuccess)
+    {
+      g->bounds = nullptr;
+      return fail(e == hipErrorOutOfMemory ? OCEAN_ERR_OOM : OCEAN_ERR_HIP,
+                  std::string("ocean_generator_build_bounds: ") + hipGetErrorString(e));
+    }
+  }
+  g->bounds_fresh = false;
+  HIP_TRY(launch_build_bounds(f->n, g->cascades, g->maps, g->jac, g->bounds, f->stream, f->cus),
+          "ocean_generator_build_bounds");
+  g->bounds_fresh = true;
+  return OCEAN_OK;
+}
+
+// The table of a generator whose bounds are built and not older than its maps, else null with a message
+static const float* generator_bounds(ocean_generator* g, const char* who)
+{
+  if (!g)
+  {
+    fail(OCEAN_ERR_INVALID, std::string(who) + ": null generator");
+    return nullptr;
+  }
+  if (!g->bounds || !g->bounds_fresh)
+  {
+    fail(OCEAN_ERR_INVALID, std::string(who) + (g->bounds ? ": the bounds are stale (the maps were rewritten since"
+                                                           : ": the bounds were never built (call") +
+                                " ocean_generator_build_bounds)");
+    return nullptr;
+  }
+  return g->bounds;
+}
+
+const float* ocean_generator_bounds_device(ocean_generator* g)
+{
+  return generator_bounds(g, "ocean_generator_bounds_device");
+}
+
+int ocean_generator_bounds(ocean_generator* g, int cascade, float out[18])
+{
+  const float* table = generator_bounds(g, "ocean_generator_bounds");
+  if (!table)
+    return OCEAN_ERR_INVALID;
+  if (cascade < 0 || cascade >= g->cascades || !out)
+    return fail(OCEAN_ERR_INVALID, "ocean_generator_bounds: cascade out of range or null output");
+  HIP_TRY(hipMemcpyAsync(out, table + (size_t)cascade * 18, 18 * sizeof(float), hipMemcpyDeviceToHost, g->fft->stream),
+          "ocean_generator_bounds");
+  HIP_TRY(hipStreamSynchronize(g->fft->stream), "ocean_generator_bounds");
+  return OCEAN_OK;
+}
+
+int ocean_surface_raycast(ocean_generator* const* gens, const int* cascades, int count, const float* rays,
+                          int64_t n_rays, float step, int max_steps, int refine, int iterations, float tolerance,
+                          float slope, float pad, float* out)
+{
+  // the scalar rules first: they need no generator
+  if (!gens || !cascades)
+    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: null gens / cascades");
+  if (!std::isfinite(step) || !(step > 0.0f))
+    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: step must be finite and > 0");
+  if (max_steps < 1 || max_steps > 65535)
+    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: max_steps outside 1..65535");
+  if (refine < 0 || refine > 32)
+    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: refine outside 0..32");
+  if (iterations < 0 || iterations > 64)
+    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: iterations outside 0..64");
+  if (!(tolerance >= 0.0f) || !std::isfinite(tolerance))
+    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: tolerance must be finite and >= 0");
+  if (!(pad >= 0.0f) || !std::isfinite(pad))
+    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: pad must be finite and >= 0");
+  if (!(slope >= 0.0f))
+    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: slope must be >= 0 (+inf: fixed steps)");
+  if (n_rays < 0 || (n_rays > 0 && (!rays || !out)))
+    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: null rays/output or negative count");
+  SurfaceParams p;
+  ocean_fft* fft;
+  const int rc = surface_params(gens, cascades, count, p, fft, "ocean_surface_raycast");
+  if (rc != OCEAN_OK)
+    return rc;
+  RaycastParams r{};
+  for (int i = 0; i < count; i++)
+  {
+    ocean_generator* g = gens[i];
+    if (!g->bounds || !g->bounds_fresh)
+      return fail(OCEAN_ERR_INVALID, std::string("ocean_surface_raycast: generator ") + std::to_string(i) +
+                                         (g->bounds ? " has stale bounds (its maps were rewritten since"
+                                                    : " has no bounds (call") +
+                                         " ocean_generator_build_bounds)");
+    r.bounds[i] = g->bounds + (size_t)cascades[i] * 18;
+  }
+  r.step = step;
+  r.max_steps = max_steps;
+  r.refine = refine;
+  r.iterations = iterations;
+  r.tolerance = tolerance;
+  r.slope = slope;
+  r.pad = pad;
+  HIP_TRY(launch_surface_raycast(p, r, reinterpret_cast<const float4*>(rays), n_rays, reinterpret_cast<float4*>(out),
+                                 fft->stream, fft->cus),
+          "ocean_surface_raycast");
   return OCEAN_OK;
 }
 

@@ -297,6 +297,24 @@ struct SurfaceRates
 };
 hipError_t launch_surface_velocity(const SurfaceParams& p, const SurfaceRates& r, const float2* xz, int64_t count,
                                    float4* out, hipStream_t stream, int cus);
+// The bounds of a whole-grid generator's maps (device/k_bounds.h): per cascade 18 floats, (min, max) of
+// heightMap x, y, z, w, displacementMap x, y, z, w and the Jacobian, at the start of `bounds`
+// (bounds_floats(n, cascades) floats: the table, then stage 1's partial rows). Two launches.
+int bounds_tiles(int n);  // stage-1 items per cascade
+size_t bounds_floats(int n, int cascades);
+hipError_t launch_build_bounds(int n, int cascades, const float4* maps, const float* jac, float* bounds,
+                               hipStream_t stream, int cus);
+// ocean_surface_raycast (include/oceanfft.h, device/k_raycast.h): the cascades' bounds rows beside
+// SurfaceParams' maps (same order) and the call's parameters; rays [n][2], out [n][4].
+struct RaycastParams
+{
+  const float* bounds[kMaxSurfaceCascades];
+  float step;
+  int max_steps, refine, iterations;
+  float tolerance, slope, pad;
+};
+hipError_t launch_surface_raycast(const SurfaceParams& p, const RaycastParams& rc, const float4* rays, int64_t n_rays,
+                                  float4* out, hipStream_t stream, int cus);
 // ocean_hulls (include/oceanfft.h, device/k_hulls.h): the tables ocean_hulls_create builds and one call
 constexpr int kHullTilePoints = 64;  // points per work item: the lanes of one wave
 // One tile of one body: points [first, first + count) of the hull set's points, point_out rows from

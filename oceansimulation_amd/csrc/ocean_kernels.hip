@@ -263,47 +263,7 @@ __global__ __launch_bounds__(256) void k_surface_atlas(SurfaceParams p)
   }
 }
 
-// Fragment stage at the displaced position (waveShader.glsl:127-144): (nx, ny, nz, averaged Jacobian)
-template <bool ATLAS>
-__device__ __forceinline__ float4 surface_fragment_stage(const SurfaceParams& p, float px, float pz)
-{
-#pragma clang fp contract(off)
-  const int nn = p.n * p.n;
-  float d[4] = {0.0f, 0.0f, 0.0f, 0.0f}, jac = 0.0f;
-  for (int c = 0; c < p.count; c++)
-  {
-    const float u = px / p.c[c].plane, v = pz / p.c[c].plane;
-    const LinearTaps k = linear_repeat_taps(p.n, u, v);
-    float hx, dxx, hz, dzz;
-    if constexpr (ATLAS)
-    {
-      const float4 b = linear_texel(p.atlas + (size_t)(2 * c + 1) * nn, k);
-      hx = b.x;
-      hz = b.y;
-      dxx = b.z;
-      dzz = b.w;
-    }
-    else
-    {
-      const float* hm = reinterpret_cast<const float*>(p.c[c].height);
-      const float* dm = reinterpret_cast<const float*>(p.c[c].disp);
-      hx = linear_channel<4>(hm, k, 1);
-      dxx = linear_channel<4>(dm, k, 1);
-      hz = linear_channel<4>(hm, k, 2);
-      dzz = linear_channel<4>(dm, k, 2);
-    }
-    jac += linear_channel<1>(p.c[c].jac, k, 0) / (float)p.count;
-    const float f = p.c[c].scale;
-    d[0] += hx;        // dh/dx
-    d[1] += dxx * f;   // dDx/dx
-    d[2] += hz;        // dh/dz
-    d[3] += dzz * f;   // dDz/dz
-  }
-  const float sx = d[0] / (1.0f + d[1]), sz = d[2] / (1.0f + d[3]);
-  const float nx = -sx, ny = 1.0f, nz = -sz;
-  const float len = sqrtf(nx * nx + ny * ny + nz * nz);
-  return make_float4(nx / len, ny / len, nz / len, jac);
-}
+// The fragment stage at the displaced position is there too (shared with device/k_raycast.h).
 
 template <bool ATLAS>
 __global__ __launch_bounds__(256) void k_surface(SurfaceParams p, SurfacePlane plane, const float2* __restrict__ xz,

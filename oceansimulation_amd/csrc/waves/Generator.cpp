@@ -100,6 +100,18 @@ Vision::ID Generator::Rate(Vision::ID map) const
   return map;
 }
 
+void Generator::BuildBounds()
+{
+  if (ocean_generator_build_bounds(gen) != OCEAN_OK)
+    throw std::runtime_error(std::string("Waves::Generator::BuildBounds: ") + ocean_last_error());
+}
+
+void Generator::GetBounds(float out[18]) const
+{
+  if (ocean_generator_bounds(gen, 0, out) != OCEAN_OK)
+    throw std::runtime_error(std::string("Waves::Generator::GetBounds: ") + ocean_last_error());
+}
+
 void Generator::LoadShaders(bool) {}
 
 }  // namespace Waves

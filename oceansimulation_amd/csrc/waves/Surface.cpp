@@ -19,6 +19,8 @@ SurfaceSampler::~SurfaceSampler()
     renderDevice->DestroyTexture2D(verticesLod);
   if (velocities)
     renderDevice->DestroyTexture2D(velocities);
+  if (rayHits)
+    renderDevice->DestroyTexture2D(rayHits);
 }
 
 Vision::ID SurfaceSampler::Sample(const std::vector<Generator*>& generators, const float camera[5], int res)
@@ -135,6 +137,39 @@ Vision::ID SurfaceSampler::Velocity(const std::vector<Generator*>& generators, c
   if (rc != OCEAN_OK)
     throw std::runtime_error(std::string("SurfaceSampler::Velocity: ") + ocean_last_error());
   return velocities;
+}
+
+Vision::ID SurfaceSampler::Raycast(const std::vector<Generator*>& generators, const float* raysDevice, int64_t rays,
+                                   float step, int maxSteps, int refine, int iterations, float tolerance, float slope,
+                                   float pad)
+{
+  if (rays < 1)
+    throw std::runtime_error("SurfaceSampler::Raycast: need at least one ray");
+  if (!rayHits || rayCount != rays)
+  {
+    if (rayHits)
+      renderDevice->DestroyTexture2D(rayHits);
+    rayHits = 0;
+    Vision::Texture2DDesc desc;
+    desc.Width = 4 * (std::size_t)rays;
+    desc.Height = 1;
+    desc.PixelType = Vision::PixelType::RGBA32Float;
+    rayHits = renderDevice->CreateTexture2D(desc);
+    rayCount = rays;
+  }
+  std::vector<ocean_generator*> gens;
+  std::vector<int> cascades;
+  for (auto* g : generators)
+  {
+    gens.push_back(g->GetHandle());
+    cascades.push_back(0);
+  }
+  const int rc = ocean_surface_raycast(gens.data(), cascades.data(), (int)gens.size(), raysDevice, rays, step, maxSteps,
+                                       refine, iterations, tolerance, slope, pad,
+                                       static_cast<float*>(renderDevice->GetTexturePointer(rayHits)));
+  if (rc != OCEAN_OK)
+    throw std::runtime_error(std::string("SurfaceSampler::Raycast: ") + ocean_last_error());
+  return rayHits;
 }
 
 HullSet::HullSet(Vision::RenderDevice* device, FFTCalculator* fft, const float* points, int64_t nPoints,

@@ -14,6 +14,9 @@ from .capi import check, lib
 from .hip import DeviceBuffer
 
 FLOATS_PER_VERTEX = 8  # x, y, z, jacobian, nx, ny, nz, 0 (query: base x, height, base z, ..., residual)
+FLOATS_PER_RAY = 8     # ox, oy, oz, tmin, dx, dy, dz, tmax
+FLOATS_PER_HIT = 16    # ocean_surface_raycast's four rows
+RAY_HIT, RAY_OUTSIDE, RAY_EXIT, RAY_STEP_LIMIT = 0, 1, 2, 3
 
 
 class SurfaceSampler:
@@ -101,6 +104,30 @@ class SurfaceSampler:
         self.velocity(src.ptr if pts else 0, pts, out.ptr if pts else 0)
         self.fft.synchronize()
         return out.to_host((pts, FLOATS_PER_VERTEX)) if pts else np.zeros((0, FLOATS_PER_VERTEX), np.float32)
+
+    # ---- ray casting against the displaced surface (Generator.BuildBounds first) ----
+    def raycast(self, rays_ptr: int, n_rays: int, out_ptr: int, step: float = 0.25, max_steps: int = 256,
+                refine: int = 10, iterations: int = 4, tolerance: float = 1e-3, slope: float = float("inf"),
+                pad: float = 0.0) -> None:
+        """Enqueue ocean_surface_raycast: device rays (n, 8) -> device rows (n, 16)."""
+        check(lib().ocean_surface_raycast(self._gens, self._cas, len(self.pairs), ctypes.c_void_p(rays_ptr),
+                                          ctypes.c_int64(n_rays), ctypes.c_float(step), int(max_steps), int(refine),
+                                          int(iterations), ctypes.c_float(tolerance), ctypes.c_float(slope),
+                                          ctypes.c_float(pad), ctypes.c_void_p(out_ptr)), "ocean_surface_raycast")
+
+    def raycast_host(self, rays: np.ndarray, step: float = 0.25, max_steps: int = 256, refine: int = 10,
+                     iterations: int = 4, tolerance: float = 1e-3, slope: float = float("inf"),
+                     pad: float = 0.0) -> np.ndarray:
+        """Per ray (ox, oy, oz, tmin, dx, dy, dz, tmax): 16 floats, (hit point, t), (normal, jacobian),
+        (base x, water height, base z, residual), (status, below, steps, gap); include/oceanfft.h."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, FLOATS_PER_RAY)
+        n = rays.shape[0]
+        src = DeviceBuffer.from_array(rays) if n else None
+        out = DeviceBuffer(n * FLOATS_PER_HIT * 4) if n else None
+        self.raycast(src.ptr if n else 0, n, out.ptr if n else 0, step, max_steps, refine, iterations, tolerance,
+                     slope, pad)
+        self.fft.synchronize()
+        return out.to_host((n, FLOATS_PER_HIT)) if n else np.zeros((0, FLOATS_PER_HIT), np.float32)
 
     def plane_host(self, camera, res: int) -> np.ndarray:
         pts = (res + 1) * (res + 1)

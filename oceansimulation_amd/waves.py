@@ -223,6 +223,29 @@ class Generator:
         """d/dt (Dz, dDx/dx, dDz/dz, dDx/dz)"""
         return self._rate_host("ocean_generator_displacement_rate_map", cascade)
 
+    # ---- bounds of the maps (ocean_generator_build_bounds, include/oceanfft.h) ----
+    def BuildBounds(self) -> None:
+        """Enqueue the (min, max) of the nine map channels of every cascade from the current maps."""
+        check(lib().ocean_generator_build_bounds(self._h), "ocean_generator_build_bounds")
+
+    build_bounds = BuildBounds
+
+    def GetBounds(self, cascade: int = 0) -> np.ndarray:
+        """(9, 2) float32: (min, max) of heightMap x, y, z, w, displacementMap x, y, z, w and the Jacobian."""
+        out = np.zeros(18, np.float32)
+        check(lib().ocean_generator_bounds(self._h, int(cascade), out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))),
+              "ocean_generator_bounds")
+        return out.reshape(9, 2)
+
+    get_bounds = GetBounds
+
+    def bounds_device(self) -> int:
+        """The table [cascade][18] in device memory (built and fresh, else OceanError)."""
+        ptr = lib().ocean_generator_bounds_device(self._h)
+        if not ptr:
+            raise capi.OceanError(capi.OCEAN_ERR_INVALID, "ocean_generator_bounds_device")
+        return int(ptr)
+
     # ---- instrumentation ----
     def set_profiling(self, enable: bool) -> None:
         check(lib().ocean_generator_set_profiling(self._h, 1 if enable else 0), "ocean_generator_set_profiling")
