@@ -24,17 +24,28 @@ all: $(LIB) $(WAVES) $(ORACLE) $(CPPTEST) $(APP)
 DEVICE_H := $(wildcard $(CSRC)/device/*.h) $(CSRC)/ocean_internal.h $(CSRC)/launch_common.h
 # one translation unit per frame path, compiled in parallel
 KERNEL_TUS := ocean_kernels launch_half launch_slab launch_fft launch_mips launch_rates launch_hulls launch_bounds \
-              launch_raycast
+              launch_raycast launch_surface
 KERNEL_OBJS := $(KERNEL_TUS:%=$(CSRC)/build/%.o)
+# hipcc gives every HIP translation unit an exported id symbol (__hip_cuid_<hash>; only relocatable device
+# code, which this build does not use, refers to it). The units split off from ocean_kernels and ocean_capi
+# keep theirs local, so the library's dynamic symbol table is what it was before the split.
+OBJCOPY ?= /opt/rocm/lib/llvm/bin/llvm-objcopy
+LOCAL_CUID := launch_surface ocean_capi_surface
+local_cuid = $(if $(filter $(basename $(notdir $@)),$(LOCAL_CUID)),$(OBJCOPY) -w -L '__hip_cuid_*' $@)
 $(CSRC)/build/%.o: $(CSRC)/%.hip $(DEVICE_H)
 	@mkdir -p $(CSRC)/build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+	$(local_cuid)
 
-$(CSRC)/build/ocean_capi.o: $(CSRC)/ocean_capi.cpp $(CSRC)/ocean_internal.h $(CSRC)/device/mip_index.h include/oceanfft.h
+# the C ABI: the plans, generators and exchanges, and the surface consumers' entry points
+CAPI_OBJS := $(CSRC)/build/ocean_capi.o $(CSRC)/build/ocean_capi_surface.o
+$(CAPI_OBJS): $(CSRC)/build/%.o: $(CSRC)/%.cpp $(CSRC)/ocean_capi_internal.h $(CSRC)/ocean_internal.h \
+              $(CSRC)/device/mip_index.h include/oceanfft.h
 	@mkdir -p $(CSRC)/build
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
+	$(local_cuid)
 
-$(LIB): $(KERNEL_OBJS) $(CSRC)/build/ocean_capi.o
+$(LIB): $(KERNEL_OBJS) $(CAPI_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ -Wl,-soname,liboceanfft.so -L/opt/rocm/lib -lrccl
 
 # C++ drop-in layer (Waves::FFTCalculator / Waves::Generator / Vision::RenderDevice shim) over the C ABI.

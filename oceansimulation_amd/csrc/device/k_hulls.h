@@ -132,24 +132,11 @@ __global__ __launch_bounds__(kHullTile) void k_hulls_loads(SurfaceParams p, Surf
       const float dy = (P[3] * l0.x + P[4] * l0.y) + P[5] * l0.z;
       const float dz = (P[6] * l0.x + P[7] * l0.y) + P[8] * l0.z;
       const float xx = P[9] + dx, xy = P[10] + dy, xz = P[11] + dz;
-      // ocean_surface_query at q = (xx, xz), vertex stage only (k_surface_query's loop)
+      // ocean_surface_query at q = (xx, xz), vertex stage only
       float bx = xx, bz = xz;
-      float vx = bx, vy = 0.0f, vz = bz;
-      surface_vertex_stage<ATLAS>(p, vx, vy, vz);
-      for (int it = 0; it < h.iterations; it++)
-      {
-        const float rx = xx - vx, rz = xz - vz;
-        if (fabsf(rx) <= h.tolerance && fabsf(rz) <= h.tolerance)
-          break;
-        bx += rx;
-        bz += rz;
-        vx = bx;
-        vy = 0.0f;
-        vz = bz;
-        surface_vertex_stage<ATLAS>(p, vx, vy, vz);
-      }
-      const float ex = fabsf(xx - vx), ez = fabsf(xz - vz);
-      const float res = (ex >= ez || ex != ex) ? ex : ez;
+      float vx, vy, vz;
+      surface_base_point<ATLAS>(p, xx, xz, h.iterations, h.tolerance, bx, bz, vx, vy, vz);
+      const float res = surface_residual(xx, xz, vx, vz);
       const float t = (vy - xy) / (l1.x + l1.x) + 0.5f;
       const float s = t > 0.0f ? (t < 1.0f ? t : 1.0f) : 0.0f;  // NaN -> 0
       float ux = 0.0f, uy = 0.0f, uz = 0.0f;

@@ -84,22 +84,7 @@ __global__ __launch_bounds__(kRaycastThreads) void k_surface_raycast(SurfacePara
       qz = oz + te * dz;
       bx = qx + offx;
       bz = qz + offz;
-      vx = bx;
-      vy = 0.0f;
-      vz = bz;
-      surface_vertex_stage<false>(p, vx, vy, vz);
-      for (int it = 0; it < rc.iterations; it++)
-      {
-        const float rx = qx - vx, rz = qz - vz;
-        if (fabsf(rx) <= rc.tolerance && fabsf(rz) <= rc.tolerance)
-          break;
-        bx += rx;
-        bz += rz;
-        vx = bx;
-        vy = 0.0f;
-        vz = bz;
-        surface_vertex_stage<false>(p, vx, vy, vz);
-      }
+      surface_base_point<false>(p, qx, qz, rc.iterations, rc.tolerance, bx, bz, vx, vy, vz);
       offx = bx - qx;
       offz = bz - qz;
       g = (oy + te * dy) - vy;
@@ -171,10 +156,9 @@ __global__ __launch_bounds__(kRaycastThreads) void k_surface_raycast(SurfacePara
       }
     }
     const float4 f = surface_fragment_stage<false>(p, vx, vz);
-    const float ex = fabsf(qx - vx), ez = fabsf(qz - vz);
-    out[4 * idx] = make_float4(ox + te * dx, oy + te * dy, oz + te * dz, te);
+    out[4 * idx]= make_float4(ox + te * dx, oy + te * dy, oz + te * dz, te);
     out[4 * idx + 1] = make_float4(f.x, f.y, f.z, f.w);
-    out[4 * idx + 2] = make_float4(bx, vy, bz, (ex >= ez || ex != ex) ? ex : ez);
+    out[4 * idx + 2] = make_float4(bx, vy, bz, surface_residual(qx, qz, vx, vz));
     out[4 * idx + 3] = make_float4((float)status, below ? 1.0f : 0.0f, (float)steps, g);
   }
 }

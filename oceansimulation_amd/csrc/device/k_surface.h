@@ -1,0 +1,249 @@
+// device/k_surface.h — the point kernels of the surface consumer: the atlas repack,
+// ocean_surface_sample[_plane] (k_surface), ocean_surface_query, ocean_surface_velocity and the
+// footprint-aware ocean_surface_sample[_plane]_lod (include/oceanfft.h). One thread per point, item loops
+// on the grid of launch_surface.hip's launch_points.
+//
+// resources/waveShader.glsl evaluated per mesh vertex on the generator's maps. Vertex stage (:101-110):
+// each cascade samples heightMap/displacementMap at pos.xz / planeSize, the position the earlier cascades
+// already displaced, and adds (scale * Dx, h, scale * Dz). Fragment stage at the displaced position
+// (:127-144): summed slopes -> normal, averaged Jacobian. Sampling is GL_LINEAR + GL_REPEAT
+// (src/Generator.cpp:116-119) in fp32 with the specification's weights, unfused and with correctly
+// rounded division / sqrt, so the oracle restatement (oracle_surface_vertex) is matched bit for bit.
+// Memory: the maps of a scene (3 x 256^2 x 36 B) live in L2; per vertex 32 B are written.
+//
+// The taps, the filtered channel / texel, the two stages, the query's fixed point and the plane warp are
+// in device/surface_sample.h (shared with device/k_hulls.h and device/k_raycast.h).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "device/mip_index.h"
+#include "device/surface_sample.h"
+#include "ocean_internal.h"
+
+namespace oceanfft
+{
+
+// the surface atlas of the cascades' maps (SurfaceParams::atlas)
+__global__ __launch_bounds__(256) void k_surface_atlas(SurfaceParams p)
+{
+  const int nn = p.n * p.n;
+  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < p.count * nn; idx += gridDim.x * blockDim.x)
+  {
+    const int c = idx / nn, t = idx - c * nn;
+    const float4 h = p.c[c].height[t], d = p.c[c].disp[t];
+    p.atlas[(size_t)(2 * c) * nn + t] = make_float4(h.x, h.w, d.x, 0.0f);
+    p.atlas[(size_t)(2 * c + 1) * nn + t] = make_float4(h.y, h.z, d.y, d.z);
+  }
+}
+
+template <bool ATLAS>
+__global__ __launch_bounds__(256) void k_surface(SurfaceParams p, SurfacePlane plane, const float2* __restrict__ xz,
+                                                 int64_t count, float4* __restrict__ out)
+{
+#pragma clang fp contract(off)
+  const SurfacePlaneTurn turn = surface_plane_turn(plane);
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < count;
+       idx += (int64_t)gridDim.x * blockDim.x)
+  {
+    float px, pz;
+    if (plane.res > 0)
+    {
+      float k;
+      surface_plane_point(plane, turn, idx, px, pz, k);
+    }
+    else
+    {
+      const float2 q = xz[idx];
+      px = q.x;
+      pz = q.y;
+    }
+    float py = 0.0f;
+    surface_vertex_stage<ATLAS>(p, px, py, pz);
+    const float4 f = surface_fragment_stage<ATLAS>(p, px, pz);
+    out[2 * idx] = make_float4(px, py, pz, f.w);
+    out[2 * idx + 1] = make_float4(f.x, f.y, f.z, 0.0f);
+  }
+}
+
+// The inverse direction (ocean_surface_query, include/oceanfft.h): surface_base_point from a cold start
+// (one 16-B load per tap and cascade from the atlas, three dwords from the maps); the fragment stage runs
+// once, at the last V(p). A NaN residual keeps iterating and reaches slot 7.
+template <bool ATLAS>
+__global__ __launch_bounds__(256) void k_surface_query(SurfaceParams p, const float2* __restrict__ xz, int64_t count,
+                                                       int iterations, float tolerance, float4* __restrict__ out)
+{
+#pragma clang fp contract(off)
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < count;
+       idx += (int64_t)gridDim.x * blockDim.x)
+  {
+    const float2 q = xz[idx];
+    float bx = q.x, bz = q.y;  // the base point p
+    float vx, vy, vz;
+    surface_base_point<ATLAS>(p, q.x, q.y, iterations, tolerance, bx, bz, vx, vy, vz);
+    const float4 f = surface_fragment_stage<ATLAS>(p, vx, vz);
+    out[2 * idx] = make_float4(bx, vy, bz, f.w);
+    out[2 * idx + 1] = make_float4(f.x, f.y, f.z, surface_residual(q.x, q.y, vx, vz));
+  }
+}
+
+// The velocity of the water particle whose rest position is the base point (ocean_surface_velocity,
+// include/oceanfft.h): d/dt of the vertex stage V(p). Cascade c samples at the position the earlier
+// cascades displaced, which itself moves with the velocity u accumulated so far, so its share is the
+// rate maps' sample plus grad(field) . u, the gradients being map channels (dDx/dz = dDz/dx). The
+// position advances exactly as in surface_vertex_stage (same taps, weights and sums), so slots 0-2 are
+// ocean_surface_sample's bits. Per cascade and tap two 16-B loads (the maps) and three dwords (the rates).
+__global__ __launch_bounds__(256) void k_surface_velocity(SurfaceParams p, SurfaceRates r, const float2* __restrict__ xz,
+                                                          int64_t count, float4* __restrict__ out)
+{
+#pragma clang fp contract(off)
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < count;
+       idx += (int64_t)gridDim.x * blockDim.x)
+  {
+    const float2 q = xz[idx];
+    float px = q.x, py = 0.0f, pz = q.y;
+    float ux = 0.0f, uy = 0.0f, uz = 0.0f;
+    surface_particle_velocity(p, r, px, py, pz, ux, uy, uz);
+    out[2 * idx] = make_float4(px, py, pz, 0.0f);
+    out[2 * idx + 1] = make_float4(ux, uy, uz, 0.0f);
+  }
+}
+
+// Footprint-aware sampling (ocean_surface_sample_lod, include/oceanfft.h): a sample whose neighbours sit
+// `footprint` metres away covers r = footprint * N / planeSize texels of cascade c's level 0, so it reads
+// level l = floor(log2 r) and level l + 1 of the mip pyramid (device/k_mips.h) and blends them by
+// f = r / 2^l - 1 in [0, 1): linear in the footprint, continuous across levels. l is r's exponent field
+// and f is exact (a scaling by a power of two and a subtraction in [1, 2)), so no log2f is involved.
+struct SurfaceLod
+{
+  int l;
+  float f;
+};
+
+__device__ __forceinline__ SurfaceLod surface_lod(float footprint, int n, int top, float plane)
+{
+#pragma clang fp contract(off)
+  const float r = (footprint * (float)n) / plane;
+  if (!(r >= 1.0f))  // also NaN
+    return SurfaceLod{0, 0.0f};
+  if (r >= (float)(1 << top))  // also +inf
+    return SurfaceLod{top, 0.0f};
+  const int l = (int)(__float_as_uint(r) >> 23) - 127;
+  return SurfaceLod{l, r * __uint_as_float((uint32_t)(127 - l) << 23) - 1.0f};
+}
+
+// Level l of a map whose chain (levels >= 1) is `mip`, CH floats per texel
+template <int CH>
+__device__ __forceinline__ const float* surface_level(const void* map, const void* mip, int n, int l)
+{
+  return l == 0 ? static_cast<const float*>(map) : static_cast<const float*>(mip) + mip_level_offset(n, l) * CH;
+}
+
+__device__ __forceinline__ float lod_blend(float a, float b, float f)
+{
+#pragma clang fp contract(off)
+  return a + f * (b - a);
+}
+
+// surface_vertex_stage with cascade c's (l, f): A = level l, B = level l + 1 (read only when f != 0;
+// l == top has f == 0)
+__device__ __forceinline__ void surface_vertex_stage_lod(const SurfaceParams& p, int top, float footprint, float& px,
+                                                         float& py, float& pz)
+{
+#pragma clang fp contract(off)
+  for (int c = 0; c < p.count; c++)
+  {
+    const SurfaceLod lod = surface_lod(footprint, p.n, top, p.c[c].plane);
+    const float u = px / p.c[c].plane, v = pz / p.c[c].plane;
+    const LinearTaps k = linear_repeat_taps(p.n >> lod.l, u, v);
+    const float* hm = surface_level<4>(p.c[c].height, p.c[c].height_mip, p.n, lod.l);
+    const float* dm = surface_level<4>(p.c[c].disp, p.c[c].disp_mip, p.n, lod.l);
+    float h = linear_channel<4>(hm, k, 0), dx = linear_channel<4>(hm, k, 3), dz = linear_channel<4>(dm, k, 0);
+    if (lod.f != 0.0f)
+    {
+      const LinearTaps kb = linear_repeat_taps(p.n >> (lod.l + 1), u, v);
+      const float* hb = surface_level<4>(p.c[c].height, p.c[c].height_mip, p.n, lod.l + 1);
+      const float* db = surface_level<4>(p.c[c].disp, p.c[c].disp_mip, p.n, lod.l + 1);
+      h = lod_blend(h, linear_channel<4>(hb, kb, 0), lod.f);
+      dx = lod_blend(dx, linear_channel<4>(hb, kb, 3), lod.f);
+      dz = lod_blend(dz, linear_channel<4>(db, kb, 0), lod.f);
+    }
+    px += p.c[c].scale * dx;
+    py += h;
+    pz += p.c[c].scale * dz;
+  }
+}
+
+// surface_fragment_stage with the same (l, f) per cascade, at the displaced position
+__device__ __forceinline__ float4 surface_fragment_stage_lod(const SurfaceParams& p, int top, float footprint, float px,
+                                                             float pz)
+{
+#pragma clang fp contract(off)
+  float d[4] = {0.0f, 0.0f, 0.0f, 0.0f}, jac = 0.0f;
+  for (int c = 0; c < p.count; c++)
+  {
+    const SurfaceLod lod = surface_lod(footprint, p.n, top, p.c[c].plane);
+    const float u = px / p.c[c].plane, v = pz / p.c[c].plane;
+    const LinearTaps k = linear_repeat_taps(p.n >> lod.l, u, v);
+    const float* hm = surface_level<4>(p.c[c].height, p.c[c].height_mip, p.n, lod.l);
+    const float* dm = surface_level<4>(p.c[c].disp, p.c[c].disp_mip, p.n, lod.l);
+    const float* jm = surface_level<1>(p.c[c].jac, p.c[c].jac_mip, p.n, lod.l);
+    float hx = linear_channel<4>(hm, k, 1), dxx = linear_channel<4>(dm, k, 1), hz = linear_channel<4>(hm, k, 2),
+          dzz = linear_channel<4>(dm, k, 2), j = linear_channel<1>(jm, k, 0);
+    if (lod.f != 0.0f)
+    {
+      const LinearTaps kb = linear_repeat_taps(p.n >> (lod.l + 1), u, v);
+      const float* hb = surface_level<4>(p.c[c].height, p.c[c].height_mip, p.n, lod.l + 1);
+      const float* db = surface_level<4>(p.c[c].disp, p.c[c].disp_mip, p.n, lod.l + 1);
+      const float* jb = surface_level<1>(p.c[c].jac, p.c[c].jac_mip, p.n, lod.l + 1);
+      hx = lod_blend(hx, linear_channel<4>(hb, kb, 1), lod.f);
+      dxx = lod_blend(dxx, linear_channel<4>(db, kb, 1), lod.f);
+      hz = lod_blend(hz, linear_channel<4>(hb, kb, 2), lod.f);
+      dzz = lod_blend(dzz, linear_channel<4>(db, kb, 2), lod.f);
+      j = lod_blend(j, linear_channel<1>(jb, kb, 0), lod.f);
+    }
+    jac += j / (float)p.count;
+    const float f = p.c[c].scale;
+    d[0] += hx;        // dh/dx
+    d[1] += dxx * f;   // dDx/dx
+    d[2] += hz;        // dh/dz
+    d[3] += dzz * f;   // dDz/dz
+  }
+  return surface_normal(d[0], d[1], d[2], d[3], jac);
+}
+
+// k_surface with a footprint per point: xzf = (x, z, footprint) triples, or on the plane mesh the spacing
+// of the warped vertices, k * (40 / res) with k the vertex's warp factor. Slot 7: the footprint used.
+__global__ __launch_bounds__(256) void k_surface_lod(SurfaceParams p, SurfacePlane plane, const float* __restrict__ xzf,
+                                                     int64_t count, float4* __restrict__ out)
+{
+#pragma clang fp contract(off)
+  const SurfacePlaneTurn turn = surface_plane_turn(plane);
+  const int top = 31 - __clz(p.n);
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < count;
+       idx += (int64_t)gridDim.x * blockDim.x)
+  {
+    float px, pz, footprint;
+    if (plane.res > 0)
+    {
+      float k;
+      surface_plane_point(plane, turn, idx, px, pz, k);
+      footprint = k * (40.0f / (float)plane.res);
+    }
+    else
+    {
+      px = xzf[3 * idx];
+      pz = xzf[3 * idx + 1];
+      footprint = xzf[3 * idx + 2];
+    }
+    float py = 0.0f;
+    surface_vertex_stage_lod(p, top, footprint, px, py, pz);
+    const float4 f = surface_fragment_stage_lod(p, top, footprint, px, pz);
+    out[2 * idx] = make_float4(px, py, pz, f.w);
+    out[2 * idx + 1] = make_float4(f.x, f.y, f.z, footprint);
+  }
+}
+
+}  // namespace oceanfft

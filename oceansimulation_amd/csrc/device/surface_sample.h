@@ -1,7 +1,9 @@
 // device/surface_sample.h — the GL_LINEAR + GL_REPEAT sampling of the generator's maps and the stages
-// built on it that more than one translation unit runs: the vertex stage (ocean_kernels.hip's surface
-// kernels, device/k_hulls.h, device/k_raycast.h), the fragment stage (ocean_kernels.hip, device/k_raycast.h)
-// and the velocity of a water particle (k_surface_velocity, device/k_hulls.h).
+// built on it that more than one kernel runs: the vertex stage and the query's fixed point on it (device/
+// k_surface.h, device/k_hulls.h, device/k_raycast.h), the fragment stage and its tail (device/k_surface.h,
+// device/k_raycast.h), the plane mesh's warp (k_surface, k_surface_lod) and the velocity of a water particle
+// (k_surface_velocity, device/k_hulls.h). Each operation is defined here once, so a hull point, a ray
+// evaluation and a query are the same fp32 operations in the same order.
 // Everything is unfused fp32: the oracle and the numpy references are matched bit for bit.
 #pragma once
 
@@ -91,6 +93,17 @@ __device__ __forceinline__ void surface_vertex_stage(const SurfaceParams& p, flo
   }
 }
 
+// The fragment stage's tail (waveShader.glsl:139-144): the summed slopes d = (dh/dx, dDx/dx, dh/dz, dDz/dz)
+// and the averaged Jacobian -> (nx, ny, nz, jac)
+__device__ __forceinline__ float4 surface_normal(float d0, float d1, float d2, float d3, float jac)
+{
+#pragma clang fp contract(off)
+  const float sx = d0 / (1.0f + d1), sz = d2 / (1.0f + d3);
+  const float nx = -sx, ny = 1.0f, nz = -sz;
+  const float len = sqrtf(nx * nx + ny * ny + nz * nz);
+  return make_float4(nx / len, ny / len, nz / len, jac);
+}
+
 // Fragment stage at the displaced position (waveShader.glsl:127-144): (nx, ny, nz, averaged Jacobian)
 template <bool ATLAS>
 __device__ __forceinline__ float4 surface_fragment_stage(const SurfaceParams& p, float px, float pz)
@@ -127,10 +140,91 @@ __device__ __forceinline__ float4 surface_fragment_stage(const SurfaceParams& p,
     d[2] += hz;        // dh/dz
     d[3] += dzz * f;   // dDz/dz
   }
-  const float sx = d[0] / (1.0f + d[1]), sz = d[2] / (1.0f + d[3]);
-  const float nx = -sx, ny = 1.0f, nz = -sz;
-  const float len = sqrtf(nx * nx + ny * ny + nz * nz);
-  return make_float4(nx / len, ny / len, nz / len, jac);
+  return surface_normal(d[0], d[1], d[2], d[3], jac);
+}
+
+// The query's fixed point (ocean_surface_query, include/oceanfft.h): the base point p whose displaced
+// position V(p).xz is q, by p <- p + (q - V(p).xz), at most `iterations` steps, a lane stopping once
+// max|q - V(p).xz| <= tolerance. base_x, base_z enter as the start (q itself for a cold start) and leave as
+// the base point; out_v* leave as V(p). Only the vertex stage is iterated. Lanes of a wave stop at
+// different steps: the wave runs until its last lane is done. |a| > tolerance is written as
+// !(|a| <= tolerance), so a NaN residual keeps iterating instead of passing for converged.
+template <bool ATLAS>
+__device__ __forceinline__ void surface_base_point(const SurfaceParams& p, float qx, float qz, int iterations,
+                                                   float tolerance, float& base_x, float& base_z, float& out_vx,
+                                                   float& out_vy, float& out_vz)
+{
+#pragma clang fp contract(off)
+  // The loop runs on locals: stores through the references, which may alias for all the compiler knows,
+  // give the loop another shape than the one the three kernels had when each wrote it out.
+  float bx = base_x, bz = base_z;
+  float vx = bx, vy = 0.0f, vz = bz;
+  surface_vertex_stage<ATLAS>(p, vx, vy, vz);
+  for (int it = 0; it < iterations; it++)
+  {
+    const float rx = qx - vx, rz = qz - vz;
+    if (fabsf(rx) <= tolerance && fabsf(rz) <= tolerance)
+      break;
+    bx += rx;
+    bz += rz;
+    vx = bx;
+    vy = 0.0f;
+    vz = bz;
+    surface_vertex_stage<ATLAS>(p, vx, vy, vz);
+  }
+  base_x = bx;
+  base_z = bz;
+  out_vx = vx;
+  out_vy = vy;
+  out_vz = vz;
+}
+
+// max(|qx - vx|, |qz - vz|), NaN if either is: the residual a query reports
+__device__ __forceinline__ float surface_residual(float qx, float qz, float vx, float vz)
+{
+#pragma clang fp contract(off)
+  const float ex = fabsf(qx - vx), ez = fabsf(qz - vz);
+  return (ex >= ez || ex != ex) ? ex : ez;
+}
+
+// The plane mesh (ocean_surface_sample_plane). The wave-uniform part, computed once ahead of the item
+// loop: turnDir = normalize(forward.xz) rotated by 45 degrees (waveShader.glsl:84-88) and the clamped
+// camera height; zeros for a request with positions (plane.res == 0).
+struct SurfacePlaneTurn
+{
+  float tx, tz, cam_y;
+};
+
+__device__ __forceinline__ SurfacePlaneTurn surface_plane_turn(const SurfacePlane& plane)
+{
+#pragma clang fp contract(off)
+  SurfacePlaneTurn t{0.0f, 0.0f, 0.0f};
+  if (plane.res > 0)
+  {
+    const float fl = sqrtf(plane.fwd_x * plane.fwd_x + plane.fwd_z * plane.fwd_z);
+    const float tx0 = plane.fwd_x / fl, tz0 = plane.fwd_z / fl;
+    t.tx = (tx0 - tz0) * 0.70711f;
+    t.tz = (tx0 + tz0) * 0.70711f;
+    t.cam_y = fmaxf(plane.cam_y, 10.0f);
+  }
+  return t;
+}
+
+// Vertex idx of the mesh: the plane vertex (src/Renderer.cpp:18), + (15, 0, 15), rotate, distance scale,
+// camera offset -> (px, pz); k is the vertex's warp factor (the LOD kernel's footprint is k * spacing)
+__device__ __forceinline__ void surface_plane_point(const SurfacePlane& plane, const SurfacePlaneTurn& t, int64_t idx,
+                                                    float& px, float& pz, float& k)
+{
+#pragma clang fp contract(off)
+  const int side = plane.res + 1;
+  const int i = (int)(idx % side), j = (int)(idx / side);
+  const float x = -20.0f + 40.0f * (float)i / (float)plane.res + 15.0f;
+  const float z = -20.0f + 40.0f * (float)j / (float)plane.res + 15.0f;
+  const float rx = t.tx * x - t.tz * z, rz = x * t.tz + z * t.tx;
+  const float len = sqrtf(rx * rx + rz * rz);
+  k = powf(fmaxf(len, 1.0f), 1.2f) * t.cam_y * 0.04f;
+  px = rx * k + plane.cam_x;
+  pz = rz * k + plane.cam_z;
 }
 
 // ocean_surface_velocity's loop (include/oceanfft.h): (px, pz) enters as the base point, py and u as 0;

@@ -1,8 +1,10 @@
 // ocean_capi.cpp — implementation of the C ABI in include/oceanfft.h.
 //
 // Host-side orchestration of the reference's FFTCalculator / Generator (src/FFTCalculator.cpp,
-// src/Generator.cpp) over the HIP kernels in ocean_kernels.hip. No CPU fallback exists: without a
-// GPU every entry point fails with OCEAN_ERR_NO_DEVICE / OCEAN_ERR_HIP.
+// src/Generator.cpp) over the HIP kernels in ocean_kernels.hip and launch_*.hip: the plans, the
+// generators and their exchanges. The entry points that consume a generator's maps (the map getters,
+// the surface requests, mips, rates, bounds and hull sets) are in ocean_capi_surface.cpp. No CPU fallback
+// exists: without a GPU every entry point fails with OCEAN_ERR_NO_DEVICE / OCEAN_ERR_HIP.
 #include "oceanfft.h"
 
 #include <hip/hip_runtime.h>
@@ -15,36 +17,13 @@
 #include <string>
 #include <vector>
 
-#include "device/mip_index.h"
+#include "ocean_capi_internal.h"
 #include "ocean_internal.h"
-
-using namespace oceanfft;
 
 static_assert(sizeof(ocean_settings) == sizeof(OceanSettings), "settings layout");
 
 namespace
 {
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg)
-{
-  g_err = msg;
-  return code;
-}
-
-int hip_fail(hipError_t e, const char* what)
-{
-  return fail(OCEAN_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
-#define HIP_TRY(expr, what)                                                                        \
-  do                                                                                               \
-  {                                                                                                \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess)                                                                          \
-      return hip_fail(e_, what);                                                                   \
-  } while (0)
-
 int log2_exact(size_t n)
 {
   int l = 0;
@@ -52,138 +31,11 @@ int log2_exact(size_t n)
     l++;
   return ((size_t)1 << l) == n ? l : -1;
 }
-
-struct EventPair
-{
-  int kind;
-  hipEvent_t a, b;
-};
 }  // namespace
-
-struct ocean_fft
-{
-  int n = 0;
-  int logn = 0;
-  int device = 0;
-  int device_cus = 0;  // CUs of the device
-  int cus = 0;         // CU budget persistent grids are sized for (ocean_fft_set_cu_budget)
-  hipStream_t stream = nullptr;
-  float2* twiddles = nullptr;  // two-level table, see FftShape in device/fft.h
-  float2* tw2 = nullptr;       // the N/16-point table after it (fourstep_table sizes), else null
-  float2* twm = nullptr;       // the 4096-point table after that (ifft_pre_supported sizes), else null
-  float4* work = nullptr;      // column-first EncodeIFFT work image (the reference's workImage)
-  int work_images = 0;
-  size_t work_texels = 0;      // four-step EncodeIFFT (N = 16384): work slab of N x kFourStepSlab texels
-  size_t work_limit = (size_t)-1;  // ocean_debug_fft_work_limit: no work image / slab above this many bytes
-  float4* surf_atlas = nullptr;  // the surface consumer's repacked maps (launch_surface), grown on demand
-  size_t surf_atlas_texels = 0;
-};
 
 // Four-step EncodeIFFT work slab width at N = 16384 (tools/microbench/ifft4bench,
 // profiles/r02_ifft4bench.log: 2048 columns 5.05 ms, whole image 5.39, in place 7.26)
 constexpr int kFourStepSlab = 2048;
-
-struct ocean_generator
-{
-  ocean_fft* fft = nullptr;
-  int cascades = 0;
-  int rank = 0, ranks = 1;  // slab decomposition of one grid (ranks == 1: whole grids, batched)
-  SlabGeom geom{};          // this rank's column slab [x0, x0 + w) and row slab width w
-  std::vector<ocean_settings> settings;
-  bool update_spectrum = true;  // src/Generator.h:72
-  float4* h0 = nullptr;         // [cascade][w/B][N][B] strip-blocked column slab (B = spectrum_block)
-  float4* inter = nullptr;      // [cascade][ranks][2][w/B][w][B] after the y pass (destination-block order)
-  float4* scratch = nullptr;    // [cascade][2][w][N] row-major, only when B == 1 (N = 16384)
-  float4* maps = nullptr;       // [cascade][2][w][N]: heightMap, displacementMap rows (row-major)
-  float* jac = nullptr;         // [cascade][w][N]
-  // half-spectrum path (ranks == 1, N = 1024 .. 4096; ocean_generator_set_half_spectrum)
-  bool half = false;
-  FrameParams frame{};    // the last column pass's per-cascade values (the row pass needs dk)
-  float2* hs = nullptr;    // pass-1 H scratch, half_hs_bytes(logn, device CUs)
-  float4* gab = nullptr;  // [cascade][strip][N][4]: y-transformed (H, kz H) for u >= 0 + Nyquist strip
-  float4* gcd = nullptr;  // (kz H/|k|, kz^2 H/|k|)
-  float2* ge = nullptr;   // H/|k|
-  float4* spec = nullptr; // [cascade][2][N]: the Nyquist-row term R
-  // half-spectrum paths of slabs (N >= 1024) and of whole grids of N = 8192 / 16384: the four-step
-  // column pass (gen4, N = 8192 / 16384, default) or the strip-dealt one (hsl)
-  bool hslab = false;
-  bool slab = false;  // created by ocean_generator_create_slab (also with ranks == 1)
-  HalfSlab hsl{};
-  Gen4Geom g4{};
-  float4* h0row = nullptr;                            // slabs: [cascade][N], row y = 0 of every column
-  float4* rm_ab = nullptr;                            // strip-dealt: row-major fields [cascade][w][kp] after the exchange
-  float4* rm_de = nullptr;
-  float2* rm_c = nullptr;
-  unsigned char* parts = nullptr;                     // four-step: step 1's output [field][cascade][N][lp]
-  unsigned char* xbuf = nullptr;                      // internal exchange buffer (ranks == 1, or null send/recv)
-  size_t xbuf_bytes = 0;
-  // fused re-seed frames (blocked half path): h0 evaluated inside pass 1, the h0 image left stale
-  void* seedc = nullptr;                 // device: one seed_consts record per cascade
-  std::vector<unsigned char> seedc_host; // what seedc holds
-  bool h0_stale = false;                 // the h0 image is not written yet (materialise_h0)
-  std::vector<ocean_settings> seed_settings;  // the settings the last fused re-seed evaluated
-  // N = 8192 / 16384: the four-step column pass writing destination-block order (launch_gen4_columns
-  // / _rows); off: the strip-dealt column pass + transposes. ocean_generator_set_four_step.
-  bool four_step = true;
-  int h0_block = 0;                          // strip width the h0 image was last written with
-  std::vector<ocean_settings> h0_settings;   // the settings it was written from
-  // the settings h0 was last seeded from (written or fused): a requested re-seed with the same
-  // h0 inputs (every field but `time`) would reproduce h0 bit for bit, so it is skipped
-  std::vector<ocean_settings> seeded;
-  bool memo_h0 = true;  // ocean_generator_set_h0_memo
-  // ocean_generator_slab_frame[_pipelined]: the library's own exchange buffers over RCCL, two slots
-  // (frame f in slot f % 2), the exchange on its own stream
-  unsigned char* xsend[2] = {nullptr, nullptr};
-  unsigned char* xrecv[2] = {nullptr, nullptr};
-  size_t xslot_bytes = 0;
-  hipStream_t comm_stream = nullptr;
-  hipEvent_t cols_done[2] = {nullptr, nullptr}, xchg_done[2] = {nullptr, nullptr}, rows_done[2] = {nullptr, nullptr};
-  bool rows_recorded[2] = {false, false};
-  int pending_slot = -1;           // slot whose row pass is still to be issued
-  FrameParams slot_frame[2]{};     // the column pass's per-cascade values of the frame in each slot
-  FoamParams slot_foam[2]{};       // and the settings' displacement its row pass uses
-  int64_t frames_issued = 0;
-  // the one-sided exchange bound to this generator (ocean_peers_create), and the event that orders its
-  // put stream after h0 writes on the generator's stream
-  ocean_peers* peers = nullptr;
-  hipEvent_t put_h0 = nullptr;
-  // Events, not stream handles: the peers' streams (and a caller's) may be destroyed or replaced
-  // between frames, and a recorded event stays valid (a stale `cols_stream`).
-  // cols_ev: the last strip-dealt / four-step column pass on its own stream (step 1 of a split put
-  // frame); the next column pass waits for it, on whatever stream (step 1 rewrites the parts; the
-  // strip-dealt pass reuses its H scratch); a no-op when both run on one stream.
-  // h0r_ev: the end of that pass's last h0 / h0row reader (the put stream's Nyquist-row kernel, which
-  // waited for step 1): every h0 / seed-constant write on the generator's stream waits for it.
-  hipEvent_t cols_ev = nullptr, h0r_ev = nullptr;
-  bool cols_ev_valid = false;
-  // ocean_generator_set_frame_overlap (blocked half path): frame f's column pass on `side` into field
-  // slot f % 2, beside frame f - 1's row pass on the generator's stream
-  bool overlap = false;
-  hipStream_t side = nullptr;
-  float4 *gab2 = nullptr, *gcd2 = nullptr, *spec2 = nullptr;
-  float2* ge2 = nullptr;
-  hipEvent_t ocols[2] = {nullptr, nullptr}, orows[2] = {nullptr, nullptr}, oh0 = nullptr;
-  bool orows_valid[2] = {false, false};
-  int oslot = 0;
-  bool h0_dirty = false;  // h0 (or the fused re-seed constants) written on the generator's stream since the side stream last waited
-  // the mip pyramid of the maps (ocean_generator_build_mips): [cascade][heightMap | displacementMap |
-  // jacobian chains], allocated on first use; fresh until the next call that rewrites the maps
-  float* mips = nullptr;
-  bool mips_fresh = false;
-  // the time derivative of the maps (ocean_generator_calculate_rates): [cascade][height-rate |
-  // displacement-rate][N * N], allocated on first use; fresh until the next column pass
-  float4* rates = nullptr;
-  bool rates_fresh = false;
-  // the bounds of the maps (ocean_generator_build_bounds): the table [cascade][18], then stage 1's partial
-  // rows (bounds_floats), allocated on first use; fresh until the next call that rewrites the maps
-  float* bounds = nullptr;
-  bool bounds_fresh = false;
-  bool profiling = false;
-  std::vector<EventPair> pending;
-  std::vector<hipEvent_t> pool;
-  double ms[4] = {0, 0, 0, 0};         // per kind: 0 h0, 1 column pass, 2 row pass, 3 the put inside 1
-  int64_t launches[4] = {0, 0, 0, 0};
-};
 
 static void peers_detach(ocean_peers* p);  // the one-sided exchange section below
 static bool peers_pending(const ocean_peers* p);
@@ -838,7 +690,7 @@ int ocean_generator_generate_spectrum(ocean_generator* g)
 }
 
 // After fused re-seed frames: write the h0 image those frames evaluated (their settings snapshot).
-static int materialise_h0(ocean_generator* g)
+int materialise_h0(ocean_generator* g)  // ocean_capi_internal.h
 {
   return g->h0_stale ? generate_spectrum_with(g, g->seed_settings) : OCEAN_OK;
 }
@@ -2202,700 +2054,6 @@ int ocean_generator_slab_info(const ocean_generator* g, int* rank, int* ranks, i
     *row0 = g->rank * g->geom.w;
   if (rows)
     *rows = g->geom.w;
-  return OCEAN_OK;
-}
-
-float* ocean_generator_height_map(ocean_generator* g, int c)
-{
-  if (!g || c < 0 || c >= g->cascades)
-    return nullptr;
-  return reinterpret_cast<float*>(g->maps + (size_t)g->fft->n * g->geom.w * (2 * c));
-}
-
-float* ocean_generator_displacement_map(ocean_generator* g, int c)
-{
-  if (!g || c < 0 || c >= g->cascades)
-    return nullptr;
-  return reinterpret_cast<float*>(g->maps + (size_t)g->fft->n * g->geom.w * (2 * c + 1));
-}
-
-float* ocean_generator_jacobian_map(ocean_generator* g, int c)
-{
-  if (!g || c < 0 || c >= g->cascades)
-    return nullptr;
-  return g->jac + (size_t)g->fft->n * g->geom.w * c;
-}
-
-static int surface_params(ocean_generator* const* gens, const int* cascades, int count, SurfaceParams& p,
-                          ocean_fft*& fft, const char* who)
-{
-  if (!gens || !cascades || count < 1 || count > kMaxSurfaceCascades)
-    return fail(OCEAN_ERR_INVALID, std::string(who) + ": need 1..16 (generator, cascade) pairs");
-  p = SurfaceParams{};
-  p.count = count;
-  fft = nullptr;
-  for (int i = 0; i < count; i++)
-  {
-    ocean_generator* g = gens[i];
-    if (!g || cascades[i] < 0 || cascades[i] >= g->cascades)
-      return fail(OCEAN_ERR_INVALID, std::string(who) + ": null generator or cascade out of range");
-    if (g->ranks != 1)
-      return fail(OCEAN_ERR_INVALID, std::string(who) + ": slab generators hold row slabs, not whole maps");
-    if (!fft)
-      fft = g->fft;
-    else if (g->fft->n != fft->n)
-      return fail(OCEAN_ERR_INVALID, std::string(who) + ": all cascades must share one map size");
-    const int c = cascades[i];
-    p.c[i].height = reinterpret_cast<const float4*>(ocean_generator_height_map(g, c));
-    p.c[i].disp = reinterpret_cast<const float4*>(ocean_generator_displacement_map(g, c));
-    p.c[i].jac = ocean_generator_jacobian_map(g, c);
-    p.c[i].plane = g->settings[c].planeSize;
-    p.c[i].scale = g->settings[c].displacement;
-  }
-  p.n = fft->n;
-  p.atlas = nullptr;
-  return OCEAN_OK;
-}
-
-// The surface atlas of a request that uses one (surface_use_atlas / surface_query_use_atlas), owned by the
-// plan whose stream runs the request: requests on one plan are stream-ordered, so one buffer serves them all.
-static int surface_atlas(ocean_fft* fft, SurfaceParams& p, bool use, const char* who)
-{
-  if (!use)
-    return OCEAN_OK;
-  const size_t texels = surface_atlas_texels(p);
-  if (fft->surf_atlas_texels < texels)
-  {
-    if (fft->surf_atlas)
-    {
-      HIP_TRY(hipStreamSynchronize(fft->stream), who);  // an earlier request may still read the old one
-      HIP_TRY(hipFree(fft->surf_atlas), who);
-      fft->surf_atlas = nullptr;
-      fft->surf_atlas_texels = 0;
-    }
-    HIP_TRY(hipMalloc(&fft->surf_atlas, texels * sizeof(float4)), who);
-    fft->surf_atlas_texels = texels;
-  }
-  p.atlas = fft->surf_atlas;
-  return OCEAN_OK;
-}
-
-int ocean_surface_sample(ocean_generator* const* gens, const int* cascades, int count, const float* xz,
-                         int64_t points, float* out)
-{
-  SurfaceParams p;
-  ocean_fft* fft;
-  int rc = surface_params(gens, cascades, count, p, fft, "ocean_surface_sample");
-  if (rc != OCEAN_OK)
-    return rc;
-  if (points < 0 || (points > 0 && (!xz || !out)))
-    return fail(OCEAN_ERR_INVALID, "ocean_surface_sample: null positions/output or negative count");
-  rc = surface_atlas(fft, p, surface_use_atlas(p, points), "ocean_surface_sample");
-  if (rc != OCEAN_OK)
-    return rc;
-  HIP_TRY(launch_surface(p, SurfacePlane{}, reinterpret_cast<const float2*>(xz), points, reinterpret_cast<float4*>(out),
-                         fft->stream, fft->cus),
-          "ocean_surface_sample");
-  return OCEAN_OK;
-}
-
-int ocean_surface_query(ocean_generator* const* gens, const int* cascades, int count, const float* xz, int64_t points,
-                        int iterations, float tolerance, float* out)
-{
-  SurfaceParams p;
-  ocean_fft* fft;
-  int rc = surface_params(gens, cascades, count, p, fft, "ocean_surface_query");
-  if (rc != OCEAN_OK)
-    return rc;
-  if (iterations < 0 || iterations > 64)
-    return fail(OCEAN_ERR_INVALID, "ocean_surface_query: iterations outside 0..64");
-  if (!(tolerance >= 0.0f) || !std::isfinite(tolerance))
-    return fail(OCEAN_ERR_INVALID, "ocean_surface_query: tolerance must be finite and >= 0");
-  if (points < 0 || (points > 0 && (!xz || !out)))
-    return fail(OCEAN_ERR_INVALID, "ocean_surface_query: null positions/output or negative count");
-  rc = surface_atlas(fft, p, surface_query_use_atlas(p, points, iterations), "ocean_surface_query");
-  if (rc != OCEAN_OK)
-    return rc;
-  HIP_TRY(launch_surface_query(p, reinterpret_cast<const float2*>(xz), points, iterations, tolerance,
-                               reinterpret_cast<float4*>(out), fft->stream, fft->cus),
-          "ocean_surface_query");
-  return OCEAN_OK;
-}
-
-int ocean_surface_sample_plane(ocean_generator* const* gens, const int* cascades, int count, const float camera[5],
-                               int res, float* out)
-{
-  SurfaceParams p;
-  ocean_fft* fft;
-  int rc = surface_params(gens, cascades, count, p, fft, "ocean_surface_sample_plane");
-  if (rc != OCEAN_OK)
-    return rc;
-  if (!camera || !out || res < 1 || res > 46340)
-    return fail(OCEAN_ERR_INVALID, "ocean_surface_sample_plane: null camera/output or resolution outside 1..46340");
-  if (camera[3] == 0.0f && camera[4] == 0.0f)
-    return fail(OCEAN_ERR_INVALID, "ocean_surface_sample_plane: camera forward has no horizontal component");
-  const SurfacePlane plane{res, camera[0], camera[1], camera[2], camera[3], camera[4]};
-  const int64_t pts = (int64_t)(res + 1) * (res + 1);
-  rc = surface_atlas(fft, p, surface_use_atlas(p, pts), "ocean_surface_sample_plane");
-  if (rc != OCEAN_OK)
-    return rc;
-  HIP_TRY(launch_surface(p, plane, nullptr, pts, reinterpret_cast<float4*>(out), fft->stream, fft->cus),
-          "ocean_surface_sample_plane");
-  return OCEAN_OK;
-}
-
-// ---- mip pyramid and footprint-aware sampling ----
-int ocean_generator_mip_levels(const ocean_generator* g) { return g ? g->fft->logn + 1 : 0; }
-
-int ocean_generator_build_mips(ocean_generator* g)
-{
-  if (!g)
-    return fail(OCEAN_ERR_INVALID, "ocean_generator_build_mips: null generator");
-  if (g->slab || g->ranks != 1)
-    return fail(OCEAN_ERR_INVALID, "ocean_generator_build_mips: slab generators hold row slabs, not whole maps");
-  ocean_fft* f = g->fft;
-  if (!g->mips)
-  {
-    const hipError_t e = hipMalloc(&g->mips, (size_t)g->cascades * mip_cascade_floats(f->n) * sizeof(float));
-    if (e != hipSuccess)
-    {
-      g->mips = nullptr;
-      return fail(e == hipErrorOutOfMemory ? OCEAN_ERR_OOM : OCEAN_ERR_HIP,
-                  std::string("ocean_generator_build_mips: ") + hipGetErrorString(e));
-    }
-  }
-  g->mips_fresh = false;
-  HIP_TRY(launch_build_mips(f->n, g->cascades, g->maps, g->jac, g->mips, f->stream), "ocean_generator_build_mips");
-  g->mips_fresh = true;
-  return OCEAN_OK;
-}
-
-// Level `level` of map `map` (0 heightMap, 1 displacementMap, 2 jacobian) of cascade c
-static float* generator_mip(ocean_generator* g, int c, int level, int map, const char* who)
-{
-  if (!g || c < 0 || c >= g->cascades)
-  {
-    fail(OCEAN_ERR_INVALID, std::string(who) + ": null generator or cascade out of range");
-    return nullptr;
-  }
-  if (level < 0 || level > g->fft->logn)
-  {
-    fail(OCEAN_ERR_INVALID, std::string(who) + ": level outside 0..log2(N)");
-    return nullptr;
-  }
-  if (level == 0)
-    return map == 0 ? ocean_generator_height_map(g, c)
-                    : (map == 1 ? ocean_generator_displacement_map(g, c) : ocean_generator_jacobian_map(g, c));
-  if (!g->mips)
-  {
-    fail(OCEAN_ERR_INVALID, std::string(who) + ": the pyramid was never built (ocean_generator_build_mips)");
-    return nullptr;
-  }
-  const int n = g->fft->n;
-  const size_t chain = mip_chain_texels(n), off = mip_level_offset(n, level);
-  float* base = g->mips + (size_t)c * mip_cascade_floats(n);
-  return map == 2 ? base + 8 * chain + off : base + (size_t)map * 4 * chain + 4 * off;
-}
-
-float* ocean_generator_height_mip(ocean_generator* g, int c, int level)
-{
-  return generator_mip(g, c, level, 0, "ocean_generator_height_mip");
-}
-
-float* ocean_generator_displacement_mip(ocean_generator* g, int c, int level)
-{
-  return generator_mip(g, c, level, 1, "ocean_generator_displacement_mip");
-}
-
-float* ocean_generator_jacobian_mip(ocean_generator* g, int c, int level)
-{
-  return generator_mip(g, c, level, 2, "ocean_generator_jacobian_mip");
-}
-
-// surface_params of a LOD call: also the chains, which must be built and not older than the maps
-static int surface_params_lod(ocean_generator* const* gens, const int* cascades, int count, SurfaceParams& p,
-                              ocean_fft*& fft, const char* who)
-{
-  const int rc = surface_params(gens, cascades, count, p, fft, who);
-  if (rc != OCEAN_OK)
-    return rc;
-  for (int i = 0; i < count; i++)
-  {
-    ocean_generator* g = gens[i];
-    if (!g->mips || !g->mips_fresh)
-      return fail(OCEAN_ERR_INVALID, std::string(who) + ": generator " + std::to_string(i) +
-                                         (g->mips ? " has a stale mip pyramid (its maps were rewritten since"
-                                                  : " has no mip pyramid (call") +
-                                         " ocean_generator_build_mips)");
-    const size_t chain = mip_chain_texels(fft->n);
-    const float* base = g->mips + (size_t)cascades[i] * mip_cascade_floats(fft->n);
-    p.c[i].height_mip = reinterpret_cast<const float4*>(base);
-    p.c[i].disp_mip = reinterpret_cast<const float4*>(base + 4 * chain);
-    p.c[i].jac_mip = base + 8 * chain;
-  }
-  return OCEAN_OK;
-}
-
-int ocean_surface_sample_lod(ocean_generator* const* gens, const int* cascades, int count, const float* xzf,
-                             int64_t points, float* out)
-{
-  SurfaceParams p;
-  ocean_fft* fft;
-  const int rc = surface_params_lod(gens, cascades, count, p, fft, "ocean_surface_sample_lod");
-  if (rc != OCEAN_OK)
-    return rc;
-  if (points < 0 || (points > 0 && (!xzf || !out)))
-    return fail(OCEAN_ERR_INVALID, "ocean_surface_sample_lod: null positions/output or negative count");
-  HIP_TRY(launch_surface_lod(p, SurfacePlane{}, xzf, points, reinterpret_cast<float4*>(out), fft->stream, fft->cus),
-          "ocean_surface_sample_lod");
-  return OCEAN_OK;
-}
-
-int ocean_surface_sample_plane_lod(ocean_generator* const* gens, const int* cascades, int count, const float camera[5],
-                                   int res, float* out)
-{
-  SurfaceParams p;
-  ocean_fft* fft;
-  const int rc = surface_params_lod(gens, cascades, count, p, fft, "ocean_surface_sample_plane_lod");
-  if (rc != OCEAN_OK)
-    return rc;
-  if (!camera || !out || res < 1 || res > 46340)
-    return fail(OCEAN_ERR_INVALID,
-                "ocean_surface_sample_plane_lod: null camera/output or resolution outside 1..46340");
-  if (camera[3] == 0.0f && camera[4] == 0.0f)
-    return fail(OCEAN_ERR_INVALID, "ocean_surface_sample_plane_lod: camera forward has no horizontal component");
-  const SurfacePlane plane{res, camera[0], camera[1], camera[2], camera[3], camera[4]};
-  const int64_t pts = (int64_t)(res + 1) * (res + 1);
-  HIP_TRY(launch_surface_lod(p, plane, nullptr, pts, reinterpret_cast<float4*>(out), fft->stream, fft->cus),
-          "ocean_surface_sample_plane_lod");
-  return OCEAN_OK;
-}
-
-// ---- time derivative of the maps and the velocity of water particles ----
-int ocean_generator_calculate_rates(ocean_generator* g)
-{
-  if (!g)
-    return fail(OCEAN_ERR_INVALID, "ocean_generator_calculate_rates: null generator");
-  if (g->slab || g->ranks != 1)
-    return fail(OCEAN_ERR_INVALID, "ocean_generator_calculate_rates: slab generators hold row slabs, not whole maps");
-  if (g->frame.cascades != g->cascades)
-    return fail(OCEAN_ERR_INVALID, "ocean_generator_calculate_rates: no frame calculated yet (ocean_generator_calculate)");
-  ocean_fft* f = g->fft;
-  const size_t nn = (size_t)f->n * f->n;
-  if (!g->rates)
-  {
-    const hipError_t e = hipMalloc(&g->rates, (size_t)g->cascades * 2 * nn * sizeof(float4));
-    if (e != hipSuccess)
-    {
-      g->rates = nullptr;
-      return fail(e == hipErrorOutOfMemory ? OCEAN_ERR_OOM : OCEAN_ERR_HIP,
-                  std::string("ocean_generator_calculate_rates: ") + hipGetErrorString(e));
-    }
-  }
-  g->rates_fresh = false;
-  // after fused re-seed frames the h0 image is still to be written: on the generator's stream, so with
-  // frame overlap the next column pass waits for it (h0_dirty, set by the write); the memo keeps its inputs
-  int rc = materialise_h0(g);
-  if (rc != OCEAN_OK)
-    return rc;
-  HIP_TRY(launch_rates_pack(f->logn, g->frame, g->h0_block, g->h0, g->rates, f->stream, f->cus),
-          "ocean_generator_calculate_rates");
-  rc = ocean_fft_encode_ifft_batch(f, reinterpret_cast<float*>(g->rates), 2 * g->cascades);
-  if (rc != OCEAN_OK)
-    return rc;
-  g->rates_fresh = true;
-  return OCEAN_OK;
-}
-
-// Image `image` (0 height-rate, 1 displacement-rate) of cascade c
-static float* generator_rate_map(ocean_generator* g, int c, int image, const char* who)
-{
-  if (!g || c < 0 || c >= g->cascades)
-  {
-    fail(OCEAN_ERR_INVALID, std::string(who) + ": null generator or cascade out of range");
-    return nullptr;
-  }
-  if (!g->rates)
-  {
-    fail(OCEAN_ERR_INVALID, std::string(who) + ": the rates were never calculated (ocean_generator_calculate_rates)");
-    return nullptr;
-  }
-  return reinterpret_cast<float*>(g->rates + (size_t)g->fft->n * g->fft->n * (2 * c + image));
-}
-
-float* ocean_generator_height_rate_map(ocean_generator* g, int c)
-{
-  return generator_rate_map(g, c, 0, "ocean_generator_height_rate_map");
-}
-
-float* ocean_generator_displacement_rate_map(ocean_generator* g, int c)
-{
-  return generator_rate_map(g, c, 1, "ocean_generator_displacement_rate_map");
-}
-
-// The rate maps of a request's cascades, which must be calculated and not older than the maps
-static int surface_rates(ocean_generator* const* gens, const int* cascades, int count, const ocean_fft* fft,
-                         SurfaceRates& r, const char* who)
-{
-  r = SurfaceRates{};
-  for (int i = 0; i < count; i++)
-  {
-    ocean_generator* g = gens[i];
-    if (!g->rates || !g->rates_fresh)
-      return fail(OCEAN_ERR_INVALID, std::string(who) + ": generator " + std::to_string(i) +
-                                         (g->rates ? " has stale rates (a frame was calculated since"
-                                                   : " has no rates (call") +
-                                         " ocean_generator_calculate_rates)");
-    const size_t nn = (size_t)fft->n * fft->n;
-    r.height[i] = g->rates + nn * (2 * cascades[i]);
-    r.disp[i] = g->rates + nn * (2 * cascades[i] + 1);
-  }
-  return OCEAN_OK;
-}
-
-int ocean_surface_velocity(ocean_generator* const* gens, const int* cascades, int count, const float* xz,
-                           int64_t points, float* out)
-{
-  SurfaceParams p;
-  ocean_fft* fft;
-  int rc = surface_params(gens, cascades, count, p, fft, "ocean_surface_velocity");
-  if (rc != OCEAN_OK)
-    return rc;
-  SurfaceRates r;
-  rc = surface_rates(gens, cascades, count, fft, r, "ocean_surface_velocity");
-  if (rc != OCEAN_OK)
-    return rc;
-  if (points < 0 || (points > 0 && (!xz || !out)))
-    return fail(OCEAN_ERR_INVALID, "ocean_surface_velocity: null positions/output or negative count");
-  HIP_TRY(launch_surface_velocity(p, r, reinterpret_cast<const float2*>(xz), points, reinterpret_cast<float4*>(out),
-                                  fft->stream, fft->cus),
-          "ocean_surface_velocity");
-  return OCEAN_OK;
-}
-
-// ---- bounds of the maps and ray casting against the displaced surface ----
-int ocean_generator_build_bounds(ocean_generator* g)
-{
-  if (!g)
-    return fail(OCEAN_ERR_INVALID, "ocean_generator_build_bounds: null generator");
-  if (g->slab || g->ranks != 1)
-    return fail(OCEAN_ERR_INVALID, "ocean_generator_build_bounds: slab generators hold row slabs, not whole maps");
-  if (g->frame.cascades != g->cascades)
-    return fail(OCEAN_ERR_INVALID, "ocean_generator_build_bounds: no frame calculated yet (ocean_generator_calculate)");
-  ocean_fft* f = g->fft;
-  if (!g->bounds)
-  {
-    const hipError_t e = hipMalloc(&g->bounds, bounds_floats(f->n, g->cascades) * sizeof(float));
-    if (e != hipSuccess)
-    {
-      g->bounds = nullptr;
-      return fail(e == hipErrorOutOfMemory ? OCEAN_ERR_OOM : OCEAN_ERR_HIP,
-                  std::string("ocean_generator_build_bounds: ") + hipGetErrorString(e));
-    }
-  }
-  g->bounds_fresh = false;
-  HIP_TRY(launch_build_bounds(f->n, g->cascades, g->maps, g->jac, g->bounds, f->stream, f->cus),
-          "ocean_generator_build_bounds");
-  g->bounds_fresh = true;
-  return OCEAN_OK;
-}
-
-// The table of a generator whose bounds are built and not older than its maps, else null with a message
-static const float* generator_bounds(ocean_generator* g, const char* who)
-{
-  if (!g)
-  {
-    fail(OCEAN_ERR_INVALID, std::string(who) + ": null generator");
-    return nullptr;
-  }
-  if (!g->bounds || !g->bounds_fresh)
-  {
-    fail(OCEAN_ERR_INVALID, std::string(who) + (g->bounds ? ": the bounds are stale (the maps were rewritten since"
-                                                           : ": the bounds were never built (call") +
-                                " ocean_generator_build_bounds)");
-    return nullptr;
-  }
-  return g->bounds;
-}
-
-const float* ocean_generator_bounds_device(ocean_generator* g)
-{
-  return generator_bounds(g, "ocean_generator_bounds_device");
-}
-
-int ocean_generator_bounds(ocean_generator* g, int cascade, float out[18])
-{
-  const float* table = generator_bounds(g, "ocean_generator_bounds");
-  if (!table)
-    return OCEAN_ERR_INVALID;
-  if (cascade < 0 || cascade >= g->cascades || !out)
-    return fail(OCEAN_ERR_INVALID, "ocean_generator_bounds: cascade out of range or null output");
-  HIP_TRY(hipMemcpyAsync(out, table + (size_t)cascade * 18, 18 * sizeof(float), hipMemcpyDeviceToHost, g->fft->stream),
-          "ocean_generator_bounds");
-  HIP_TRY(hipStreamSynchronize(g->fft->stream), "ocean_generator_bounds");
-  return OCEAN_OK;
-}
-
-int ocean_surface_raycast(ocean_generator* const* gens, const int* cascades, int count, const float* rays,
-                          int64_t n_rays, float step, int max_steps, int refine, int iterations, float tolerance,
-                          float slope, float pad, float* out)
-{
-  // the scalar rules first: they need no generator
-  if (!gens || !cascades)
-    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: null gens / cascades");
-  if (!std::isfinite(step) || !(step > 0.0f))
-    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: step must be finite and > 0");
-  if (max_steps < 1 || max_steps > 65535)
-    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: max_steps outside 1..65535");
-  if (refine < 0 || refine > 32)
-    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: refine outside 0..32");
-  if (iterations < 0 || iterations > 64)
-    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: iterations outside 0..64");
-  if (!(tolerance >= 0.0f) || !std::isfinite(tolerance))
-    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: tolerance must be finite and >= 0");
-  if (!(pad >= 0.0f) || !std::isfinite(pad))
-    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: pad must be finite and >= 0");
-  if (!(slope >= 0.0f))
-    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: slope must be >= 0 (+inf: fixed steps)");
-  if (n_rays < 0 || (n_rays > 0 && (!rays || !out)))
-    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: null rays/output or negative count");
-  SurfaceParams p;
-  ocean_fft* fft;
-  const int rc = surface_params(gens, cascades, count, p, fft, "ocean_surface_raycast");
-  if (rc != OCEAN_OK)
-    return rc;
-  RaycastParams r{};
-  for (int i = 0; i < count; i++)
-  {
-    ocean_generator* g = gens[i];
-    if (!g->bounds || !g->bounds_fresh)
-      return fail(OCEAN_ERR_INVALID, std::string("ocean_surface_raycast: generator ") + std::to_string(i) +
-                                         (g->bounds ? " has stale bounds (its maps were rewritten since"
-                                                    : " has no bounds (call") +
-                                         " ocean_generator_build_bounds)");
-    r.bounds[i] = g->bounds + (size_t)cascades[i] * 18;
-  }
-  r.step = step;
-  r.max_steps = max_steps;
-  r.refine = refine;
-  r.iterations = iterations;
-  r.tolerance = tolerance;
-  r.slope = slope;
-  r.pad = pad;
-  HIP_TRY(launch_surface_raycast(p, r, reinterpret_cast<const float4*>(rays), n_rays, reinterpret_cast<float4*>(out),
-                                 fft->stream, fft->cus),
-          "ocean_surface_raycast");
-  return OCEAN_OK;
-}
-
-// ---- hull sets: net wave force and torque on batches of floating bodies ----
-// Consecutive bodies of at most 32 points share a wave (tools/hulls_bench.py times both)
-static bool g_hulls_pack = true;
-
-int ocean_debug_hulls_packing(int enable)
-{
-  g_hulls_pack = enable != 0;
-  return OCEAN_OK;
-}
-
-struct ocean_hulls
-{
-  ocean_fft* fft = nullptr;
-  int bodies = 0;
-  int64_t instance_points = 0;
-  int items = 0;    // 64-point tiles
-  int n_folds = 0;  // bodies of more than one tile
-  float4* points = nullptr;
-  HullTile* tiles = nullptr;
-  HullBody* body_table = nullptr;
-  HullFold* folds = nullptr;
-  float4* partial = nullptr;  // one 8-float partial per tile of a body in `folds`
-};
-
-int ocean_hulls_destroy(ocean_hulls* h)
-{
-  if (!h)
-    return OCEAN_OK;
-  if (h->fft)
-    (void)hipStreamSynchronize(h->fft->stream);
-  for (void* p : {(void*)h->points, (void*)h->tiles, (void*)h->body_table, (void*)h->folds, (void*)h->partial})
-    if (p)
-      (void)hipFree(p);
-  delete h;
-  return OCEAN_OK;
-}
-
-int ocean_hulls_create(ocean_hulls** out, ocean_fft* fft, const float* points, int64_t n_points, const int32_t* ranges,
-                       int bodies)
-{
-  if (!out || !fft || !points || !ranges)
-    return fail(OCEAN_ERR_INVALID, "ocean_hulls_create: null argument");
-  *out = nullptr;
-  if (bodies < 1 || bodies > 1048576)
-    return fail(OCEAN_ERR_INVALID, "ocean_hulls_create: bodies outside 1..1048576");
-  if (n_points < 1)
-    return fail(OCEAN_ERR_INVALID, "ocean_hulls_create: no points");
-  int64_t n_tiles = 0, instance_points = 0;
-  for (int b = 0; b < bodies; b++)
-  {
-    const int64_t first = ranges[2 * b], count = ranges[2 * b + 1];
-    if (count < 1 || count > 262144)
-      return fail(OCEAN_ERR_INVALID, "ocean_hulls_create: body " + std::to_string(b) + " has a count outside 1..262144");
-    if (first < 0 || first + count > n_points)
-      return fail(OCEAN_ERR_INVALID, "ocean_hulls_create: the range of body " + std::to_string(b) + " leaves the points");
-    n_tiles += (count + kHullTilePoints - 1) / kHullTilePoints;
-    instance_points += count;
-  }
-  for (int64_t i = 0; i < n_points; i++)
-  {
-    const float* l = points + 8 * i;
-    for (int k = 0; k < 8; k++)
-      if (!std::isfinite(l[k]))
-        return fail(OCEAN_ERR_INVALID, "ocean_hulls_create: point " + std::to_string(i) + " has a non-finite field");
-    if (l[3] < 0.0f || !(l[4] > 0.0f) || l[5] < 0.0f || l[6] < 0.0f)
-      return fail(OCEAN_ERR_INVALID, "ocean_hulls_create: point " + std::to_string(i) +
-                                         " needs volume >= 0, half_height > 0 and drag coefficients >= 0");
-  }
-  if (n_tiles > INT32_MAX)
-    return fail(OCEAN_ERR_OOM, "ocean_hulls_create: more than 2^31 - 1 tiles of 64 points");
-
-  // the work items, in the order of the bodies: a body's 64-point tiles, or one packed tile for a run of
-  // consecutive small bodies with one segment size; point_out rows in the order of the bodies
-  std::vector<HullTile> tiles;
-  std::vector<HullBody> table((size_t)bodies);
-  std::vector<HullFold> folds;
-  tiles.reserve((size_t)n_tiles);
-  int slot = 0;
-  auto segment = [&](int b) {  // the power of two body b's points fit in
-    int seg = 1;
-    while (seg < ranges[2 * b + 1])
-      seg *= 2;
-    return seg;
-  };
-  int64_t rows = 0;
-  for (int b = 0; b < bodies; b++)
-  {
-    table[b] = HullBody{rows, ranges[2 * b], ranges[2 * b + 1]};
-    rows += ranges[2 * b + 1];
-  }
-  for (int b = 0; b < bodies; b++)
-  {
-    const int first = ranges[2 * b], count = ranges[2 * b + 1];
-    const int seg = segment(b);
-    int run = 1;  // consecutive bodies with this segment size, as many as fit a wave
-    while (g_hulls_pack && seg <= kHullTilePoints / 2 && run < kHullTilePoints / seg && b + run < bodies &&
-           segment(b + run) == seg)
-      run++;
-    if (run > 1)
-    {
-      HullTile t{};
-      t.count = run;
-      t.body = b;
-      t.slot = -1;
-      t.seg = seg;
-      tiles.push_back(t);
-      b += run - 1;
-      continue;
-    }
-    const int64_t offset = table[b].offset;
-    const int nt = (count + kHullTilePoints - 1) / kHullTilePoints;
-    if (nt > 1)
-      folds.push_back(HullFold{b, slot, nt, 0});
-    for (int j = 0; j < nt; j++)
-      tiles.push_back(HullTile{offset + (int64_t)j * kHullTilePoints, first + j * kHullTilePoints,
-                               std::min(kHullTilePoints, count - j * kHullTilePoints), b, nt > 1 ? slot + j : -1});
-    if (nt > 1)
-      slot += nt;
-  }
-
-  auto* h = new ocean_hulls();
-  h->fft = fft;
-  h->bodies = bodies;
-  h->instance_points = instance_points;
-  h->items = (int)tiles.size();
-  h->n_folds = (int)folds.size();
-  hipError_t e = hipMalloc(&h->points, (size_t)n_points * 2 * sizeof(float4));
-  if (e == hipSuccess)
-    e = hipMalloc(&h->tiles, tiles.size() * sizeof(HullTile));
-  if (e == hipSuccess)
-    e = hipMalloc(&h->body_table, table.size() * sizeof(HullBody));
-  if (e == hipSuccess && !folds.empty())
-    e = hipMalloc(&h->folds, folds.size() * sizeof(HullFold));
-  if (e == hipSuccess && slot > 0)
-    e = hipMalloc(&h->partial, (size_t)slot * 2 * sizeof(float4));
-  // synchronous copies from the caller's and these pageable buffers: complete on return
-  if (e == hipSuccess)
-    e = hipMemcpy(h->points, points, (size_t)n_points * 2 * sizeof(float4), hipMemcpyHostToDevice);
-  if (e == hipSuccess)
-    e = hipMemcpy(h->tiles, tiles.data(), tiles.size() * sizeof(HullTile), hipMemcpyHostToDevice);
-  if (e == hipSuccess)
-    e = hipMemcpy(h->body_table, table.data(), table.size() * sizeof(HullBody), hipMemcpyHostToDevice);
-  if (e == hipSuccess && !folds.empty())
-    e = hipMemcpy(h->folds, folds.data(), folds.size() * sizeof(HullFold), hipMemcpyHostToDevice);
-  if (e != hipSuccess)
-  {
-    h->fft = nullptr;
-    ocean_hulls_destroy(h);
-    return fail(e == hipErrorOutOfMemory ? OCEAN_ERR_OOM : OCEAN_ERR_HIP,
-                std::string("ocean_hulls_create: ") + hipGetErrorString(e));
-  }
-  *out = h;
-  return OCEAN_OK;
-}
-
-int ocean_hulls_bodies(const ocean_hulls* h) { return h ? h->bodies : 0; }
-
-int64_t ocean_hulls_instance_points(const ocean_hulls* h) { return h ? h->instance_points : 0; }
-
-int ocean_hulls_loads(ocean_hulls* h, ocean_generator* const* gens, const int* cascades, int count, const float* poses,
-                      float rho_g, int iterations, float tolerance, int water_velocity, float* loads, float* point_out)
-{
-  if (!h)
-    return fail(OCEAN_ERR_INVALID, "ocean_hulls_loads: null hull set");
-  SurfaceParams p;
-  ocean_fft* fft;
-  int rc = surface_params(gens, cascades, count, p, fft, "ocean_hulls_loads");
-  if (rc != OCEAN_OK)
-    return rc;
-  if (gens[0]->fft != h->fft)
-    return fail(OCEAN_ERR_INVALID, "ocean_hulls_loads: the first generator is on another plan than the hull set");
-  if (iterations < 0 || iterations > 64)
-    return fail(OCEAN_ERR_INVALID, "ocean_hulls_loads: iterations outside 0..64");
-  if (!(tolerance >= 0.0f) || !std::isfinite(tolerance))
-    return fail(OCEAN_ERR_INVALID, "ocean_hulls_loads: tolerance must be finite and >= 0");
-  if (!(rho_g >= 0.0f) || !std::isfinite(rho_g))
-    return fail(OCEAN_ERR_INVALID, "ocean_hulls_loads: rho_g must be finite and >= 0");
-  if (water_velocity != 0 && water_velocity != 1)
-    return fail(OCEAN_ERR_INVALID, "ocean_hulls_loads: water_velocity must be 0 or 1");
-  if (!poses || !loads)
-    return fail(OCEAN_ERR_INVALID, "ocean_hulls_loads: null poses/loads");
-  SurfaceRates r{};
-  if (water_velocity)
-  {
-    rc = surface_rates(gens, cascades, count, fft, r, "ocean_hulls_loads");
-    if (rc != OCEAN_OK)
-      return rc;
-  }
-  const bool atlas = surface_query_use_atlas(p, h->instance_points, iterations);
-  rc = surface_atlas(fft, p, atlas, "ocean_hulls_loads");
-  if (rc != OCEAN_OK)
-    return rc;
-  if (atlas)
-    launch_surface_atlas(p, fft->stream, fft->cus);
-  HullCall call{};
-  call.points = h->points;
-  call.tiles = h->tiles;
-  call.bodies = h->body_table;
-  call.poses = poses;
-  call.loads = reinterpret_cast<float4*>(loads);
-  call.partial = h->partial;
-  call.point_out = reinterpret_cast<float4*>(point_out);
-  call.items = h->items;
-  call.iterations = iterations;
-  call.tolerance = tolerance;
-  call.rho_g = rho_g;
-  HIP_TRY(launch_hulls_loads(p, r, water_velocity != 0, call, h->folds, h->n_folds, fft->stream, fft->cus),
-          "ocean_hulls_loads");
   return OCEAN_OK;
 }
 

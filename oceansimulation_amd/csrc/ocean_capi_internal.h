@@ -1,0 +1,173 @@
+// ocean_capi_internal.h — what the translation units of the C ABI (ocean_capi.cpp, ocean_capi_surface.cpp)
+// share: the plan and the generator behind the opaque handles of include/oceanfft.h, and the error string
+// with the helpers that set it.
+#pragma once
+
+#include "oceanfft.h"
+
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "ocean_internal.h"
+
+using namespace oceanfft;
+
+// (hidden, as everything private below: no std::vector<EventPair> member joins the exported symbols)
+struct __attribute__((visibility("hidden"))) EventPair
+{
+  int kind;
+  hipEvent_t a, b;
+};
+
+struct ocean_fft
+{
+  int n = 0;
+  int logn = 0;
+  int device = 0;
+  int device_cus = 0;  // CUs of the device
+  int cus = 0;         // CU budget persistent grids are sized for (ocean_fft_set_cu_budget)
+  hipStream_t stream = nullptr;
+  float2* twiddles = nullptr;  // two-level table, see FftShape in device/fft.h
+  float2* tw2 = nullptr;       // the N/16-point table after it (fourstep_table sizes), else null
+  float2* twm = nullptr;       // the 4096-point table after that (ifft_pre_supported sizes), else null
+  float4* work = nullptr;      // column-first EncodeIFFT work image (the reference's workImage)
+  int work_images = 0;
+  size_t work_texels = 0;      // four-step EncodeIFFT (N = 16384): work slab of N x kFourStepSlab texels
+  size_t work_limit = (size_t)-1;  // ocean_debug_fft_work_limit: no work image / slab above this many bytes
+  float4* surf_atlas = nullptr;  // the surface consumer's repacked maps (launch_surface), grown on demand
+  size_t surf_atlas_texels = 0;
+};
+
+struct ocean_generator
+{
+  ocean_fft* fft = nullptr;
+  int cascades = 0;
+  int rank = 0, ranks = 1;  // slab decomposition of one grid (ranks == 1: whole grids, batched)
+  SlabGeom geom{};          // this rank's column slab [x0, x0 + w) and row slab width w
+  std::vector<ocean_settings> settings;
+  bool update_spectrum = true;  // src/Generator.h:72
+  float4* h0 = nullptr;         // [cascade][w/B][N][B] strip-blocked column slab (B = spectrum_block)
+  float4* inter = nullptr;      // [cascade][ranks][2][w/B][w][B] after the y pass (destination-block order)
+  float4* scratch = nullptr;    // [cascade][2][w][N] row-major, only when B == 1 (N = 16384)
+  float4* maps = nullptr;       // [cascade][2][w][N]: heightMap, displacementMap rows (row-major)
+  float* jac = nullptr;         // [cascade][w][N]
+  // half-spectrum path (ranks == 1, N = 1024 .. 4096; ocean_generator_set_half_spectrum)
+  bool half = false;
+  FrameParams frame{};    // the last column pass's per-cascade values (the row pass needs dk)
+  float2* hs = nullptr;    // pass-1 H scratch, half_hs_bytes(logn, device CUs)
+  float4* gab = nullptr;  // [cascade][strip][N][4]: y-transformed (H, kz H) for u >= 0 + Nyquist strip
+  float4* gcd = nullptr;  // (kz H/|k|, kz^2 H/|k|)
+  float2* ge = nullptr;   // H/|k|
+  float4* spec = nullptr; // [cascade][2][N]: the Nyquist-row term R
+  // half-spectrum paths of slabs (N >= 1024) and of whole grids of N = 8192 / 16384: the four-step
+  // column pass (gen4, N = 8192 / 16384, default) or the strip-dealt one (hsl)
+  bool hslab = false;
+  bool slab = false;  // created by ocean_generator_create_slab (also with ranks == 1)
+  HalfSlab hsl{};
+  Gen4Geom g4{};
+  float4* h0row = nullptr;                            // slabs: [cascade][N], row y = 0 of every column
+  float4* rm_ab = nullptr;                            // strip-dealt: row-major fields [cascade][w][kp] after the exchange
+  float4* rm_de = nullptr;
+  float2* rm_c = nullptr;
+  unsigned char* parts = nullptr;                     // four-step: step 1's output [field][cascade][N][lp]
+  unsigned char* xbuf = nullptr;                      // internal exchange buffer (ranks == 1, or null send/recv)
+  size_t xbuf_bytes = 0;
+  // fused re-seed frames (blocked half path): h0 evaluated inside pass 1, the h0 image left stale
+  void* seedc = nullptr;                 // device: one seed_consts record per cascade
+  std::vector<unsigned char> seedc_host; // what seedc holds
+  bool h0_stale = false;                 // the h0 image is not written yet (materialise_h0)
+  std::vector<ocean_settings> seed_settings;  // the settings the last fused re-seed evaluated
+  // N = 8192 / 16384: the four-step column pass writing destination-block order (launch_gen4_columns
+  // / _rows); off: the strip-dealt column pass + transposes. ocean_generator_set_four_step.
+  bool four_step = true;
+  int h0_block = 0;                          // strip width the h0 image was last written with
+  std::vector<ocean_settings> h0_settings;   // the settings it was written from
+  // the settings h0 was last seeded from (written or fused): a requested re-seed with the same
+  // h0 inputs (every field but `time`) would reproduce h0 bit for bit, so it is skipped
+  std::vector<ocean_settings> seeded;
+  bool memo_h0 = true;  // ocean_generator_set_h0_memo
+  // ocean_generator_slab_frame[_pipelined]: the library's own exchange buffers over RCCL, two slots
+  // (frame f in slot f % 2), the exchange on its own stream
+  unsigned char* xsend[2] = {nullptr, nullptr};
+  unsigned char* xrecv[2] = {nullptr, nullptr};
+  size_t xslot_bytes = 0;
+  hipStream_t comm_stream = nullptr;
+  hipEvent_t cols_done[2] = {nullptr, nullptr}, xchg_done[2] = {nullptr, nullptr}, rows_done[2] = {nullptr, nullptr};
+  bool rows_recorded[2] = {false, false};
+  int pending_slot = -1;           // slot whose row pass is still to be issued
+  FrameParams slot_frame[2]{};     // the column pass's per-cascade values of the frame in each slot
+  FoamParams slot_foam[2]{};       // and the settings' displacement its row pass uses
+  int64_t frames_issued = 0;
+  // the one-sided exchange bound to this generator (ocean_peers_create), and the event that orders its
+  // put stream after h0 writes on the generator's stream
+  ocean_peers* peers = nullptr;
+  hipEvent_t put_h0 = nullptr;
+  // Events, not stream handles: the peers' streams (and a caller's) may be destroyed or replaced
+  // between frames, and a recorded event stays valid (a stale `cols_stream`).
+  // cols_ev: the last strip-dealt / four-step column pass on its own stream (step 1 of a split put
+  // frame); the next column pass waits for it, on whatever stream (step 1 rewrites the parts; the
+  // strip-dealt pass reuses its H scratch); a no-op when both run on one stream.
+  // h0r_ev: the end of that pass's last h0 / h0row reader (the put stream's Nyquist-row kernel, which
+  // waited for step 1): every h0 / seed-constant write on the generator's stream waits for it.
+  hipEvent_t cols_ev = nullptr, h0r_ev = nullptr;
+  bool cols_ev_valid = false;
+  // ocean_generator_set_frame_overlap (blocked half path): frame f's column pass on `side` into field
+  // slot f % 2, beside frame f - 1's row pass on the generator's stream
+  bool overlap = false;
+  hipStream_t side = nullptr;
+  float4 *gab2 = nullptr, *gcd2 = nullptr, *spec2 = nullptr;
+  float2* ge2 = nullptr;
+  hipEvent_t ocols[2] = {nullptr, nullptr}, orows[2] = {nullptr, nullptr}, oh0 = nullptr;
+  bool orows_valid[2] = {false, false};
+  int oslot = 0;
+  bool h0_dirty = false;  // h0 (or the fused re-seed constants) written on the generator's stream since the side stream last waited
+  // the mip pyramid of the maps (ocean_generator_build_mips): [cascade][heightMap | displacementMap |
+  // jacobian chains], allocated on first use; fresh until the next call that rewrites the maps
+  float* mips = nullptr;
+  bool mips_fresh = false;
+  // the time derivative of the maps (ocean_generator_calculate_rates): [cascade][height-rate |
+  // displacement-rate][N * N], allocated on first use; fresh until the next column pass
+  float4* rates = nullptr;
+  bool rates_fresh = false;
+  // the bounds of the maps (ocean_generator_build_bounds): the table [cascade][18], then stage 1's partial
+  // rows (bounds_floats), allocated on first use; fresh until the next call that rewrites the maps
+  float* bounds = nullptr;
+  bool bounds_fresh = false;
+  bool profiling = false;
+  std::vector<EventPair> pending;
+  std::vector<hipEvent_t> pool;
+  double ms[4] = {0, 0, 0, 0};         // per kind: 0 h0, 1 column pass, 2 row pass, 3 the put inside 1
+  int64_t launches[4] = {0, 0, 0, 0};
+};
+
+// One error string per thread for the whole library, and the helpers that set it. Hidden: the library
+// exports what include/oceanfft.h and ocean_internal.h declare, nothing from here.
+#pragma GCC visibility push(hidden)
+
+inline thread_local std::string g_err;
+
+inline int fail(int code, const std::string& msg)
+{
+  g_err = msg;
+  return code;
+}
+
+inline int hip_fail(hipError_t e, const char* what)
+{
+  return fail(OCEAN_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+#define HIP_TRY(expr, what)                                                                        \
+  do                                                                                               \
+  {                                                                                                \
+    hipError_t e_ = (expr);                                                                        \
+    if (e_ != hipSuccess)                                                                          \
+      return hip_fail(e_, what);                                                                   \
+  } while (0)
+
+// After fused re-seed frames the h0 image is still to be written: writes it (ocean_capi.cpp)
+extern "C" int materialise_h0(ocean_generator* g);
+
+#pragma GCC visibility pop

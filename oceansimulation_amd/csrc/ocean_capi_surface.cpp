@@ -1,0 +1,694 @@
+// ocean_capi_surface.cpp — the part of the C ABI (include/oceanfft.h) that consumes a generator's maps:
+// the map getters, ocean_surface_sample / _query / _sample_plane, the mip pyramids and the *_lod requests,
+// the rate maps and ocean_surface_velocity, the bounds and ocean_surface_raycast, and the hull sets.
+// The plans and generators themselves are in ocean_capi.cpp; ocean_capi_internal.h has what both share.
+//
+// Every request checks its arguments in the order its contract lists them, and every message starts with
+// the entry point's name (`who`); the checks more than one entry point makes are written once, below.
+#include "oceanfft.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "device/mip_index.h"
+#include "ocean_capi_internal.h"
+#include "ocean_internal.h"
+
+// A step that failed has set the message: its status is the entry point's
+#define TRY(expr)                                                                                  \
+  do                                                                                               \
+  {                                                                                                \
+    const int rc_ = (expr);                                                                        \
+    if (rc_ != OCEAN_OK)                                                                           \
+      return rc_;                                                                                  \
+  } while (0)
+
+namespace
+{
+
+int alloc_fail(hipError_t e, const std::string& who)
+{
+  return fail(e == hipErrorOutOfMemory ? OCEAN_ERR_OOM : OCEAN_ERR_HIP, who + ": " + hipGetErrorString(e));
+}
+
+// A generator's buffer that is allocated on first use
+template <typename T>
+int alloc_once(T*& ptr, size_t bytes, const std::string& who)
+{
+  if (ptr)
+    return OCEAN_OK;
+  const hipError_t e = hipMalloc(&ptr, bytes);
+  if (e == hipSuccess)
+    return OCEAN_OK;
+  ptr = nullptr;
+  return alloc_fail(e, who);
+}
+
+// A generator that holds whole maps and, with `frame`, has calculated a frame
+int whole_maps(const ocean_generator* g, bool frame, const std::string& who)
+{
+  if (!g)
+    return fail(OCEAN_ERR_INVALID, who + ": null generator");
+  if (g->slab || g->ranks != 1)
+    return fail(OCEAN_ERR_INVALID, who + ": slab generators hold row slabs, not whole maps");
+  if (frame && g->frame.cascades != g->cascades)
+    return fail(OCEAN_ERR_INVALID, who + ": no frame calculated yet (ocean_generator_calculate)");
+  return OCEAN_OK;
+}
+
+int check_points(int64_t points, const float* positions, const float* out, const std::string& who)
+{
+  if (points < 0 || (points > 0 && (!positions || !out)))
+    return fail(OCEAN_ERR_INVALID, who + ": null positions/output or negative count");
+  return OCEAN_OK;
+}
+
+// The parameters of the query's fixed point
+int check_fixed_point(int iterations, float tolerance, const std::string& who)
+{
+  if (iterations < 0 || iterations > 64)
+    return fail(OCEAN_ERR_INVALID, who + ": iterations outside 0..64");
+  if (!(tolerance >= 0.0f) || !std::isfinite(tolerance))
+    return fail(OCEAN_ERR_INVALID, who + ": tolerance must be finite and >= 0");
+  return OCEAN_OK;
+}
+
+// A plane-mesh request: its SurfacePlane and vertex count
+int plane_request(const float camera[5], int res, const float* out, const std::string& who, SurfacePlane& plane,
+                  int64_t& points)
+{
+  if (!camera || !out || res < 1 || res > 46340)
+    return fail(OCEAN_ERR_INVALID, who + ": null camera/output or resolution outside 1..46340");
+  if (camera[3] == 0.0f && camera[4] == 0.0f)
+    return fail(OCEAN_ERR_INVALID, who + ": camera forward has no horizontal component");
+  plane = SurfacePlane{res, camera[0], camera[1], camera[2], camera[3], camera[4]};
+  points = (int64_t)(res + 1) * (res + 1);
+  return OCEAN_OK;
+}
+
+// Generator i of a request lacks the data `builder` makes (none / stale: the two wordings up to its name)
+int not_fresh(const std::string& who, int i, bool have, const char* none, const char* stale, const char* builder)
+{
+  return fail(OCEAN_ERR_INVALID, who + ": generator " + std::to_string(i) + (have ? stale : none) + " " + builder + ")");
+}
+
+}  // namespace
+
+extern "C" {
+
+float* ocean_generator_height_map(ocean_generator* g, int c)
+{
+  if (!g || c < 0 || c >= g->cascades)
+    return nullptr;
+  return reinterpret_cast<float*>(g->maps + (size_t)g->fft->n * g->geom.w * (2 * c));
+}
+
+float* ocean_generator_displacement_map(ocean_generator* g, int c)
+{
+  if (!g || c < 0 || c >= g->cascades)
+    return nullptr;
+  return reinterpret_cast<float*>(g->maps + (size_t)g->fft->n * g->geom.w * (2 * c + 1));
+}
+
+float* ocean_generator_jacobian_map(ocean_generator* g, int c)
+{
+  if (!g || c < 0 || c >= g->cascades)
+    return nullptr;
+  return g->jac + (size_t)g->fft->n * g->geom.w * c;
+}
+
+static int surface_params(ocean_generator* const* gens, const int* cascades, int count, SurfaceParams& p,
+                          ocean_fft*& fft, const char* who)
+{
+  if (!gens || !cascades || count < 1 || count > kMaxSurfaceCascades)
+    return fail(OCEAN_ERR_INVALID, std::string(who) + ": need 1..16 (generator, cascade) pairs");
+  p = SurfaceParams{};
+  p.count = count;
+  fft = nullptr;
+  for (int i = 0; i < count; i++)
+  {
+    ocean_generator* g = gens[i];
+    if (!g || cascades[i] < 0 || cascades[i] >= g->cascades)
+      return fail(OCEAN_ERR_INVALID, std::string(who) + ": null generator or cascade out of range");
+    if (g->ranks != 1)
+      return fail(OCEAN_ERR_INVALID, std::string(who) + ": slab generators hold row slabs, not whole maps");
+    if (!fft)
+      fft = g->fft;
+    else if (g->fft->n != fft->n)
+      return fail(OCEAN_ERR_INVALID, std::string(who) + ": all cascades must share one map size");
+    const int c = cascades[i];
+    p.c[i].height = reinterpret_cast<const float4*>(ocean_generator_height_map(g, c));
+    p.c[i].disp = reinterpret_cast<const float4*>(ocean_generator_displacement_map(g, c));
+    p.c[i].jac = ocean_generator_jacobian_map(g, c);
+    p.c[i].plane = g->settings[c].planeSize;
+    p.c[i].scale = g->settings[c].displacement;
+  }
+  p.n = fft->n;
+  p.atlas = nullptr;
+  return OCEAN_OK;
+}
+
+// The surface atlas of a request that uses one (surface_use_atlas / surface_query_use_atlas), owned by the
+// plan whose stream runs the request: requests on one plan are stream-ordered, so one buffer serves them all.
+static int surface_atlas(ocean_fft* fft, SurfaceParams& p, bool use, const char* who)
+{
+  if (!use)
+    return OCEAN_OK;
+  const size_t texels = surface_atlas_texels(p);
+  if (fft->surf_atlas_texels < texels)
+  {
+    if (fft->surf_atlas)
+    {
+      HIP_TRY(hipStreamSynchronize(fft->stream), who);  // an earlier request may still read the old one
+      HIP_TRY(hipFree(fft->surf_atlas), who);
+      fft->surf_atlas = nullptr;
+      fft->surf_atlas_texels = 0;
+    }
+    HIP_TRY(hipMalloc(&fft->surf_atlas, texels * sizeof(float4)), who);
+    fft->surf_atlas_texels = texels;
+  }
+  p.atlas = fft->surf_atlas;
+  return OCEAN_OK;
+}
+
+int ocean_surface_sample(ocean_generator* const* gens, const int* cascades, int count, const float* xz,
+                         int64_t points, float* out)
+{
+  SurfaceParams p;
+  ocean_fft* fft;
+  TRY(surface_params(gens, cascades, count, p, fft, "ocean_surface_sample"));
+  TRY(check_points(points, xz, out, "ocean_surface_sample"));
+  TRY(surface_atlas(fft, p, surface_use_atlas(p, points), "ocean_surface_sample"));
+  HIP_TRY(launch_surface(p, SurfacePlane{}, reinterpret_cast<const float2*>(xz), points, reinterpret_cast<float4*>(out),
+                         fft->stream, fft->cus),
+          "ocean_surface_sample");
+  return OCEAN_OK;
+}
+
+int ocean_surface_query(ocean_generator* const* gens, const int* cascades, int count, const float* xz, int64_t points,
+                        int iterations, float tolerance, float* out)
+{
+  SurfaceParams p;
+  ocean_fft* fft;
+  TRY(surface_params(gens, cascades, count, p, fft, "ocean_surface_query"));
+  TRY(check_fixed_point(iterations, tolerance, "ocean_surface_query"));
+  TRY(check_points(points, xz, out, "ocean_surface_query"));
+  TRY(surface_atlas(fft, p, surface_query_use_atlas(p, points, iterations), "ocean_surface_query"));
+  HIP_TRY(launch_surface_query(p, reinterpret_cast<const float2*>(xz), points, iterations, tolerance,
+                               reinterpret_cast<float4*>(out), fft->stream, fft->cus),
+          "ocean_surface_query");
+  return OCEAN_OK;
+}
+
+int ocean_surface_sample_plane(ocean_generator* const* gens, const int* cascades, int count, const float camera[5],
+                               int res, float* out)
+{
+  SurfaceParams p;
+  ocean_fft* fft;
+  SurfacePlane plane;
+  int64_t pts;
+  TRY(surface_params(gens, cascades, count, p, fft, "ocean_surface_sample_plane"));
+  TRY(plane_request(camera, res, out, "ocean_surface_sample_plane", plane, pts));
+  TRY(surface_atlas(fft, p, surface_use_atlas(p, pts), "ocean_surface_sample_plane"));
+  HIP_TRY(launch_surface(p, plane, nullptr, pts, reinterpret_cast<float4*>(out), fft->stream, fft->cus),
+          "ocean_surface_sample_plane");
+  return OCEAN_OK;
+}
+
+// ---- mip pyramid and footprint-aware sampling ----
+int ocean_generator_mip_levels(const ocean_generator* g) { return g ? g->fft->logn + 1 : 0; }
+
+int ocean_generator_build_mips(ocean_generator* g)
+{
+  TRY(whole_maps(g, false, "ocean_generator_build_mips"));
+  ocean_fft* f = g->fft;
+  TRY(alloc_once(g->mips, (size_t)g->cascades * mip_cascade_floats(f->n) * sizeof(float), "ocean_generator_build_mips"));
+  g->mips_fresh = false;
+  HIP_TRY(launch_build_mips(f->n, g->cascades, g->maps, g->jac, g->mips, f->stream), "ocean_generator_build_mips");
+  g->mips_fresh = true;
+  return OCEAN_OK;
+}
+
+// Level `level` of map `map` (0 heightMap, 1 displacementMap, 2 jacobian) of cascade c
+static float* generator_mip(ocean_generator* g, int c, int level, int map, const char* who)
+{
+  if (!g || c < 0 || c >= g->cascades)
+  {
+    fail(OCEAN_ERR_INVALID, std::string(who) + ": null generator or cascade out of range");
+    return nullptr;
+  }
+  if (level < 0 || level > g->fft->logn)
+  {
+    fail(OCEAN_ERR_INVALID, std::string(who) + ": level outside 0..log2(N)");
+    return nullptr;
+  }
+  if (level == 0)
+    return map == 0 ? ocean_generator_height_map(g, c)
+                    : (map == 1 ? ocean_generator_displacement_map(g, c) : ocean_generator_jacobian_map(g, c));
+  if (!g->mips)
+  {
+    fail(OCEAN_ERR_INVALID, std::string(who) + ": the pyramid was never built (ocean_generator_build_mips)");
+    return nullptr;
+  }
+  const int n = g->fft->n;
+  const size_t chain = mip_chain_texels(n), off = mip_level_offset(n, level);
+  float* base = g->mips + (size_t)c * mip_cascade_floats(n);
+  return map == 2 ? base + 8 * chain + off : base + (size_t)map * 4 * chain + 4 * off;
+}
+
+float* ocean_generator_height_mip(ocean_generator* g, int c, int level)
+{
+  return generator_mip(g, c, level, 0, "ocean_generator_height_mip");
+}
+
+float* ocean_generator_displacement_mip(ocean_generator* g, int c, int level)
+{
+  return generator_mip(g, c, level, 1, "ocean_generator_displacement_mip");
+}
+
+float* ocean_generator_jacobian_mip(ocean_generator* g, int c, int level)
+{
+  return generator_mip(g, c, level, 2, "ocean_generator_jacobian_mip");
+}
+
+// surface_params of a LOD call: also the chains, which must be built and not older than the maps
+static int surface_params_lod(ocean_generator* const* gens, const int* cascades, int count, SurfaceParams& p,
+                              ocean_fft*& fft, const char* who)
+{
+  TRY(surface_params(gens, cascades, count, p, fft, who));
+  for (int i = 0; i < count; i++)
+  {
+    ocean_generator* g = gens[i];
+    if (!g->mips || !g->mips_fresh)
+      return not_fresh(who, i, g->mips, " has no mip pyramid (call",
+                       " has a stale mip pyramid (its maps were rewritten since", "ocean_generator_build_mips");
+    const size_t chain = mip_chain_texels(fft->n);
+    const float* base = g->mips + (size_t)cascades[i] * mip_cascade_floats(fft->n);
+    p.c[i].height_mip = reinterpret_cast<const float4*>(base);
+    p.c[i].disp_mip = reinterpret_cast<const float4*>(base + 4 * chain);
+    p.c[i].jac_mip = base + 8 * chain;
+  }
+  return OCEAN_OK;
+}
+
+int ocean_surface_sample_lod(ocean_generator* const* gens, const int* cascades, int count, const float* xzf,
+                             int64_t points, float* out)
+{
+  SurfaceParams p;
+  ocean_fft* fft;
+  TRY(surface_params_lod(gens, cascades, count, p, fft, "ocean_surface_sample_lod"));
+  TRY(check_points(points, xzf, out, "ocean_surface_sample_lod"));
+  HIP_TRY(launch_surface_lod(p, SurfacePlane{}, xzf, points, reinterpret_cast<float4*>(out), fft->stream, fft->cus),
+          "ocean_surface_sample_lod");
+  return OCEAN_OK;
+}
+
+int ocean_surface_sample_plane_lod(ocean_generator* const* gens, const int* cascades, int count, const float camera[5],
+                                   int res, float* out)
+{
+  SurfaceParams p;
+  ocean_fft* fft;
+  SurfacePlane plane;
+  int64_t pts;
+  TRY(surface_params_lod(gens, cascades, count, p, fft, "ocean_surface_sample_plane_lod"));
+  TRY(plane_request(camera, res, out, "ocean_surface_sample_plane_lod", plane, pts));
+  HIP_TRY(launch_surface_lod(p, plane, nullptr, pts, reinterpret_cast<float4*>(out), fft->stream, fft->cus),
+          "ocean_surface_sample_plane_lod");
+  return OCEAN_OK;
+}
+
+// ---- time derivative of the maps and the velocity of water particles ----
+int ocean_generator_calculate_rates(ocean_generator* g)
+{
+  TRY(whole_maps(g, true, "ocean_generator_calculate_rates"));
+  ocean_fft* f = g->fft;
+  const size_t nn = (size_t)f->n * f->n;
+  TRY(alloc_once(g->rates, (size_t)g->cascades * 2 * nn * sizeof(float4), "ocean_generator_calculate_rates"));
+  g->rates_fresh = false;
+  // after fused re-seed frames the h0 image is still to be written: on the generator's stream, so with
+  // frame overlap the next column pass waits for it (h0_dirty, set by the write); the memo keeps its inputs
+  TRY(materialise_h0(g));
+  HIP_TRY(launch_rates_pack(f->logn, g->frame, g->h0_block, g->h0, g->rates, f->stream, f->cus),
+          "ocean_generator_calculate_rates");
+  TRY(ocean_fft_encode_ifft_batch(f, reinterpret_cast<float*>(g->rates), 2 * g->cascades));
+  g->rates_fresh = true;
+  return OCEAN_OK;
+}
+
+// Image `image` (0 height-rate, 1 displacement-rate) of cascade c
+static float* generator_rate_map(ocean_generator* g, int c, int image, const char* who)
+{
+  if (!g || c < 0 || c >= g->cascades)
+  {
+    fail(OCEAN_ERR_INVALID, std::string(who) + ": null generator or cascade out of range");
+    return nullptr;
+  }
+  if (!g->rates)
+  {
+    fail(OCEAN_ERR_INVALID, std::string(who) + ": the rates were never calculated (ocean_generator_calculate_rates)");
+    return nullptr;
+  }
+  return reinterpret_cast<float*>(g->rates + (size_t)g->fft->n * g->fft->n * (2 * c + image));
+}
+
+float* ocean_generator_height_rate_map(ocean_generator* g, int c)
+{
+  return generator_rate_map(g, c, 0, "ocean_generator_height_rate_map");
+}
+
+float* ocean_generator_displacement_rate_map(ocean_generator* g, int c)
+{
+  return generator_rate_map(g, c, 1, "ocean_generator_displacement_rate_map");
+}
+
+// The rate maps of a request's cascades, which must be calculated and not older than the maps
+static int surface_rates(ocean_generator* const* gens, const int* cascades, int count, const ocean_fft* fft,
+                         SurfaceRates& r, const char* who)
+{
+  r = SurfaceRates{};
+  for (int i = 0; i < count; i++)
+  {
+    ocean_generator* g = gens[i];
+    if (!g->rates || !g->rates_fresh)
+      return not_fresh(who, i, g->rates, " has no rates (call", " has stale rates (a frame was calculated since",
+                       "ocean_generator_calculate_rates");
+    const size_t nn = (size_t)fft->n * fft->n;
+    r.height[i] = g->rates + nn * (2 * cascades[i]);
+    r.disp[i] = g->rates + nn * (2 * cascades[i] + 1);
+  }
+  return OCEAN_OK;
+}
+
+int ocean_surface_velocity(ocean_generator* const* gens, const int* cascades, int count, const float* xz,
+                           int64_t points, float* out)
+{
+  SurfaceParams p;
+  ocean_fft* fft;
+  SurfaceRates r;
+  TRY(surface_params(gens, cascades, count, p, fft, "ocean_surface_velocity"));
+  TRY(surface_rates(gens, cascades, count, fft, r, "ocean_surface_velocity"));
+  TRY(check_points(points, xz, out, "ocean_surface_velocity"));
+  HIP_TRY(launch_surface_velocity(p, r, reinterpret_cast<const float2*>(xz), points, reinterpret_cast<float4*>(out),
+                                  fft->stream, fft->cus),
+          "ocean_surface_velocity");
+  return OCEAN_OK;
+}
+
+// ---- bounds of the maps and ray casting against the displaced surface ----
+int ocean_generator_build_bounds(ocean_generator* g)
+{
+  TRY(whole_maps(g, true, "ocean_generator_build_bounds"));
+  ocean_fft* f = g->fft;
+  TRY(alloc_once(g->bounds, bounds_floats(f->n, g->cascades) * sizeof(float), "ocean_generator_build_bounds"));
+  g->bounds_fresh = false;
+  HIP_TRY(launch_build_bounds(f->n, g->cascades, g->maps, g->jac, g->bounds, f->stream, f->cus),
+          "ocean_generator_build_bounds");
+  g->bounds_fresh = true;
+  return OCEAN_OK;
+}
+
+// The table of a generator whose bounds are built and not older than its maps, else null with a message
+static const float* generator_bounds(ocean_generator* g, const char* who)
+{
+  if (!g)
+  {
+    fail(OCEAN_ERR_INVALID, std::string(who) + ": null generator");
+    return nullptr;
+  }
+  if (!g->bounds || !g->bounds_fresh)
+  {
+    fail(OCEAN_ERR_INVALID, std::string(who) + (g->bounds ? ": the bounds are stale (the maps were rewritten since"
+                                                           : ": the bounds were never built (call") +
+                                " ocean_generator_build_bounds)");
+    return nullptr;
+  }
+  return g->bounds;
+}
+
+const float* ocean_generator_bounds_device(ocean_generator* g)
+{
+  return generator_bounds(g, "ocean_generator_bounds_device");
+}
+
+int ocean_generator_bounds(ocean_generator* g, int cascade, float out[18])
+{
+  const float* table = generator_bounds(g, "ocean_generator_bounds");
+  if (!table)
+    return OCEAN_ERR_INVALID;
+  if (cascade < 0 || cascade >= g->cascades || !out)
+    return fail(OCEAN_ERR_INVALID, "ocean_generator_bounds: cascade out of range or null output");
+  HIP_TRY(hipMemcpyAsync(out, table + (size_t)cascade * 18, 18 * sizeof(float), hipMemcpyDeviceToHost, g->fft->stream),
+          "ocean_generator_bounds");
+  HIP_TRY(hipStreamSynchronize(g->fft->stream), "ocean_generator_bounds");
+  return OCEAN_OK;
+}
+
+int ocean_surface_raycast(ocean_generator* const* gens, const int* cascades, int count, const float* rays,
+                          int64_t n_rays, float step, int max_steps, int refine, int iterations, float tolerance,
+                          float slope, float pad, float* out)
+{
+  // the scalar rules first: they need no generator
+  if (!gens || !cascades)
+    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: null gens / cascades");
+  if (!std::isfinite(step) || !(step > 0.0f))
+    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: step must be finite and > 0");
+  if (max_steps < 1 || max_steps > 65535)
+    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: max_steps outside 1..65535");
+  if (refine < 0 || refine > 32)
+    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: refine outside 0..32");
+  TRY(check_fixed_point(iterations, tolerance, "ocean_surface_raycast"));
+  if (!(pad >= 0.0f) || !std::isfinite(pad))
+    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: pad must be finite and >= 0");
+  if (!(slope >= 0.0f))
+    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: slope must be >= 0 (+inf: fixed steps)");
+  if (n_rays < 0 || (n_rays > 0 && (!rays || !out)))
+    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: null rays/output or negative count");
+  SurfaceParams p;
+  ocean_fft* fft;
+  TRY(surface_params(gens, cascades, count, p, fft, "ocean_surface_raycast"));
+  RaycastParams r{};
+  for (int i = 0; i < count; i++)
+  {
+    ocean_generator* g = gens[i];
+    if (!g->bounds || !g->bounds_fresh)
+      return not_fresh("ocean_surface_raycast", i, g->bounds, " has no bounds (call",
+                       " has stale bounds (its maps were rewritten since", "ocean_generator_build_bounds");
+    r.bounds[i] = g->bounds + (size_t)cascades[i] * 18;
+  }
+  r.step = step;
+  r.max_steps = max_steps;
+  r.refine = refine;
+  r.iterations = iterations;
+  r.tolerance = tolerance;
+  r.slope = slope;
+  r.pad = pad;
+  HIP_TRY(launch_surface_raycast(p, r, reinterpret_cast<const float4*>(rays), n_rays, reinterpret_cast<float4*>(out),
+                                 fft->stream, fft->cus),
+          "ocean_surface_raycast");
+  return OCEAN_OK;
+}
+
+// ---- hull sets: net wave force and torque on batches of floating bodies ----
+// Consecutive bodies of at most 32 points share a wave (tools/hulls_bench.py times both)
+static bool g_hulls_pack = true;
+
+int ocean_debug_hulls_packing(int enable)
+{
+  g_hulls_pack = enable != 0;
+  return OCEAN_OK;
+}
+
+struct ocean_hulls
+{
+  ocean_fft* fft = nullptr;
+  int bodies = 0;
+  int64_t instance_points = 0;
+  int items = 0;    // 64-point tiles
+  int n_folds = 0;  // bodies of more than one tile
+  float4* points = nullptr;
+  HullTile* tiles = nullptr;
+  HullBody* body_table = nullptr;
+  HullFold* folds = nullptr;
+  float4* partial = nullptr;  // one 8-float partial per tile of a body in `folds`
+};
+
+int ocean_hulls_destroy(ocean_hulls* h)
+{
+  if (!h)
+    return OCEAN_OK;
+  if (h->fft)
+    (void)hipStreamSynchronize(h->fft->stream);
+  for (void* p : {(void*)h->points, (void*)h->tiles, (void*)h->body_table, (void*)h->folds, (void*)h->partial})
+    if (p)
+      (void)hipFree(p);
+  delete h;
+  return OCEAN_OK;
+}
+
+int ocean_hulls_create(ocean_hulls** out, ocean_fft* fft, const float* points, int64_t n_points, const int32_t* ranges,
+                       int bodies)
+{
+  if (!out || !fft || !points || !ranges)
+    return fail(OCEAN_ERR_INVALID, "ocean_hulls_create: null argument");
+  *out = nullptr;
+  if (bodies < 1 || bodies > 1048576)
+    return fail(OCEAN_ERR_INVALID, "ocean_hulls_create: bodies outside 1..1048576");
+  if (n_points < 1)
+    return fail(OCEAN_ERR_INVALID, "ocean_hulls_create: no points");
+  int64_t n_tiles = 0, instance_points = 0;
+  for (int b = 0; b < bodies; b++)
+  {
+    const int64_t first = ranges[2 * b], count = ranges[2 * b + 1];
+    if (count < 1 || count > 262144)
+      return fail(OCEAN_ERR_INVALID, "ocean_hulls_create: body " + std::to_string(b) + " has a count outside 1..262144");
+    if (first < 0 || first + count > n_points)
+      return fail(OCEAN_ERR_INVALID, "ocean_hulls_create: the range of body " + std::to_string(b) + " leaves the points");
+    n_tiles += (count + kHullTilePoints - 1) / kHullTilePoints;
+    instance_points += count;
+  }
+  for (int64_t i = 0; i < n_points; i++)
+  {
+    const float* l = points + 8 * i;
+    for (int k = 0; k < 8; k++)
+      if (!std::isfinite(l[k]))
+        return fail(OCEAN_ERR_INVALID, "ocean_hulls_create: point " + std::to_string(i) + " has a non-finite field");
+    if (l[3] < 0.0f || !(l[4] > 0.0f) || l[5] < 0.0f || l[6] < 0.0f)
+      return fail(OCEAN_ERR_INVALID, "ocean_hulls_create: point " + std::to_string(i) +
+                                         " needs volume >= 0, half_height > 0 and drag coefficients >= 0");
+  }
+  if (n_tiles > INT32_MAX)
+    return fail(OCEAN_ERR_OOM, "ocean_hulls_create: more than 2^31 - 1 tiles of 64 points");
+
+  // the work items, in the order of the bodies: a body's 64-point tiles, or one packed tile for a run of
+  // consecutive small bodies with one segment size; point_out rows in the order of the bodies
+  std::vector<HullTile> tiles;
+  std::vector<HullBody> table((size_t)bodies);
+  std::vector<HullFold> folds;
+  tiles.reserve((size_t)n_tiles);
+  int slot = 0;
+  auto segment = [&](int b) {  // the power of two body b's points fit in
+    int seg = 1;
+    while (seg < ranges[2 * b + 1])
+      seg *= 2;
+    return seg;
+  };
+  int64_t rows = 0;
+  for (int b = 0; b < bodies; b++)
+  {
+    table[b] = HullBody{rows, ranges[2 * b], ranges[2 * b + 1]};
+    rows += ranges[2 * b + 1];
+  }
+  for (int b = 0; b < bodies; b++)
+  {
+    const int first = ranges[2 * b], count = ranges[2 * b + 1];
+    const int seg = segment(b);
+    int run = 1;  // consecutive bodies with this segment size, as many as fit a wave
+    while (g_hulls_pack && seg <= kHullTilePoints / 2 && run < kHullTilePoints / seg && b + run < bodies &&
+           segment(b + run) == seg)
+      run++;
+    if (run > 1)
+    {
+      HullTile t{};
+      t.count = run;
+      t.body = b;
+      t.slot = -1;
+      t.seg = seg;
+      tiles.push_back(t);
+      b += run - 1;
+      continue;
+    }
+    const int64_t offset = table[b].offset;
+    const int nt = (count + kHullTilePoints - 1) / kHullTilePoints;
+    if (nt > 1)
+      folds.push_back(HullFold{b, slot, nt, 0});
+    for (int j = 0; j < nt; j++)
+      tiles.push_back(HullTile{offset + (int64_t)j * kHullTilePoints, first + j * kHullTilePoints,
+                               std::min(kHullTilePoints, count - j * kHullTilePoints), b, nt > 1 ? slot + j : -1});
+    if (nt > 1)
+      slot += nt;
+  }
+
+  auto* h = new ocean_hulls();
+  h->fft = fft;
+  h->bodies = bodies;
+  h->instance_points = instance_points;
+  h->items = (int)tiles.size();
+  h->n_folds = (int)folds.size();
+  hipError_t e = hipMalloc(&h->points, (size_t)n_points * 2 * sizeof(float4));
+  if (e == hipSuccess)
+    e = hipMalloc(&h->tiles, tiles.size() * sizeof(HullTile));
+  if (e == hipSuccess)
+    e = hipMalloc(&h->body_table, table.size() * sizeof(HullBody));
+  if (e == hipSuccess && !folds.empty())
+    e = hipMalloc(&h->folds, folds.size() * sizeof(HullFold));
+  if (e == hipSuccess && slot > 0)
+    e = hipMalloc(&h->partial, (size_t)slot * 2 * sizeof(float4));
+  // synchronous copies from the caller's and these pageable buffers: complete on return
+  if (e == hipSuccess)
+    e = hipMemcpy(h->points, points, (size_t)n_points * 2 * sizeof(float4), hipMemcpyHostToDevice);
+  if (e == hipSuccess)
+    e = hipMemcpy(h->tiles, tiles.data(), tiles.size() * sizeof(HullTile), hipMemcpyHostToDevice);
+  if (e == hipSuccess)
+    e = hipMemcpy(h->body_table, table.data(), table.size() * sizeof(HullBody), hipMemcpyHostToDevice);
+  if (e == hipSuccess && !folds.empty())
+    e = hipMemcpy(h->folds, folds.data(), folds.size() * sizeof(HullFold), hipMemcpyHostToDevice);
+  if (e != hipSuccess)
+  {
+    h->fft = nullptr;
+    ocean_hulls_destroy(h);
+    return alloc_fail(e, "ocean_hulls_create");
+  }
+  *out = h;
+  return OCEAN_OK;
+}
+
+int ocean_hulls_bodies(const ocean_hulls* h) { return h ? h->bodies : 0; }
+
+int64_t ocean_hulls_instance_points(const ocean_hulls* h) { return h ? h->instance_points : 0; }
+
+int ocean_hulls_loads(ocean_hulls* h, ocean_generator* const* gens, const int* cascades, int count, const float* poses,
+                      float rho_g, int iterations, float tolerance, int water_velocity, float* loads, float* point_out)
+{
+  if (!h)
+    return fail(OCEAN_ERR_INVALID, "ocean_hulls_loads: null hull set");
+  SurfaceParams p;
+  ocean_fft* fft;
+  TRY(surface_params(gens, cascades, count, p, fft, "ocean_hulls_loads"));
+  if (gens[0]->fft != h->fft)
+    return fail(OCEAN_ERR_INVALID, "ocean_hulls_loads: the first generator is on another plan than the hull set");
+  TRY(check_fixed_point(iterations, tolerance, "ocean_hulls_loads"));
+  if (!(rho_g >= 0.0f) || !std::isfinite(rho_g))
+    return fail(OCEAN_ERR_INVALID, "ocean_hulls_loads: rho_g must be finite and >= 0");
+  if (water_velocity != 0 && water_velocity != 1)
+    return fail(OCEAN_ERR_INVALID, "ocean_hulls_loads: water_velocity must be 0 or 1");
+  if (!poses || !loads)
+    return fail(OCEAN_ERR_INVALID, "ocean_hulls_loads: null poses/loads");
+  SurfaceRates r{};
+  if (water_velocity)
+    TRY(surface_rates(gens, cascades, count, fft, r, "ocean_hulls_loads"));
+  const bool atlas = surface_query_use_atlas(p, h->instance_points, iterations);
+  TRY(surface_atlas(fft, p, atlas, "ocean_hulls_loads"));
+  if (atlas)
+    launch_surface_atlas(p, fft->stream, fft->cus);
+  HullCall call{};
+  call.points = h->points;
+  call.tiles = h->tiles;
+  call.bodies = h->body_table;
+  call.poses = poses;
+  call.loads = reinterpret_cast<float4*>(loads);
+  call.partial = h->partial;
+  call.point_out = reinterpret_cast<float4*>(point_out);
+  call.items = h->items;
+  call.iterations = iterations;
+  call.tolerance = tolerance;
+  call.rho_g = rho_g;
+  HIP_TRY(launch_hulls_loads(p, r, water_velocity != 0, call, h->folds, h->n_folds, fft->stream, fft->cus),
+          "ocean_hulls_loads");
+  return OCEAN_OK;
+}
+
+}  // extern "C"

@@ -1,8 +1,9 @@
 // ocean_kernels.hip — gfx950 device code of the ocean hot path, core translation unit: h0 seeding
-// (generateSpectrum), the debug Hash, the Nyquist-row term of the half-spectrum paths and the surface
-// consumer, with their launchers and the host-side size helpers. The frame passes live in
-// launch_half.hip (whole grids of 1024 .. 4096), launch_slab.hip (slabs, and 8192 / 16384) and
-// launch_fft.hip (standalone EncodeIFFT and the full-spectrum path); their kernels in device/k_*.h.
+// (generateSpectrum), the debug Hash, the Nyquist-row term of the half-spectrum paths and the peer
+// signals of the one-sided exchange, with their launchers and the host-side size helpers. The frame
+// passes live in launch_half.hip (whole grids of 1024 .. 4096), launch_slab.hip (slabs, and 8192 / 16384)
+// and launch_fft.hip (standalone EncodeIFFT and the full-spectrum path), the surface consumer in
+// launch_surface.hip and the launch_*.hip of its later requests; their kernels in device/k_*.h.
 //
 // Reference semantics (paths relative to the reference root):
 //   spectrum seeding      resources/spectrum.compute:38-172   (generateSpectrum)
@@ -27,9 +28,7 @@
 #include "device/fft.h"
 #include "device/grid.h"
 #include "device/memory.h"
-#include "device/mip_index.h"
 #include "device/spectrum.h"
-#include "device/surface_sample.h"
 
 namespace oceanfft
 {
@@ -238,294 +237,6 @@ hipError_t launch_peer_wait(const PeerWait& w, hipStream_t stream)
 }
 
 // ------------------------------------------------------------------------------------------------
-// Surface consumer: resources/waveShader.glsl evaluated per mesh vertex on the
-// generator's maps. Vertex stage (:101-110): each cascade samples heightMap/displacementMap at
-// pos.xz / planeSize, the position the earlier cascades already displaced, and adds
-// (scale * Dx, h, scale * Dz). Fragment stage at the displaced position (:127-144): summed slopes
-// -> normal, averaged Jacobian. Sampling is GL_LINEAR + GL_REPEAT (src/Generator.cpp:116-119) in
-// fp32 with the specification's weights, unfused and with correctly rounded division / sqrt, so
-// the oracle restatement (oracle_surface_vertex) is matched bit for bit. Memory: the maps of a
-// scene (3 x 256^2 x 36 B) live in L2; per vertex 32 B are written.
-// ------------------------------------------------------------------------------------------------
-// The taps, the filtered channel / texel and the vertex stage are in device/surface_sample.h (shared with
-// the hull loads, device/k_hulls.h).
-
-// the surface atlas of the cascades' maps (SurfaceParams::atlas)
-__global__ __launch_bounds__(256) void k_surface_atlas(SurfaceParams p)
-{
-  const int nn = p.n * p.n;
-  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < p.count * nn; idx += gridDim.x * blockDim.x)
-  {
-    const int c = idx / nn, t = idx - c * nn;
-    const float4 h = p.c[c].height[t], d = p.c[c].disp[t];
-    p.atlas[(size_t)(2 * c) * nn + t] = make_float4(h.x, h.w, d.x, 0.0f);
-    p.atlas[(size_t)(2 * c + 1) * nn + t] = make_float4(h.y, h.z, d.y, d.z);
-  }
-}
-
-// The fragment stage at the displaced position is there too (shared with device/k_raycast.h).
-
-template <bool ATLAS>
-__global__ __launch_bounds__(256) void k_surface(SurfaceParams p, SurfacePlane plane, const float2* __restrict__ xz,
-                                                 int64_t count, float4* __restrict__ out)
-{
-#pragma clang fp contract(off)
-  float tx = 0.0f, tz = 0.0f, cam_y = 0.0f;
-  if (plane.res > 0)
-  {
-    // turnDir = normalize(forward.xz) rotated by 45 degrees (waveShader.glsl:84-88)
-    const float fl = sqrtf(plane.fwd_x * plane.fwd_x + plane.fwd_z * plane.fwd_z);
-    const float tx0 = plane.fwd_x / fl, tz0 = plane.fwd_z / fl;
-    tx = (tx0 - tz0) * 0.70711f;
-    tz = (tx0 + tz0) * 0.70711f;
-    cam_y = fmaxf(plane.cam_y, 10.0f);
-  }
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < count;
-       idx += (int64_t)gridDim.x * blockDim.x)
-  {
-    float px, pz;
-    if (plane.res > 0)
-    {
-      // plane vertex (src/Renderer.cpp:18), + (15, 0, 15), rotate, distance scale, camera offset
-      const int side = plane.res + 1;
-      const int i = (int)(idx % side), j = (int)(idx / side);
-      const float x = -20.0f + 40.0f * (float)i / (float)plane.res + 15.0f;
-      const float z = -20.0f + 40.0f * (float)j / (float)plane.res + 15.0f;
-      float rx = tx * x - tz * z, rz = x * tz + z * tx;
-      const float len = sqrtf(rx * rx + rz * rz);
-      const float k = powf(fmaxf(len, 1.0f), 1.2f) * cam_y * 0.04f;
-      px = rx * k + plane.cam_x;
-      pz = rz * k + plane.cam_z;
-    }
-    else
-    {
-      const float2 q = xz[idx];
-      px = q.x;
-      pz = q.y;
-    }
-    float py = 0.0f;
-    surface_vertex_stage<ATLAS>(p, px, py, pz);
-    const float4 f = surface_fragment_stage<ATLAS>(p, px, pz);
-    out[2 * idx] = make_float4(px, py, pz, f.w);
-    out[2 * idx + 1] = make_float4(f.x, f.y, f.z, 0.0f);
-  }
-}
-
-// The inverse direction (ocean_surface_query, include/oceanfft.h): the base point p whose displaced
-// position V(p).xz is the query q, by the plain fixed point p <- p + (q - V(p).xz), at most `iterations`
-// steps, a lane stopping once max|q - V(p).xz| <= tolerance. Only the vertex stage is iterated (one
-// 16-B load per tap and cascade from the atlas, three dwords from the maps); the fragment stage runs
-// once, at the last V(p). Lanes of a wave stop at different steps: the wave runs until its last lane
-// is done. |a| > tolerance is written as !(|a| <= tolerance), so a NaN residual keeps iterating and
-// reaches slot 7 instead of passing for converged.
-template <bool ATLAS>
-__global__ __launch_bounds__(256) void k_surface_query(SurfaceParams p, const float2* __restrict__ xz, int64_t count,
-                                                       int iterations, float tolerance, float4* __restrict__ out)
-{
-#pragma clang fp contract(off)
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < count;
-       idx += (int64_t)gridDim.x * blockDim.x)
-  {
-    const float2 q = xz[idx];
-    float bx = q.x, bz = q.y;  // the base point p
-    float vx = bx, vy = 0.0f, vz = bz;
-    surface_vertex_stage<ATLAS>(p, vx, vy, vz);
-    for (int it = 0; it < iterations; it++)
-    {
-      const float rx = q.x - vx, rz = q.y - vz;
-      if (fabsf(rx) <= tolerance && fabsf(rz) <= tolerance)
-        break;
-      bx += rx;
-      bz += rz;
-      vx = bx;
-      vy = 0.0f;
-      vz = bz;
-      surface_vertex_stage<ATLAS>(p, vx, vy, vz);
-    }
-    const float4 f = surface_fragment_stage<ATLAS>(p, vx, vz);
-    const float ex = fabsf(q.x - vx), ez = fabsf(q.y - vz);
-    out[2 * idx] = make_float4(bx, vy, bz, f.w);
-    out[2 * idx + 1] = make_float4(f.x, f.y, f.z, (ex >= ez || ex != ex) ? ex : ez);
-  }
-}
-
-// The velocity of the water particle whose rest position is the base point (ocean_surface_velocity,
-// include/oceanfft.h): d/dt of the vertex stage V(p). Cascade c samples at the position the earlier
-// cascades displaced, which itself moves with the velocity u accumulated so far, so its share is the
-// rate maps' sample plus grad(field) . u, the gradients being map channels (dDx/dz = dDz/dx). The
-// position advances exactly as in surface_vertex_stage (same taps, weights and sums), so slots 0-2 are
-// ocean_surface_sample's bits. Per cascade and tap two 16-B loads (the maps) and three dwords (the rates).
-__global__ __launch_bounds__(256) void k_surface_velocity(SurfaceParams p, SurfaceRates r, const float2* __restrict__ xz,
-                                                          int64_t count, float4* __restrict__ out)
-{
-#pragma clang fp contract(off)
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < count;
-       idx += (int64_t)gridDim.x * blockDim.x)
-  {
-    const float2 q = xz[idx];
-    float px = q.x, py = 0.0f, pz = q.y;
-    float ux = 0.0f, uy = 0.0f, uz = 0.0f;
-    surface_particle_velocity(p, r, px, py, pz, ux, uy, uz);
-    out[2 * idx] = make_float4(px, py, pz, 0.0f);
-    out[2 * idx + 1] = make_float4(ux, uy, uz, 0.0f);
-  }
-}
-
-// Footprint-aware sampling (ocean_surface_sample_lod, include/oceanfft.h): a sample whose neighbours sit
-// `footprint` metres away covers r = footprint * N / planeSize texels of cascade c's level 0, so it reads
-// level l = floor(log2 r) and level l + 1 of the mip pyramid (device/k_mips.h) and blends them by
-// f = r / 2^l - 1 in [0, 1): linear in the footprint, continuous across levels. l is r's exponent field
-// and f is exact (a scaling by a power of two and a subtraction in [1, 2)), so no log2f is involved.
-struct SurfaceLod
-{
-  int l;
-  float f;
-};
-
-__device__ __forceinline__ SurfaceLod surface_lod(float footprint, int n, int top, float plane)
-{
-#pragma clang fp contract(off)
-  const float r = (footprint * (float)n) / plane;
-  if (!(r >= 1.0f))  // also NaN
-    return SurfaceLod{0, 0.0f};
-  if (r >= (float)(1 << top))  // also +inf
-    return SurfaceLod{top, 0.0f};
-  const int l = (int)(__float_as_uint(r) >> 23) - 127;
-  return SurfaceLod{l, r * __uint_as_float((uint32_t)(127 - l) << 23) - 1.0f};
-}
-
-// Level l of a map whose chain (levels >= 1) is `mip`, CH floats per texel
-template <int CH>
-__device__ __forceinline__ const float* surface_level(const void* map, const void* mip, int n, int l)
-{
-  return l == 0 ? static_cast<const float*>(map) : static_cast<const float*>(mip) + mip_level_offset(n, l) * CH;
-}
-
-__device__ __forceinline__ float lod_blend(float a, float b, float f)
-{
-#pragma clang fp contract(off)
-  return a + f * (b - a);
-}
-
-// surface_vertex_stage with cascade c's (l, f): A = level l, B = level l + 1 (read only when f != 0;
-// l == top has f == 0)
-__device__ __forceinline__ void surface_vertex_stage_lod(const SurfaceParams& p, int top, float footprint, float& px,
-                                                         float& py, float& pz)
-{
-#pragma clang fp contract(off)
-  for (int c = 0; c < p.count; c++)
-  {
-    const SurfaceLod lod = surface_lod(footprint, p.n, top, p.c[c].plane);
-    const float u = px / p.c[c].plane, v = pz / p.c[c].plane;
-    const LinearTaps k = linear_repeat_taps(p.n >> lod.l, u, v);
-    const float* hm = surface_level<4>(p.c[c].height, p.c[c].height_mip, p.n, lod.l);
-    const float* dm = surface_level<4>(p.c[c].disp, p.c[c].disp_mip, p.n, lod.l);
-    float h = linear_channel<4>(hm, k, 0), dx = linear_channel<4>(hm, k, 3), dz = linear_channel<4>(dm, k, 0);
-    if (lod.f != 0.0f)
-    {
-      const LinearTaps kb = linear_repeat_taps(p.n >> (lod.l + 1), u, v);
-      const float* hb = surface_level<4>(p.c[c].height, p.c[c].height_mip, p.n, lod.l + 1);
-      const float* db = surface_level<4>(p.c[c].disp, p.c[c].disp_mip, p.n, lod.l + 1);
-      h = lod_blend(h, linear_channel<4>(hb, kb, 0), lod.f);
-      dx = lod_blend(dx, linear_channel<4>(hb, kb, 3), lod.f);
-      dz = lod_blend(dz, linear_channel<4>(db, kb, 0), lod.f);
-    }
-    px += p.c[c].scale * dx;
-    py += h;
-    pz += p.c[c].scale * dz;
-  }
-}
-
-// surface_fragment_stage with the same (l, f) per cascade, at the displaced position
-__device__ __forceinline__ float4 surface_fragment_stage_lod(const SurfaceParams& p, int top, float footprint, float px,
-                                                             float pz)
-{
-#pragma clang fp contract(off)
-  float d[4] = {0.0f, 0.0f, 0.0f, 0.0f}, jac = 0.0f;
-  for (int c = 0; c < p.count; c++)
-  {
-    const SurfaceLod lod = surface_lod(footprint, p.n, top, p.c[c].plane);
-    const float u = px / p.c[c].plane, v = pz / p.c[c].plane;
-    const LinearTaps k = linear_repeat_taps(p.n >> lod.l, u, v);
-    const float* hm = surface_level<4>(p.c[c].height, p.c[c].height_mip, p.n, lod.l);
-    const float* dm = surface_level<4>(p.c[c].disp, p.c[c].disp_mip, p.n, lod.l);
-    const float* jm = surface_level<1>(p.c[c].jac, p.c[c].jac_mip, p.n, lod.l);
-    float hx = linear_channel<4>(hm, k, 1), dxx = linear_channel<4>(dm, k, 1), hz = linear_channel<4>(hm, k, 2),
-          dzz = linear_channel<4>(dm, k, 2), j = linear_channel<1>(jm, k, 0);
-    if (lod.f != 0.0f)
-    {
-      const LinearTaps kb = linear_repeat_taps(p.n >> (lod.l + 1), u, v);
-      const float* hb = surface_level<4>(p.c[c].height, p.c[c].height_mip, p.n, lod.l + 1);
-      const float* db = surface_level<4>(p.c[c].disp, p.c[c].disp_mip, p.n, lod.l + 1);
-      const float* jb = surface_level<1>(p.c[c].jac, p.c[c].jac_mip, p.n, lod.l + 1);
-      hx = lod_blend(hx, linear_channel<4>(hb, kb, 1), lod.f);
-      dxx = lod_blend(dxx, linear_channel<4>(db, kb, 1), lod.f);
-      hz = lod_blend(hz, linear_channel<4>(hb, kb, 2), lod.f);
-      dzz = lod_blend(dzz, linear_channel<4>(db, kb, 2), lod.f);
-      j = lod_blend(j, linear_channel<1>(jb, kb, 0), lod.f);
-    }
-    jac += j / (float)p.count;
-    const float f = p.c[c].scale;
-    d[0] += hx;        // dh/dx
-    d[1] += dxx * f;   // dDx/dx
-    d[2] += hz;        // dh/dz
-    d[3] += dzz * f;   // dDz/dz
-  }
-  const float sx = d[0] / (1.0f + d[1]), sz = d[2] / (1.0f + d[3]);
-  const float nx = -sx, ny = 1.0f, nz = -sz;
-  const float len = sqrtf(nx * nx + ny * ny + nz * nz);
-  return make_float4(nx / len, ny / len, nz / len, jac);
-}
-
-// k_surface with a footprint per point: xzf = (x, z, footprint) triples, or on the plane mesh the spacing
-// of the warped vertices, k * (40 / res) with k the vertex's warp factor. Slot 7: the footprint used.
-__global__ __launch_bounds__(256) void k_surface_lod(SurfaceParams p, SurfacePlane plane, const float* __restrict__ xzf,
-                                                     int64_t count, float4* __restrict__ out)
-{
-#pragma clang fp contract(off)
-  float tx = 0.0f, tz = 0.0f, cam_y = 0.0f;
-  if (plane.res > 0)
-  {
-    const float fl = sqrtf(plane.fwd_x * plane.fwd_x + plane.fwd_z * plane.fwd_z);
-    const float tx0 = plane.fwd_x / fl, tz0 = plane.fwd_z / fl;
-    tx = (tx0 - tz0) * 0.70711f;
-    tz = (tx0 + tz0) * 0.70711f;
-    cam_y = fmaxf(plane.cam_y, 10.0f);
-  }
-  const int top = 31 - __clz(p.n);
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < count;
-       idx += (int64_t)gridDim.x * blockDim.x)
-  {
-    float px, pz, footprint;
-    if (plane.res > 0)
-    {
-      // the plane vertex and its warp exactly as in k_surface
-      const int side = plane.res + 1;
-      const int i = (int)(idx % side), j = (int)(idx / side);
-      const float x = -20.0f + 40.0f * (float)i / (float)plane.res + 15.0f;
-      const float z = -20.0f + 40.0f * (float)j / (float)plane.res + 15.0f;
-      float rx = tx * x - tz * z, rz = x * tz + z * tx;
-      const float len = sqrtf(rx * rx + rz * rz);
-      const float k = powf(fmaxf(len, 1.0f), 1.2f) * cam_y * 0.04f;
-      px = rx * k + plane.cam_x;
-      pz = rz * k + plane.cam_z;
-      footprint = k * (40.0f / (float)plane.res);
-    }
-    else
-    {
-      px = xzf[3 * idx];
-      pz = xzf[3 * idx + 1];
-      footprint = xzf[3 * idx + 2];
-    }
-    float py = 0.0f;
-    surface_vertex_stage_lod(p, top, footprint, px, py, pz);
-    const float4 f = surface_fragment_stage_lod(p, top, footprint, px, pz);
-    out[2 * idx] = make_float4(px, py, pz, f.w);
-    out[2 * idx + 1] = make_float4(f.x, f.y, f.z, footprint);
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
 // Host-side launchers and size helpers.
 // ------------------------------------------------------------------------------------------------
 size_t seed_consts_bytes() { return sizeof(SpectrumConsts); }
@@ -566,109 +277,6 @@ hipError_t launch_generate_spectrum(const OceanSettings& s, int n, float4* h0, h
     hipLaunchKernelGGL(k_generate_spectrum, dim3((unsigned)blocks), dim3(256), 0, stream, spectrum_consts(s, n), n,
                        blk, x0, width, h0, n);
   return hipGetLastError();
-}
-
-// the repack of the cascades' maps into p.atlas (k_surface_atlas), ahead of a request that samples it
-void launch_surface_atlas(const SurfaceParams& p, hipStream_t stream, int cus)
-{
-  const long texels = (long)p.count * p.n * p.n;
-  long ab = (texels + 255) / 256;
-  if (ab > (long)cus * 4)
-    ab = (long)cus * 4;
-  hipLaunchKernelGGL(k_surface_atlas, dim3((unsigned)ab), dim3(256), 0, stream, p);
-}
-
-hipError_t launch_surface(const SurfaceParams& p, const SurfacePlane& plane, const float2* xz, int64_t count,
-                          float4* out, hipStream_t stream, int cus)
-{
-  if (count <= 0)
-    return hipSuccess;
-  long blocks = (long)((count + 255) / 256);
-  const long cap = (long)cus * 8;
-  if (blocks > cap)
-    blocks = cap;
-  if (p.atlas)
-  {
-    launch_surface_atlas(p, stream, cus);
-    hipLaunchKernelGGL(k_surface<true>, dim3((unsigned)blocks), dim3(256), 0, stream, p, plane, xz, count, out);
-  }
-  else
-    hipLaunchKernelGGL(k_surface<false>, dim3((unsigned)blocks), dim3(256), 0, stream, p, plane, xz, count, out);
-  return hipGetLastError();
-}
-
-hipError_t launch_surface_query(const SurfaceParams& p, const float2* xz, int64_t count, int iterations,
-                                float tolerance, float4* out, hipStream_t stream, int cus)
-{
-  if (count <= 0)
-    return hipSuccess;
-  long blocks = (long)((count + 255) / 256);
-  const long cap = (long)cus * 8;
-  if (blocks > cap)
-    blocks = cap;
-  if (p.atlas)
-  {
-    launch_surface_atlas(p, stream, cus);
-    hipLaunchKernelGGL(k_surface_query<true>, dim3((unsigned)blocks), dim3(256), 0, stream, p, xz, count, iterations,
-                       tolerance, out);
-  }
-  else
-    hipLaunchKernelGGL(k_surface_query<false>, dim3((unsigned)blocks), dim3(256), 0, stream, p, xz, count, iterations,
-                       tolerance, out);
-  return hipGetLastError();
-}
-
-hipError_t launch_surface_velocity(const SurfaceParams& p, const SurfaceRates& r, const float2* xz, int64_t count,
-                                   float4* out, hipStream_t stream, int cus)
-{
-  if (count <= 0)
-    return hipSuccess;
-  long blocks = (long)((count + 255) / 256);
-  const long cap = (long)cus * 8;
-  if (blocks > cap)
-    blocks = cap;
-  hipLaunchKernelGGL(k_surface_velocity, dim3((unsigned)blocks), dim3(256), 0, stream, p, r, xz, count, out);
-  return hipGetLastError();
-}
-
-hipError_t launch_surface_lod(const SurfaceParams& p, const SurfacePlane& plane, const float* xzf, int64_t count,
-                              float4* out, hipStream_t stream, int cus)
-{
-  if (count <= 0)
-    return hipSuccess;
-  long blocks = (long)((count + 255) / 256);
-  const long cap = (long)cus * 8;
-  if (blocks > cap)
-    blocks = cap;
-  hipLaunchKernelGGL(k_surface_lod, dim3((unsigned)blocks), dim3(256), 0, stream, p, plane, xzf, count, out);
-  return hipGetLastError();
-}
-
-size_t surface_atlas_texels(const SurfaceParams& p) { return (size_t)2 * p.count * p.n * p.n; }
-
-// The repack reads 36 B and writes 32 B per map texel and launches one more kernel; sampling from the
-// atlas saves ~90 ps per vertex (profiles/r06_surfbench2.log). Used when the request's vertices
-// outnumber the maps' texels 4 : 1 (and are at least 64 Ki) and the atlas stays within 256 MiB.
-bool surface_use_atlas(const SurfaceParams& p, int64_t points)
-{
-  const size_t texels = surface_atlas_texels(p);
-  return points >= 65536 && (uint64_t)points >= 2 * (uint64_t)texels && texels * 16 <= ((size_t)256 << 20);
-}
-
-// A query samples the vertex stage up to iterations + 1 times per point, so the repack pays much sooner
-// than for a forward sample: measured on 3 x 256^2 and 3 x 1024^2 maps with each path forced at 4 Ki ..
-// 1 Mi points and 0 / 1 / 2 / 4 / 8 / 16 iterations (tools/surface_query_bench.py,
-// profiles/surface_query_bench.log), the atlas wins from 16 Ki points (256^2) and 64 Ki points (1024^2) at
-// 2 or more iterations, and from 64 Ki and 128 Ki points at 0 or 1: e.g. 8 iterations on 64 Ki points of
-// the 256^2 scene 56 -> 29 us, on 1025^2 points 900 -> 339 us. The repack costs ~6 us at 256^2 and ~31 us
-// at 1024^2, hence a floor and a share of the atlas texels (2 per map texel and cascade).
-bool surface_query_use_atlas(const SurfaceParams& p, int64_t points, int iterations)
-{
-  const size_t texels = surface_atlas_texels(p);
-  const int64_t floor_points = iterations >= 2 ? 16384 : 65536;
-  const uint64_t per_point = iterations >= 2 ? 96 : 48;  // atlas texels one point pays for
-  return points >= floor_points && (uint64_t)points * per_point >= (uint64_t)texels &&
-         texels * 16 <= ((size_t)256 << 20);
 }
 
 // A plain 16-B copy on a fixed number of 256-thread workgroups (ocean_debug_copy): bench.py paces the

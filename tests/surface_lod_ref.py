@@ -4,7 +4,7 @@ fp32 does.
 
     pyramid     L[l+1](x, y) = 0.25f * ((L[l](2x, 2y) + L[l](2x+1, 2y)) + (L[l](2x, 2y+1) + L[l](2x+1, 2y+1)))
     lod_of      r -> (l, f): (0, 0) unless r >= 1; (top, 0) from 2^top; else r's exponent and r / 2^l - 1
-    bilinear    GL_LINEAR + GL_REPEAT, the taps and weights of linear_repeat_taps (ocean_kernels.hip)
+    bilinear    GL_LINEAR + GL_REPEAT, the taps and weights of linear_repeat_taps (device/surface_sample.h)
     surface_lod the vertex and fragment stages with A + f * (B - A) between levels l and l + 1
 """
 import numpy as np

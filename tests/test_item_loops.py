@@ -1,4 +1,4 @@
-"""Every kernel's item loop past its first item: frames, rates, slabs and hull loads under a CU budget.
+"""Every kernel's item loop past its first item: frames, rates, slabs, hull loads and surface requests under a CU budget.
 
 Every frame kernel is a loop `for (item = slot(blockIdx.x, gridDim.x); item < total; item += gridDim.x)`
 whose body reuses the LDS exchange, the twiddle table and (some) loads carried from one item to the next.
@@ -519,3 +519,74 @@ def test_budgeted_hull_loads_equal_full_device(ocean, oracle, hull_scene, case, 
         want_loads, want_pts, _ = H.hull_loads(oracle, host, rates, points, ranges, poses, 9810.0, 8, 0.0, velocity)
         assert np.array_equal(one[1], want_pts) and np.array_equal(one[0], want_loads)
     hulls.close()
+
+
+# ---- the surface consumer's point kernels -------------------------------------------------------------
+# launch_surface.hip: k_surface, k_surface_query, k_surface_velocity and k_surface_lod run one thread per point
+# on at most budget * 8 workgroups of 256 (launch_points), k_surface_atlas one per map texel on at most budget * 4.
+POINT_BUDGETS = (1, 3)
+POINTS = 24576
+
+
+def query_uses_atlas(cascades, n, points, iterations):
+    """surface_query_use_atlas (launch_surface.hip), restated."""
+    texels = 2 * cascades * n * n
+    floor_points, per_point = (16384, 96) if iterations >= 2 else (65536, 48)
+    return points >= floor_points and points * per_point >= texels and texels * 16 <= 256 << 20
+
+
+@gpu
+def test_budgeted_point_kernels_equal_full_device(ocean, hull_scene):
+    """ocean_surface_sample, _query (8 iterations: the atlas repack and k_surface_query<true>; 1 iteration:
+    <false>), _velocity and _sample_lod (footprints from below level 0 to past the top level) on 24576 points
+    of three 64^2 cascades at budgets 1 and 3 against budget 0 on the same plan, bit for bit, every output
+    filled with 0xFF bytes first. Each request is compared with itself only."""
+    from oceansimulation_amd.hip import DeviceBuffer
+
+    fft, sampler, _, _, gens = hull_scene
+    n, cascades = 64, len(gens)
+    for b in POINT_BUDGETS:
+        assert POINTS >= 3 * 8 * 256 * b + 1       # every thread of the four point kernels runs >= 3 items
+        assert cascades * n * n >= 3 * 4 * 256 * b  # and every thread of the repack
+    assert query_uses_atlas(cascades, n, POINTS, 8) and not query_uses_atlas(cascades, n, POINTS, 1)
+    for g in gens:
+        g.build_mips()
+    rng = np.random.default_rng(17)
+    xz = rng.uniform(-150.0, 150.0, (POINTS, 2)).astype(np.float32)
+    footprint = np.exp(rng.uniform(np.log(0.01), np.log(200.0), POINTS)).astype(np.float32)
+    for plane in (5.0, 101.0):  # r = footprint * N / planeSize: below 1 (level 0 alone) up to >= N (the top level)
+        r = footprint * np.float32(n) / np.float32(plane)
+        assert r.min() < 1.0 and r.max() >= n / 2
+    assert (footprint * np.float32(n) / np.float32(5.0)).max() >= n
+    xz_dev = DeviceBuffer.from_array(xz)
+    xzf_dev = DeviceBuffer.from_array(np.concatenate([xz, footprint[:, None]], axis=1))
+    out = DeviceBuffer(POINTS * 32)
+    calls = {
+        "sample": lambda: sampler.sample(xz_dev.ptr, POINTS, out.ptr),
+        "query-8": lambda: sampler.query(xz_dev.ptr, POINTS, 8, 0.0, out.ptr),
+        "query-1": lambda: sampler.query(xz_dev.ptr, POINTS, 1, 0.0, out.ptr),
+        "velocity": lambda: sampler.velocity(xz_dev.ptr, POINTS, out.ptr),
+        "sample_lod": lambda: sampler.sample_lod(xzf_dev.ptr, POINTS, out.ptr),
+    }
+
+    def run(budget):
+        got = {}
+        fft.set_cu_budget(budget)
+        for name, call in calls.items():
+            _fill_sentinel(out.ptr, out.nbytes)
+            call()
+            fft.synchronize()
+            got[name] = out.to_host((POINTS, 8)).view(np.uint32)
+        return got
+
+    try:
+        full = run(0)
+        budgeted = {b: run(b) for b in POINT_BUDGETS}
+    finally:
+        fft.set_cu_budget(0)
+    for name, want in full.items():
+        assert not (want == 0xFFFFFFFF).all(axis=1).any(), name  # no point left unwritten
+        for b in POINT_BUDGETS:
+            assert np.array_equal(budgeted[b][name], want), (name, "budget", b)
+    for buf in (xz_dev, xzf_dev, out):
+        buf.free()

@@ -2,7 +2,7 @@
 """Times ocean_surface_query against ocean_surface_sample on the same points (surface
 consumer): the 3 x 256^2 scene at t = 1, positions uniform in a +-400 m box, HIP events on the plan's
 stream around 20 calls after 3 warm-ups, the median of 5 such windows (and their spread). The path
-columns restate surface_use_atlas / surface_query_use_atlas (ocean_kernels.hip): which of the maps or
+columns restate surface_use_atlas / surface_query_use_atlas (launch_surface.hip): which of the maps or
 the repacked atlas each call samples.
 
     python tools/surface_query_bench.py [--n 256] [--points 4096,1050625] [--iterations 8] [--steep]
