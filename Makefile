@@ -30,15 +30,15 @@ KERNEL_OBJS := $(KERNEL_TUS:%=$(CSRC)/build/%.o)
 # code, which this build does not use, refers to it). The units split off from ocean_kernels and ocean_capi
 # keep theirs local, so the library's dynamic symbol table is what it was before the split.
 OBJCOPY ?= /opt/rocm/lib/llvm/bin/llvm-objcopy
-LOCAL_CUID := launch_surface ocean_capi_surface
+LOCAL_CUID := launch_surface ocean_capi_surface ocean_capi_exchange
 local_cuid = $(if $(filter $(basename $(notdir $@)),$(LOCAL_CUID)),$(OBJCOPY) -w -L '__hip_cuid_*' $@)
 $(CSRC)/build/%.o: $(CSRC)/%.hip $(DEVICE_H)
 	@mkdir -p $(CSRC)/build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 	$(local_cuid)
 
-# the C ABI: the plans, generators and exchanges, and the surface consumers' entry points
-CAPI_OBJS := $(CSRC)/build/ocean_capi.o $(CSRC)/build/ocean_capi_surface.o
+# the C ABI: the plans and generators, their exchanges, and the surface consumers' entry points
+CAPI_OBJS := $(CSRC)/build/ocean_capi.o $(CSRC)/build/ocean_capi_exchange.o $(CSRC)/build/ocean_capi_surface.o
 $(CAPI_OBJS): $(CSRC)/build/%.o: $(CSRC)/%.cpp $(CSRC)/ocean_capi_internal.h $(CSRC)/ocean_internal.h \
               $(CSRC)/device/mip_index.h include/oceanfft.h
 	@mkdir -p $(CSRC)/build

@@ -1,14 +1,14 @@
 // ocean_capi.cpp — implementation of the C ABI in include/oceanfft.h.
 //
 // Host-side orchestration of the reference's FFTCalculator / Generator (src/FFTCalculator.cpp,
-// src/Generator.cpp) over the HIP kernels in ocean_kernels.hip and launch_*.hip: the plans, the
-// generators and their exchanges. The entry points that consume a generator's maps (the map getters,
-// the surface requests, mips, rates, bounds and hull sets) are in ocean_capi_surface.cpp. No CPU fallback
-// exists: without a GPU every entry point fails with OCEAN_ERR_NO_DEVICE / OCEAN_ERR_HIP.
+// src/Generator.cpp) over the HIP kernels in ocean_kernels.hip and launch_*.hip: the plans and the
+// generators. The exchanges that move a slab frame's blocks between ranks are in ocean_capi_exchange.cpp,
+// the entry points that consume a generator's maps (the map getters, the surface requests, mips, rates,
+// bounds and hull sets) in ocean_capi_surface.cpp. No CPU fallback exists: without a GPU every entry point
+// fails with OCEAN_ERR_NO_DEVICE / OCEAN_ERR_HIP.
 #include "oceanfft.h"
 
 #include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
 
 #include <algorithm>
 #include <cmath>
@@ -31,14 +31,63 @@ int log2_exact(size_t n)
     l++;
   return ((size_t)1 << l) == n ? l : -1;
 }
+
+// Twiddle table exp(+2 pi i e / N), two levels (FFTCalculator's pass table analogue,
+// src/FFTCalculator.cpp:14-32): [0, TB) = low part, [TB, TB+TA) = high part. The four-step
+// EncodeIFFT (N = 16384) appends the N/16-point table at tw2_at, the pre-stage one (N = 8192) the
+// 4096-point table at twm_at.
+std::vector<float2> twiddle_tables(int logn, size_t& tw2_at, size_t& twm_at)
+{
+  std::vector<float2> tab;
+  const double two_pi = 6.283185307179586476925286766559;
+  auto append_table = [&](int lg) {
+    const int lb = lg / 2, tb = 1 << lb, ta = 1 << (lg - lb);
+    const double len = (double)(1 << lg);
+    for (int e2 = 0; e2 < tb; e2++)
+    {
+      double a = two_pi * e2 / len;
+      tab.push_back(make_float2((float)std::cos(a), (float)std::sin(a)));
+    }
+    for (int e2 = 0; e2 < ta; e2++)
+    {
+      double a = two_pi * ((double)e2 * tb) / len;
+      tab.push_back(make_float2((float)std::cos(a), (float)std::sin(a)));
+    }
+  };
+  append_table(logn);
+  tw2_at = tab.size();
+  if (fourstep_table(logn))
+    append_table(logn - 4);
+  twm_at = tab.size();
+  if (ifft_pre_supported(logn))
+    append_table(12);
+  return tab;
+}
+
+// Replaces the plan's work buffer by one of `texels` (`images` whole images; 0: the four-step slab).
+// Capped (ocean_debug_fft_work_limit) or without room, the plan keeps what it has and the caller falls
+// back to the in-place passes.
+void grow_work(ocean_fft* fft, size_t texels, int images)
+{
+  float4* w = nullptr;
+  if (texels * sizeof(float4) > fft->work_limit)
+    return;
+  if (hipMalloc(&w, texels * sizeof(float4)) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return;
+  }
+  if (fft->work)
+    (void)hipFree(fft->work);
+  fft->work = w;
+  fft->work_images = images;
+  fft->work_texels = texels;
+}
 }  // namespace
 
 // Four-step EncodeIFFT work slab width at N = 16384 (tools/microbench/ifft4bench,
 // profiles/r02_ifft4bench.log: 2048 columns 5.05 ms, whole image 5.39, in place 7.26)
 constexpr int kFourStepSlab = 2048;
-
-static void peers_detach(ocean_peers* p);  // the one-sided exchange section below
-static bool peers_pending(const ocean_peers* p);
 
 extern "C" {
 
@@ -103,32 +152,8 @@ int ocean_fft_create(ocean_fft** out, size_t texture_size, void* hip_stream)
     return hip_fail(e, "ocean_fft_create: device query");
   }
 
-  // Twiddle table exp(+2 pi i e / N), two levels (FFTCalculator's pass table analogue,
-  // src/FFTCalculator.cpp:14-32): [0, TB) = low part, [TB, TB+TA) = high part. The four-step
-  // EncodeIFFT (N = 16384) appends the N/16-point table.
-  std::vector<float2> tab;
-  const double two_pi = 6.283185307179586476925286766559;
-  auto append_table = [&](int lg) {
-    const int lb = lg / 2, tb = 1 << lb, ta = 1 << (lg - lb);
-    const double len = (double)(1 << lg);
-    for (int e2 = 0; e2 < tb; e2++)
-    {
-      double a = two_pi * e2 / len;
-      tab.push_back(make_float2((float)std::cos(a), (float)std::sin(a)));
-    }
-    for (int e2 = 0; e2 < ta; e2++)
-    {
-      double a = two_pi * ((double)e2 * tb) / len;
-      tab.push_back(make_float2((float)std::cos(a), (float)std::sin(a)));
-    }
-  };
-  append_table(logn);
-  const size_t tw2_at = tab.size();
-  if (fourstep_table(logn))
-    append_table(logn - 4);
-  const size_t twm_at = tab.size();
-  if (ifft_pre_supported(logn))
-    append_table(12);
+  size_t tw2_at = 0, twm_at = 0;
+  const std::vector<float2> tab = twiddle_tables(logn, tw2_at, twm_at);
   e = hipMalloc(&f->twiddles, tab.size() * sizeof(float2));
   if (e == hipSuccess)
     e = hipMemcpy(f->twiddles, tab.data(), tab.size() * sizeof(float2), hipMemcpyHostToDevice);
@@ -203,22 +228,7 @@ int ocean_fft_encode_ifft_batch(ocean_fft* fft, float* images, int n_images)
     const int chunk = std::max(1, (int)(((size_t)2 << 30) / ((size_t)fft->n * fft->n * sizeof(float4))));
     const int want = n_images < chunk ? n_images : chunk;
     if (fft->work_images < want)
-    {
-      float4* w = nullptr;
-      const size_t bytes = (size_t)want * fft->n * fft->n * sizeof(float4);
-      if (bytes > fft->work_limit)
-        ;  // capped (ocean_debug_fft_work_limit): as a failed allocation
-      else if (hipMalloc(&w, bytes) == hipSuccess)
-      {
-        if (fft->work)
-          (void)hipFree(fft->work);
-        fft->work = w;
-        fft->work_images = want;
-        fft->work_texels = (size_t)want * fft->n * fft->n;
-      }
-      else
-        (void)hipGetLastError();  // no room for the work image: the in-place passes below
-    }
+      grow_work(fft, (size_t)want * fft->n * fft->n, want);
     if (fft->work)
     {
       for (int first = 0; first < n_images; first += fft->work_images)
@@ -241,21 +251,7 @@ int ocean_fft_encode_ifft_batch(ocean_fft* fft, float* images, int n_images)
     // texels (512 MiB): every access a >= 256-B row piece instead of one-column 16-B pieces
     const size_t want = ifft_fourstep_work_texels(fft->logn, kFourStepSlab);
     if (fft->work_texels < want)
-    {
-      float4* w = nullptr;
-      if (want * sizeof(float4) > fft->work_limit)
-        ;  // capped (ocean_debug_fft_work_limit): as a failed allocation
-      else if (hipMalloc(&w, want * sizeof(float4)) == hipSuccess)
-      {
-        if (fft->work)
-          (void)hipFree(fft->work);
-        fft->work = w;
-        fft->work_texels = want;
-        fft->work_images = 0;
-      }
-      else
-        (void)hipGetLastError();  // no room for the slab: the in-place passes below
-    }
+      grow_work(fft, want, 0);
     if (fft->work_texels >= want)
     {
       HIP_TRY(launch_ifft_fourstep(fft->logn, n_images, img, fft->work, kFourStepSlab, fft->twiddles, fft->tw2,
@@ -281,6 +277,9 @@ int ocean_fft_synchronize(ocean_fft* fft)
 
 }  // extern "C"
 
+// ---------------------------------------------------------------------------------------------
+// Generator
+// ---------------------------------------------------------------------------------------------
 namespace
 {
 hipEvent_t take_event(ocean_generator* g)
@@ -315,32 +314,26 @@ hipError_t timed(ocean_generator* g, int kind, F&& launch, hipStream_t stream = 
   g->pending.push_back(p);
   return e;
 }
-}  // namespace
 
-extern "C" {
-
-// ---------------------------------------------------------------------------------------------
-// Generator
-// ---------------------------------------------------------------------------------------------
-static hipError_t half_buffers(ocean_generator* g)
+// One slot of the blocked half path's fields
+hipError_t half_fields(ocean_generator* g, int slot)
 {
   const size_t t = half_field_texels(g->fft->logn) * g->cascades;
-  hipError_t e = hipSuccess;
-  if (!g->gab)
-    e = hipMalloc(&g->gab, t * sizeof(float4));
-  if (e == hipSuccess && !g->gcd)
-    e = hipMalloc(&g->gcd, t * sizeof(float4));
-  if (e == hipSuccess && !g->ge)
-    e = hipMalloc(&g->ge, t * sizeof(float2));
-  if (e == hipSuccess && !g->spec)
-    e = hipMalloc(&g->spec, (size_t)g->cascades * 2 * g->fft->n * sizeof(float4));
-  if (e == hipSuccess && !g->hs)  // pass 1's H scratch: one slice per resident block (1 per CU)
-    e = hipMalloc(&g->hs, half_hs_bytes(g->fft->logn, g->fft->device_cus));
-  return e;
+  HalfFields& f = g->fields[slot];
+  hipError_t e = alloc_if_null(f.gab, t * sizeof(float4));
+  e = alloc_if_null(f.gde, t * sizeof(float4), e);
+  e = alloc_if_null(f.gc, t * sizeof(float2), e);
+  return alloc_if_null(f.spec, (size_t)g->cascades * 2 * g->fft->n * sizeof(float4), e);
+}
+
+hipError_t half_buffers(ocean_generator* g)
+{
+  // slot 0, and pass 1's H scratch: one slice per resident block (1 per CU)
+  return alloc_if_null(g->hs, half_hs_bytes(g->fft->logn, g->fft->device_cus), half_fields(g, 0));
 }
 
 // The strip-dealt path's geometry: STRIPS kept strips dealt S = ceil(STRIPS / ranks) per rank.
-static HalfSlab half_slab_geom(int logn, int rank, int ranks)
+HalfSlab half_slab_geom(int logn, int rank, int ranks)
 {
   const int strips = half_strips(logn);
   HalfSlab h{};
@@ -351,25 +344,24 @@ static HalfSlab half_slab_geom(int logn, int rank, int ranks)
   return h;
 }
 
-static bool uses_gen4(const ocean_generator* g)
-{
-  return g->four_step && g->hslab && gen4_supported(g->fft->logn);
-}
-
 // strip width of the h0 image the current frame path reads (the whole-grid half path at <= 2
 // cascades of 4096: 2-column strips, one per half-strip item, launch_common.h half_h0_block)
-static int h0_block(const ocean_generator* g)
+int h0_block(const ocean_generator* g)
 {
-  if (uses_gen4(g))
-    return gen4_h0_block();
-  if (g->half && g->ranks == 1)
-    return half_h0_block(g->fft->logn, g->cascades);
-  return spectrum_block(g->fft->logn);
+  switch (frame_path(g))
+  {
+    case FramePath::FourStep:
+      return gen4_h0_block();
+    case FramePath::HalfBlocked:
+      return half_h0_block(g->fft->logn, g->cascades);
+    default:
+      return spectrum_block(g->fft->logn);
+  }
 }
 
 // h0 texels per cascade: the whole grid (ranks == 1), or the largest of a slab's layouts (its column
 // slab, its dealt strips, its four-step columns blocked 64 wide), so switching paths needs no reallocation
-static size_t h0_texels(const ocean_generator* g)
+size_t h0_texels(const ocean_generator* g)
 {
   const size_t full = (size_t)g->fft->n * g->geom.w;  // the full path's column slab (whole grid: N^2)
   if (g->ranks == 1)
@@ -381,36 +373,51 @@ static size_t h0_texels(const ocean_generator* g)
   return t;
 }
 
-static size_t hslab_xbuf_bytes(const ocean_generator* g)
+hipError_t full_buffers(ocean_generator* g)
 {
-  if (uses_gen4(g))
+  const size_t slab = (size_t)g->fft->n * g->geom.w * g->cascades;
+  hipError_t e = alloc_if_null(g->inter, slab * 2 * sizeof(float4));
+  return rows_need_transpose(g->fft->logn) ? alloc_if_null(g->scratch, slab * 2 * sizeof(float4), e) : e;
+}
+
+// The buffers of the current frame path (allocated when the path is first used; a path switch keeps the
+// other paths' buffers)
+hipError_t path_buffers(ocean_generator* g)
+{
+  switch (frame_path(g))
+  {
+    case FramePath::Full:
+      return full_buffers(g);
+    case FramePath::HalfBlocked:
+      return half_buffers(g);
+    default:
+      return hslab_buffers(g);
+  }
+}
+}  // namespace
+
+size_t hslab_xbuf_bytes(const ocean_generator* g)
+{
+  if (frame_path(g) == FramePath::FourStep)
     return (size_t)g->ranks * g->g4.blk_bytes;
   return (size_t)g->ranks * half_slab_block_bytes(g->fft->logn, g->cascades, g->hsl);
 }
 
-// The buffers of the current half-spectrum slab path (allocated when the path is first used; a path
-// switch keeps the other path's buffers). Four-step: step 1's parts and the exchange blocks (ranks ==
-// 1: one block, read back by the row pass). Strip-dealt: the row-major fields and the H scratch.
-static hipError_t hslab_buffers(ocean_generator* g)
+// Four-step: step 1's parts and the exchange blocks (ranks == 1: one block, read back by the row pass).
+// Strip-dealt: the row-major fields and the H scratch.
+hipError_t hslab_buffers(ocean_generator* g)
 {
   const int logn = g->fft->logn, C = g->cascades;
   hipError_t e = hipSuccess;
-  if (uses_gen4(g))
-  {
-    if (!g->parts)
-      e = hipMalloc(&g->parts, gen4_parts_bytes(logn, C, g->g4));
-  }
+  if (frame_path(g) == FramePath::FourStep)
+    e = alloc_if_null(g->parts, gen4_parts_bytes(logn, C, g->g4));
   else
   {
     const size_t rt = half_slab_row_texels(logn, C, g->hsl.w);
-    if (!g->rm_ab)
-      e = hipMalloc(&g->rm_ab, rt * sizeof(float4));
-    if (e == hipSuccess && !g->rm_de)
-      e = hipMalloc(&g->rm_de, rt * sizeof(float4));
-    if (e == hipSuccess && !g->rm_c)
-      e = hipMalloc(&g->rm_c, rt * sizeof(float2));
-    if (e == hipSuccess && !g->hs)
-      e = hipMalloc(&g->hs, half_hs_bytes(logn, g->fft->device_cus));
+    e = alloc_if_null(g->rm_ab, rt * sizeof(float4));
+    e = alloc_if_null(g->rm_de, rt * sizeof(float4), e);
+    e = alloc_if_null(g->rm_c, rt * sizeof(float2), e);
+    e = alloc_if_null(g->hs, half_hs_bytes(logn, g->fft->device_cus), e);
   }
   const size_t xb = hslab_xbuf_bytes(g);
   if (e == hipSuccess && g->xbuf_bytes < xb)
@@ -423,23 +430,14 @@ static hipError_t hslab_buffers(ocean_generator* g)
     if (e == hipSuccess)
       g->xbuf_bytes = xb;
   }
-  if (e == hipSuccess && g->ranks > 1 && !g->h0row)
-    e = hipMalloc(&g->h0row, (size_t)C * g->fft->n * sizeof(float4));
+  if (g->ranks > 1)
+    e = alloc_if_null(g->h0row, (size_t)C * g->fft->n * sizeof(float4), e);
   return e;
 }
 
-static hipError_t full_buffers(ocean_generator* g)
+namespace
 {
-  const size_t slab = (size_t)g->fft->n * g->geom.w * g->cascades;
-  hipError_t e = hipSuccess;
-  if (!g->inter)
-    e = hipMalloc(&g->inter, slab * 2 * sizeof(float4));
-  if (e == hipSuccess && rows_need_transpose(g->fft->logn) && !g->scratch)
-    e = hipMalloc(&g->scratch, slab * 2 * sizeof(float4));
-  return e;
-}
-
-static int generator_alloc(ocean_generator** out, ocean_fft* fft, int cascades, int rank, int ranks, bool is_slab)
+int generator_alloc(ocean_generator** out, ocean_fft* fft, int cascades, int rank, int ranks, bool is_slab)
 {
   auto* g = new ocean_generator();
   g->fft = fft;
@@ -452,11 +450,9 @@ static int generator_alloc(ocean_generator** out, ocean_fft* fft, int cascades, 
   for (auto& s : g->settings)
     ocean_default_settings(&s);
   const size_t slab = (size_t)fft->n * g->geom.w;  // texels per cascade image slab
-  g->half = ranks == 1 && half_spectrum_supported(fft->logn);
-  // slabs of N >= 1024 and whole grids above the blocked half path's sizes: strip-dealt half spectrum
   g->slab = is_slab;
-  g->half = g->half && !is_slab;
-  g->hslab = !g->half && half_slab_supported(fft->logn) && (is_slab || fft->logn > 12);
+  g->half_kind = half_kind_of(fft->logn, is_slab);
+  g->half_on = g->half_kind != HalfKind::None;
   g->hsl = half_slab_geom(fft->logn, rank, ranks);
   if (gen4_supported(fft->logn))
   {
@@ -472,33 +468,425 @@ static int generator_alloc(ocean_generator** out, ocean_fft* fft, int cascades, 
     delete g;
     return fail(OCEAN_ERR_INVALID, "generator allocation: a slab generator holds exactly one cascade");
   }
-  hipError_t e = hipMalloc(&g->h0, h0_texels(g) * cascades * sizeof(float4));
-  if (e == hipSuccess && !g->half && !g->hslab)
-    e = full_buffers(g);
-  if (e == hipSuccess && g->half)
-    e = half_buffers(g);
-  if (e == hipSuccess && g->hslab)
-    e = hslab_buffers(g);
+  const size_t h0_bytes = h0_texels(g) * cascades * sizeof(float4);
+  hipError_t e = alloc_if_null(g->h0, h0_bytes);
   if (e == hipSuccess)
-    e = hipMalloc(&g->maps, slab * cascades * 2 * sizeof(float4));
-  if (e == hipSuccess)
-    e = hipMalloc(&g->jac, slab * cascades * sizeof(float));
+    e = path_buffers(g);
+  e = alloc_if_null(g->maps, slab * cascades * 2 * sizeof(float4), e);
+  e = alloc_if_null(g->jac, slab * cascades * sizeof(float), e);
   // Textures start zeroed like the reference's (Data = nullptr) images.
   if (e == hipSuccess)
-    e = hipMemsetAsync(g->h0, 0, h0_texels(g) * cascades * sizeof(float4), fft->stream);
+    e = hipMemsetAsync(g->h0, 0, h0_bytes, fft->stream);
   if (e == hipSuccess)
     e = hipMemsetAsync(g->maps, 0, slab * cascades * 2 * sizeof(float4), fft->stream);
   if (e == hipSuccess)
     e = hipMemsetAsync(g->jac, 0, slab * cascades * sizeof(float), fft->stream);
   if (e != hipSuccess)
   {
-    int code = (e == hipErrorOutOfMemory) ? OCEAN_ERR_OOM : OCEAN_ERR_HIP;
     ocean_generator_destroy(g);
-    return fail(code, std::string("generator allocation: ") + hipGetErrorString(e));
+    return alloc_fail(e, "generator allocation");
   }
   *out = g;
   return OCEAN_OK;
 }
+
+// h0, h0row and the fused re-seed constants are written on the generator's stream; a column pass that
+// ran on another stream (the one-sided exchange's step-1 / put streams) may still be reading them
+int wait_h0_readers(ocean_generator* g)
+{
+  if (g->cols_ev_valid)
+    HIP_TRY(hipStreamWaitEvent(g->fft->stream, g->h0r_ev, 0), "h0 write: wait for the last column pass");
+  return OCEAN_OK;
+}
+
+// One launch of the seeding kernel: `cols` columns from x0 into a cascade's h0 image at texel `at`, in
+// strips `block` columns wide (0: spectrum_block)
+struct H0Piece
+{
+  size_t at;
+  int x0, cols, block;
+};
+
+struct H0Pieces
+{
+  H0Piece piece[2];
+  int count = 0;
+  bool row0 = false;  // slabs: also row y = 0 of every column into h0row (the Nyquist-row term)
+};
+
+// What the current frame path keeps in a cascade's h0 image
+H0Pieces h0_pieces(const ocean_generator* g)
+{
+  const int n = g->fft->n;
+  const FramePath path = frame_path(g);
+  H0Pieces p;
+  if (g->ranks > 1 && path == FramePath::FourStep)
+  {
+    // this rank's kept columns x = N/2 + u0 .. (blocked 64 wide), rank P - 1 also the block of
+    // x = 0 .. 63 (the Nyquist column x = 0 is its first)
+    const Gen4Geom& q = g->g4;
+    const int B = gen4_h0_block();
+    p.piece[p.count++] = {q.h0_reg, n / 2 + q.u0, q.cols, B};
+    if (q.nyq)
+      p.piece[p.count++] = {q.h0_nyq, 0, B, B};
+    p.row0 = true;
+  }
+  else if (g->ranks > 1 && path == FramePath::StripDealt)
+  {
+    // this rank's strips: the regular ones are columns N/2 + strip*B .. (contiguous), the last
+    // global strip is the Nyquist strip x = 0..B-1
+    const int B = spectrum_block(g->fft->logn), strips = half_strips(g->fft->logn);
+    const HalfSlab& h = g->hsl;
+    const int nreg = std::max(0, std::min(h.nstrips, strips - 1 - h.strip0));
+    if (nreg > 0)
+      p.piece[p.count++] = {0, n / 2 + h.strip0 * B, nreg * B, 0};
+    if (nreg < h.nstrips)
+      p.piece[p.count++] = {(size_t)nreg * n * B, 0, B, 0};
+    p.row0 = true;
+  }
+  else
+    p.piece[p.count++] = {0, g->geom.x0, g->geom.w, h0_block(g)};
+  return p;
+}
+
+// generateSpectrum with the given per-cascade settings (the current ones, or those a fused re-seed
+// frame evaluated h0 with, when that h0 image is materialised later)
+int generate_spectrum_with(ocean_generator* g, const std::vector<ocean_settings>& settings)
+{
+  TRY(wait_h0_readers(g));  // write-after-read on h0 (a pipelined put frame still in flight)
+  g->h0_dirty = true;
+  g->h0_stale = false;
+  g->h0_block = h0_block(g);
+  g->h0_settings = settings;
+  g->seeded = settings;
+  ocean_fft* f = g->fft;
+  const H0Pieces pieces = h0_pieces(g);
+  for (int c = 0; c < g->cascades; c++)
+  {
+    OceanSettings s;
+    std::memcpy(&s, &settings[c], sizeof(s));
+    float4* base = g->h0 + h0_texels(g) * c;
+    HIP_TRY(timed(g, 0, [&] {
+              hipError_t e = hipSuccess;
+              for (int i = 0; i < pieces.count && e == hipSuccess; i++)
+              {
+                const H0Piece& p = pieces.piece[i];
+                e = launch_generate_spectrum(s, f->n, base + p.at, f->stream, f->cus, p.x0, p.cols, p.block);
+              }
+              if (e == hipSuccess && pieces.row0)
+                e = launch_generate_spectrum_row(s, f->n, g->h0row + (size_t)c * f->n, f->stream);
+              return e;
+            }),
+            "generateSpectrum");
+  }
+  return OCEAN_OK;
+}
+
+// True when h0 seeded from `a` and from `b` is the same image: every field but the accumulated
+// time (generateSpectrum does not read it, spectrum.compute:157-172).
+bool same_h0_inputs(const std::vector<ocean_settings>& a, const std::vector<ocean_settings>& b)
+{
+  if (a.size() != b.size())
+    return false;
+  for (size_t i = 0; i < a.size(); i++)
+  {
+    ocean_settings x = a[i], y = b[i];
+    x.time = y.time = 0.0f;
+    if (std::memcmp(&x, &y, sizeof(x)) != 0)
+      return false;
+  }
+  return true;
+}
+
+// Fused re-seed (src/Generator.cpp:55-59 followed by :63-72): pass 1 evaluates h0 itself from one
+// record of constants per cascade, `seed`; the h0 image is left stale
+int fused_reseed(ocean_generator* g, const void*& seed)
+{
+  ocean_fft* f = g->fft;
+  std::vector<unsigned char> host((size_t)g->cascades * seed_consts_bytes());
+  for (int c = 0; c < g->cascades; c++)
+  {
+    OceanSettings os;
+    std::memcpy(&os, &g->settings[c], sizeof(os));
+    seed_consts(os, f->n, host.data() + (size_t)c * seed_consts_bytes());
+  }
+  if (!g->seedc)
+    HIP_TRY(hipMalloc(&g->seedc, (size_t)kMaxCascades * seed_consts_bytes()), "seed constants");
+  if (host != g->seedc_host)  // pageable source: staged before the call returns
+  {
+    TRY(wait_h0_readers(g));
+    HIP_TRY(hipMemcpyAsync(g->seedc, host.data(), host.size(), hipMemcpyHostToDevice, f->stream), "seed constants");
+    g->seedc_host.swap(host);
+  }
+  seed = g->seedc;
+  g->h0_dirty = true;
+  g->h0_stale = true;
+  g->seed_settings = g->settings;
+  g->seeded = g->settings;
+  return OCEAN_OK;
+}
+
+// What a column pass does about h0 (src/Generator.cpp:55-59): nothing, a (fused) re-seed, the first
+// seeding, or writing the image that fused frames or a path switch left to do. `seed`: the constants of a
+// fused re-seed, null when pass 1 reads the h0 image.
+int seed_h0(ocean_generator* g, int update_spectrum, const void*& seed)
+{
+  // The reference app asks for a re-seed on every frame (src/Waves.cpp:91-94); when the h0 inputs
+  // are unchanged since the last seeding the result would be bit-identical, so it is skipped.
+  if (update_spectrum && !g->update_spectrum && g->memo_h0 && same_h0_inputs(g->settings, g->seeded))
+    update_spectrum = 0;
+  if (g->update_spectrum || update_spectrum)
+  {
+    // The generator's first seeding writes the h0 image. Explicit re-seeds (the reference app's
+    // every-frame CalculateOcean(dt, true)) are fused into pass 1 on the blocked half path; the
+    // inlined ocml functions round the same amplitude within an ulp of the seeding kernels' (frames
+    // agree to ~1e-7 of max, test_fused_reseed_frames), so the first frame keeps the kernels that
+    // slabs and batches are compared with bit-exactly.
+    const bool fused = update_spectrum && !g->update_spectrum && frame_path(g) == FramePath::HalfBlocked && g->hs;
+    g->update_spectrum = false;
+    return fused ? fused_reseed(g, seed) : ocean_generator_generate_spectrum(g);
+  }
+  TRY(materialise_h0(g));          // the next frames read the h0 image
+  if (g->h0_block != h0_block(g))  // the frame path changed (four-step on/off): same h0, new layout
+    TRY(generate_spectrum_with(g, g->h0_settings));
+  return OCEAN_OK;
+}
+
+FrameParams frame_params(const ocean_generator* g)
+{
+  FrameParams fp{};
+  fp.cascades = g->cascades;
+  for (int c = 0; c < g->cascades; c++)
+  {
+    const ocean_settings& s = g->settings[c];
+    // spectrum.compute:189 — `2.0 * M_PI / planeSize` in fp32
+    fp.c[c].dk = 2.0f * 3.14159265358f / s.planeSize;
+    fp.c[c].time = s.time;
+    fp.c[c].g = s.g;
+    fp.c[c].h = s.h;
+  }
+  return fp;
+}
+
+// The column pass of the strip-dealt and four-step paths, on col_stream (null: the generator's stream).
+// put (the one-sided exchange): step 2 stores into the peers' receive slots.
+int half_slab_columns(ocean_generator* g, const FrameParams& fp, float4* out, const Gen4Put* put,
+                      hipStream_t col_stream)
+{
+  ocean_fft* f = g->fft;
+  const hipError_t eb = hslab_buffers(g);  // the current path's buffers (a path switch allocates here)
+  if (eb != hipSuccess)
+    return alloc_fail(eb, "column pass buffers");
+  // the column pass's stream (the put or step-1 stream of pipelined one-sided frames) runs after the
+  // last column pass on another stream (step 1 rewrites the parts its step 2 read; the strip-dealt
+  // pass reuses its H scratch) and after h0 writes
+  hipStream_t cs = col_stream ? col_stream : f->stream;
+  // both orderings, independently: after the last column pass (whatever stream it ran on), and after
+  // the h0 writes on the generator's stream when this pass runs elsewhere
+  if (g->cols_ev_valid)
+    HIP_TRY(hipStreamWaitEvent(cs, g->cols_ev, 0), "column pass: after the last column pass");
+  if (cs != f->stream && g->h0_dirty)
+  {
+    if (!g->put_h0)
+      HIP_TRY(hipEventCreateWithFlags(&g->put_h0, hipEventDisableTiming), "column pass: event");
+    HIP_TRY(hipEventRecord(g->put_h0, f->stream), "column pass: stream event");
+    HIP_TRY(hipStreamWaitEvent(cs, g->put_h0, 0), "column pass: stream order");
+    g->h0_dirty = false;  // only once the wait is enqueued
+  }
+  // profiling a put: kind 3 brackets the wait + put kernels inside the column pass (kind 1)
+  Gen4Put timed_put = put ? *put : Gen4Put{};
+  EventPair pp{3, nullptr, nullptr};
+  if (put && g->profiling)
+  {
+    pp.a = take_event(g);
+    pp.b = take_event(g);
+    timed_put.start = pp.a;
+  }
+  if (frame_path(g) == FramePath::FourStep)
+    HIP_TRY(timed(g, 1, [&] {
+              return launch_gen4_columns(f->logn, fp, g->g4, g->h0, g->ranks > 1 ? g->h0row : nullptr,
+                                         put && put->parts ? put->parts : g->parts, out ? (void*)out : (void*)g->xbuf,
+                                         f->twiddles, f->tw2, cs, f->cus, put ? &timed_put : nullptr);
+            }, cs),
+            "column pass (half spectrum, four-step)");
+  else
+    HIP_TRY(timed(g, 1, [&] {
+              return launch_half_slab_columns(f->logn, fp, g->hsl, g->ranks, g->h0, g->ranks == 1, g->h0row,
+                                              out ? (void*)out : (void*)g->xbuf, f->twiddles, cs, f->cus, g->hs,
+                                              f->device_cus, put ? &timed_put : nullptr);
+            }, cs),
+            "column pass (half spectrum, strip-dealt)");
+  if (pp.a)
+  {
+    HIP_TRY(hipEventRecord(pp.b, put && put->stream ? put->stream : cs), "column pass: put event");
+    g->pending.push_back(pp);
+  }
+  for (hipEvent_t* ev : {&g->cols_ev, &g->h0r_ev})
+    if (!*ev)
+      HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming), "column pass: event");
+  HIP_TRY(hipEventRecord(g->cols_ev, cs), "column pass: end event");
+  // the h0 readers end on the put stream when step 2 runs there (it waited for step 1's handoff)
+  HIP_TRY(hipEventRecord(g->h0r_ev, put && put->stream ? put->stream : cs), "column pass: end event");
+  g->cols_ev_valid = true;
+  return OCEAN_OK;
+}
+
+// Frame overlap: the blocked half path's column pass on the side stream into field slot oslot, after the
+// row pass that last read the slot, and after any h0 / seed-constant writes on the generator's stream
+int overlapped_columns(ocean_generator* g, const FrameParams& fp, const void* seed)
+{
+  ocean_fft* f = g->fft;
+  const int s = g->oslot;
+  if (g->h0_dirty)
+  {
+    HIP_TRY(hipEventRecord(g->oh0, f->stream), "overlap: h0 event");
+    HIP_TRY(hipStreamWaitEvent(g->side, g->oh0, 0), "overlap: h0 wait");
+    g->h0_dirty = false;
+  }
+  if (g->orows_valid[s])
+    HIP_TRY(hipStreamWaitEvent(g->side, g->orows[s], 0), "overlap: slot wait");
+  const HalfFields& fl = g->fields[s];
+  HIP_TRY(timed(g, 1, [&] {
+            return launch_half_columns(f->logn, fp, g->h0, fl.gab, fl.gde, fl.gc, fl.spec, f->twiddles, g->side, f->cus,
+                                       g->hs, f->device_cus, seed, g->h0_block);
+          }, g->side),
+          "column pass (half spectrum, overlapped)");
+  HIP_TRY(hipEventRecord(g->ocols[s], g->side), "overlap: column event");
+  return OCEAN_OK;
+}
+
+// The buffer a whole-grid frame, or a slab frame without a caller's buffer, passes between its passes
+// (null: the half-slab paths' own exchange buffer)
+float4* own_exchange(const ocean_generator* g) { return half_slab_path(g) ? nullptr : g->inter; }
+
+// A pipelined frame in flight (one-sided or RCCL) lands before a path switch: its column pass wrote its
+// blocks in the current path's layout, so its row pass runs first
+int land_frames_in_flight(ocean_generator* g)
+{
+  if (peers_pending(g->peers))
+    TRY(ocean_peers_flush(g->peers));
+  return ocean_generator_slab_flush(g);
+}
+}  // namespace
+
+// First half of CalculateOcean: time += dt (src/Generator.cpp:50), h0 if requested (:55-59),
+// prepareFFT fused with the y direction of both EncodeIFFTs (:63-72). Output in destination-block
+// order into `out` (the internal buffer when null).
+int generator_columns(ocean_generator* g, float timestep, int update_spectrum, float4* out, const Gen4Put* put,
+                      hipStream_t col_stream)
+{
+  ocean_fft* f = g->fft;
+  g->rates_fresh = false;  // the rates belong to the time and h0 of the column pass before this one
+  for (auto& s : g->settings)
+    s.time += timestep;
+  const void* seed = nullptr;
+  TRY(seed_h0(g, update_spectrum, seed));
+  const FrameParams fp = frame_params(g);
+  if (put && !half_slab_path(g))
+    return fail(OCEAN_ERR_INVALID, "column pass: the one-sided exchange needs a half-spectrum slab path (N >= 1024)");
+  switch (frame_path(g))
+  {
+    case FramePath::FourStep:
+    case FramePath::StripDealt:
+      TRY(half_slab_columns(g, fp, out, put, col_stream));
+      break;
+    case FramePath::HalfBlocked:
+      if (g->overlap)
+        TRY(overlapped_columns(g, fp, seed));
+      else
+        HIP_TRY(timed(g, 1, [&] {
+                  const HalfFields& fl = g->fields[0];
+                  return launch_half_columns(f->logn, fp, g->h0, fl.gab, fl.gde, fl.gc, fl.spec, f->twiddles, f->stream,
+                                             f->cus, g->hs, f->device_cus, seed, g->h0_block);
+                }),
+                "column pass (half spectrum)");
+      break;
+    case FramePath::Full:
+      HIP_TRY(timed(g, 1, [&] {
+                return launch_cols_evolve(f->logn, fp, g->geom, g->h0, out, f->twiddles, f->stream, f->cus,
+                                          default_keep(f->logn));
+              }),
+              "column pass");
+      break;
+  }
+  g->frame = fp;
+  return OCEAN_OK;
+}
+
+FrameState current_frame(const ocean_generator* g)
+{
+  FrameState fs{g->frame, FoamParams{}};
+  for (int c = 0; c < g->cascades; c++)
+    fs.foam.displacement[c] = g->settings[c].displacement;
+  return fs;
+}
+
+// Second half: the x direction of both EncodeIFFTs + computeFoam (src/Generator.cpp:71-80), with the
+// column-pass values and the displacement of the frame `fs`.
+int generator_rows(ocean_generator* g, const float4* in, const FrameState& fs, hipStream_t row_stream, int row_cus)
+{
+  ocean_fft* f = g->fft;
+  g->mips_fresh = false;  // every frame path's maps are written here
+  g->bounds_fresh = false;
+  const int rcus = row_cus > 0 && row_cus < f->cus ? row_cus : f->cus;
+  if (row_stream && !half_slab_path(g))
+    return fail(OCEAN_ERR_INVALID, "row pass: a row stream needs a half-spectrum slab path");
+  hipStream_t rs = row_stream ? row_stream : f->stream;
+  switch (frame_path(g))
+  {
+    case FramePath::FourStep:
+      HIP_TRY(timed(g, 2, [&] {
+                return launch_gen4_rows(f->logn, fs.frame, g->g4, in ? (const void*)in : (const void*)g->xbuf, g->maps,
+                                        g->jac, fs.foam, f->twiddles, f->tw2, rs, rcus);
+              }, rs),
+              "row pass (half spectrum, four-step)");
+      break;
+    case FramePath::StripDealt:
+      HIP_TRY(timed(g, 2, [&] {
+                return launch_half_slab_rows(f->logn, fs.frame, g->hsl, in ? (const void*)in : (const void*)g->xbuf,
+                                             g->rm_ab, g->rm_de, g->rm_c, g->maps, g->jac, fs.foam, f->twiddles,
+                                             f->tw2, rs, rcus);
+              }, rs),
+              "row pass (half spectrum, strip-dealt)");
+      break;
+    case FramePath::HalfBlocked:
+    {
+      // frame overlap: the slot the side stream's column pass wrote, then the other one
+      const int s = g->overlap ? g->oslot : 0;
+      const HalfFields& fl = g->fields[s];
+      if (g->overlap)
+        HIP_TRY(hipStreamWaitEvent(f->stream, g->ocols[s], 0), "overlap: column wait");
+      HIP_TRY(timed(g, 2, [&] {
+                return launch_half_rows(f->logn, fs.frame, fl.gab, fl.gde, fl.gc, fl.spec, g->maps, g->jac, fs.foam,
+                                        f->twiddles, f->stream, f->cus);
+              }),
+              g->overlap ? "row pass (half spectrum, overlapped)" : "row pass (half spectrum)");
+      if (g->overlap)
+      {
+        HIP_TRY(hipEventRecord(g->orows[s], f->stream), "overlap: row event");
+        g->orows_valid[s] = true;
+        g->oslot = s ^ 1;
+      }
+      break;
+    }
+    case FramePath::Full:
+      HIP_TRY(timed(g, 2, [&] {
+                return launch_rows_final(f->logn, g->cascades, g->geom, in, g->scratch, g->maps, g->jac, fs.foam,
+                                         f->twiddles, f->stream, f->cus);
+              }),
+              "row pass");
+      break;
+  }
+  return OCEAN_OK;
+}
+
+// After fused re-seed frames: write the h0 image those frames evaluated (their settings snapshot).
+int materialise_h0(ocean_generator* g)
+{
+  return g->h0_stale ? generate_spectrum_with(g, g->seed_settings) : OCEAN_OK;
+}
+
+extern "C" {
 
 int ocean_generator_create(ocean_generator** out, ocean_fft* fft, int cascades)
 {
@@ -538,53 +926,27 @@ int ocean_generator_destroy(ocean_generator* g)
     peers_detach(g->peers);
   if (g->fft)
     (void)hipStreamSynchronize(g->fft->stream);
-  for (auto& p : g->pending)
-  {
-    (void)hipEventDestroy(p.a);
-    (void)hipEventDestroy(p.b);
-  }
-  for (auto ev : g->pool)
-    (void)hipEventDestroy(ev);
-  if (g->h0)
-    (void)hipFree(g->h0);
-  if (g->inter)
-    (void)hipFree(g->inter);
-  if (g->scratch)
-    (void)hipFree(g->scratch);
-  if (g->maps)
-    (void)hipFree(g->maps);
-  if (g->jac)
-    (void)hipFree(g->jac);
-  for (int k = 0; k < 2; k++)
-  {
-    for (hipEvent_t ev : {g->cols_done[k], g->xchg_done[k], g->rows_done[k]})
-      if (ev)
-        (void)hipEventDestroy(ev);
-    for (void* p : {(void*)g->xsend[k], (void*)g->xrecv[k]})
-      if (p)
-        (void)hipFree(p);
-  }
-  if (g->comm_stream)
-    (void)hipStreamDestroy(g->comm_stream);
-  if (g->put_h0)
-    (void)hipEventDestroy(g->put_h0);
-  for (hipEvent_t ev : {g->cols_ev, g->h0r_ev})
-    if (ev)
-      (void)hipEventDestroy(ev);
   if (g->side)
-  {
     (void)hipStreamSynchronize(g->side);
-    (void)hipStreamDestroy(g->side);
-  }
-  for (hipEvent_t ev : {g->ocols[0], g->ocols[1], g->orows[0], g->orows[1], g->oh0})
+  for (hipStream_t st : {g->comm_stream, g->side})
+    if (st)
+      (void)hipStreamDestroy(st);
+  for (auto& p : g->pending)
+    for (hipEvent_t ev : {p.a, p.b})
+      g->pool.push_back(ev);
+  for (hipEvent_t ev : g->pool)
+    (void)hipEventDestroy(ev);
+  for (hipEvent_t ev : {g->cols_done[0], g->cols_done[1], g->xchg_done[0], g->xchg_done[1], g->rows_done[0],
+                        g->rows_done[1], g->put_h0, g->cols_ev, g->h0r_ev, g->ocols[0], g->ocols[1], g->orows[0],
+                        g->orows[1], g->oh0})
     if (ev)
       (void)hipEventDestroy(ev);
-  for (void* p : {(void*)g->gab2, (void*)g->gcd2, (void*)g->ge2, (void*)g->spec2})
-    if (p)
-      (void)hipFree(p);
-  for (void* p : {(void*)g->gab, (void*)g->gcd, (void*)g->ge, (void*)g->spec, (void*)g->hs, (void*)g->h0row, g->seedc,
-                  (void*)g->rm_ab, (void*)g->rm_de, (void*)g->rm_c, (void*)g->parts, (void*)g->xbuf, (void*)g->mips,
-                  (void*)g->rates, (void*)g->bounds})
+  const HalfFields &f0 = g->fields[0], &f1 = g->fields[1];
+  for (void* p : {(void*)g->h0, (void*)g->inter, (void*)g->scratch, (void*)g->maps, (void*)g->jac, (void*)g->xsend[0],
+                  (void*)g->xsend[1], (void*)g->xrecv[0], (void*)g->xrecv[1], (void*)f0.gab, (void*)f0.gde, (void*)f0.gc,
+                  (void*)f0.spec, (void*)f1.gab, (void*)f1.gde, (void*)f1.gc, (void*)f1.spec, (void*)g->hs,
+                  (void*)g->h0row, g->seedc, (void*)g->rm_ab, (void*)g->rm_de, (void*)g->rm_c, (void*)g->parts,
+                  (void*)g->xbuf, (void*)g->mips, (void*)g->rates, (void*)g->bounds})
     if (p)
       (void)hipFree(p);
   delete g;
@@ -603,85 +965,6 @@ ocean_settings* ocean_generator_settings(ocean_generator* g, int c)
   return &g->settings[c];
 }
 
-
-// h0, h0row and the fused re-seed constants are written on the generator's stream; a column pass that
-// ran on another stream (the one-sided exchange's step-1 / put streams) may still be reading them
-static int wait_h0_readers(ocean_generator* g)
-{
-  if (g->cols_ev_valid)
-    HIP_TRY(hipStreamWaitEvent(g->fft->stream, g->h0r_ev, 0), "h0 write: wait for the last column pass");
-  return OCEAN_OK;
-}
-
-// generateSpectrum with the given per-cascade settings (the current ones, or those a fused re-seed
-// frame evaluated h0 with, when that h0 image is materialised later)
-static int generate_spectrum_with(ocean_generator* g, const std::vector<ocean_settings>& settings)
-{
-  {
-    const int rc = wait_h0_readers(g);  // write-after-read on h0 (a pipelined put frame still in flight)
-    if (rc != OCEAN_OK)
-      return rc;
-  }
-  g->h0_dirty = true;
-  g->h0_stale = false;
-  g->h0_block = h0_block(g);
-  g->h0_settings = settings;
-  g->seeded = settings;
-  ocean_fft* f = g->fft;
-  const size_t slab = h0_texels(g);
-  for (int c = 0; c < g->cascades; c++)
-  {
-    OceanSettings s;
-    std::memcpy(&s, &settings[c], sizeof(s));
-    if (uses_gen4(g) && g->ranks > 1)
-    {
-      // this rank's kept columns x = N/2 + u0 .. (blocked 64 wide), rank P - 1 also the block of
-      // x = 0 .. 63 (the Nyquist column x = 0 is its first); plus row 0 of every column
-      const Gen4Geom& q = g->g4;
-      float4* base = g->h0 + q.h0_cstride * c;
-      HIP_TRY(timed(g, 0, [&] {
-                hipError_t e = launch_generate_spectrum(s, f->n, base + q.h0_reg, f->stream, f->cus,
-                                                        f->n / 2 + q.u0, q.cols, gen4_h0_block());
-                if (e == hipSuccess && q.nyq)
-                  e = launch_generate_spectrum(s, f->n, base + q.h0_nyq, f->stream, f->cus, 0, gen4_h0_block(),
-                                               gen4_h0_block());
-                if (e == hipSuccess)
-                  e = launch_generate_spectrum_row(s, f->n, g->h0row + (size_t)c * f->n, f->stream);
-                return e;
-              }),
-              "generateSpectrum");
-      continue;
-    }
-    if (g->hslab && g->ranks > 1)
-    {
-      // this rank's strips: the regular ones are columns N/2 + strip*B .. (contiguous), the last
-      // global strip is the Nyquist strip x = 0..B-1; plus row 0 of every column (Nyquist-row term)
-      const int B = spectrum_block(f->logn), strips = half_strips(f->logn);
-      const HalfSlab& h = g->hsl;
-      const int nreg = std::max(0, std::min(h.nstrips, strips - 1 - h.strip0));
-      float4* base = g->h0 + h0_texels(g) * c;
-      HIP_TRY(timed(g, 0, [&] {
-                hipError_t e = hipSuccess;
-                if (nreg > 0)
-                  e = launch_generate_spectrum(s, f->n, base, f->stream, f->cus, f->n / 2 + h.strip0 * B, nreg * B);
-                if (e == hipSuccess && nreg < h.nstrips)
-                  e = launch_generate_spectrum(s, f->n, base + (size_t)nreg * f->n * B, f->stream, f->cus, 0, B);
-                if (e == hipSuccess)
-                  e = launch_generate_spectrum_row(s, f->n, g->h0row + (size_t)c * f->n, f->stream);
-                return e;
-              }),
-              "generateSpectrum");
-      continue;
-    }
-    HIP_TRY(timed(g, 0, [&] {
-              return launch_generate_spectrum(s, f->n, g->h0 + slab * c, f->stream, f->cus, g->geom.x0, g->geom.w,
-                                              g->h0_block);
-            }),
-            "generateSpectrum");
-  }
-  return OCEAN_OK;
-}
-
 int ocean_generator_generate_spectrum(ocean_generator* g)
 {
   if (!g)
@@ -689,327 +972,24 @@ int ocean_generator_generate_spectrum(ocean_generator* g)
   return generate_spectrum_with(g, g->settings);
 }
 
-// After fused re-seed frames: write the h0 image those frames evaluated (their settings snapshot).
-int materialise_h0(ocean_generator* g)  // ocean_capi_internal.h
-{
-  return g->h0_stale ? generate_spectrum_with(g, g->seed_settings) : OCEAN_OK;
-}
-
-// First half of CalculateOcean: time += dt (src/Generator.cpp:50), h0 if requested (:55-59),
-// prepareFFT fused with the y direction of both EncodeIFFTs (:63-72). Output in destination-block
-// order into `out` (the internal buffer when null).
-// True when h0 seeded from `a` and from `b` is the same image: every field but the accumulated
-// time (generateSpectrum does not read it, spectrum.compute:157-172).
-static bool same_h0_inputs(const std::vector<ocean_settings>& a, const std::vector<ocean_settings>& b)
-{
-  if (a.size() != b.size())
-    return false;
-  for (size_t i = 0; i < a.size(); i++)
-  {
-    ocean_settings x = a[i], y = b[i];
-    x.time = y.time = 0.0f;
-    if (std::memcmp(&x, &y, sizeof(x)) != 0)
-      return false;
-  }
-  return true;
-}
-
-// put (four-step slabs, the one-sided exchange): step 2 stores into the peers' receive slots, on
-// col_stream (null: the generator's stream), which first waits for the h0 writes issued so far.
-static int generator_columns(ocean_generator* g, float timestep, int update_spectrum, float4* out,
-                             const Gen4Put* put = nullptr, hipStream_t col_stream = nullptr)
-{
-  ocean_fft* f = g->fft;
-  g->rates_fresh = false;  // the rates belong to the time and h0 of the column pass before this one
-  for (auto& s : g->settings)
-    s.time += timestep;
-  const void* seed = nullptr;
-  // The reference app asks for a re-seed on every frame (src/Waves.cpp:91-94); when the h0 inputs
-  // are unchanged since the last seeding the result would be bit-identical, so it is skipped.
-  if (update_spectrum && !g->update_spectrum && g->memo_h0 && same_h0_inputs(g->settings, g->seeded))
-    update_spectrum = 0;
-  if (g->update_spectrum || update_spectrum)
-  {
-    // The generator's first seeding writes the h0 image. Explicit re-seeds (the reference app's
-    // every-frame CalculateOcean(dt, true)) are fused into pass 1 on the blocked half path; the
-    // inlined ocml functions round the same amplitude within an ulp of the seeding kernels' (frames
-    // agree to ~1e-7 of max, test_fused_reseed_frames), so the first frame keeps the kernels that
-    // slabs and batches are compared with bit-exactly.
-    const bool fused = update_spectrum && !g->update_spectrum && g->half && g->hs;
-    g->update_spectrum = false;
-    if (fused)
-    {
-      // fused re-seed (src/Generator.cpp:55-59 followed by :63-72): pass 1 evaluates h0 itself
-      std::vector<unsigned char> host((size_t)g->cascades * seed_consts_bytes());
-      for (int c = 0; c < g->cascades; c++)
-      {
-        OceanSettings os;
-        std::memcpy(&os, &g->settings[c], sizeof(os));
-        seed_consts(os, f->n, host.data() + (size_t)c * seed_consts_bytes());
-      }
-      if (!g->seedc)
-        HIP_TRY(hipMalloc(&g->seedc, (size_t)kMaxCascades * seed_consts_bytes()), "seed constants");
-      if (host != g->seedc_host)  // pageable source: staged before the call returns
-      {
-        const int rc = wait_h0_readers(g);
-        if (rc != OCEAN_OK)
-          return rc;
-        HIP_TRY(hipMemcpyAsync(g->seedc, host.data(), host.size(), hipMemcpyHostToDevice, f->stream), "seed constants");
-        g->seedc_host.swap(host);
-      }
-      seed = g->seedc;
-      g->h0_dirty = true;
-      g->h0_stale = true;
-      g->seed_settings = g->settings;
-      g->seeded = g->settings;
-    }
-    else
-    {
-      int rc = ocean_generator_generate_spectrum(g);
-      if (rc != OCEAN_OK)
-        return rc;
-    }
-  }
-  else
-  {
-    int rc = materialise_h0(g);  // the next frames read the h0 image
-    if (rc != OCEAN_OK)
-      return rc;
-    if (g->h0_block != h0_block(g))  // the frame path changed (four-step on/off): same h0, new layout
-    {
-      rc = generate_spectrum_with(g, g->h0_settings);
-      if (rc != OCEAN_OK)
-        return rc;
-    }
-  }
-  FrameParams fp{};
-  fp.cascades = g->cascades;
-  for (int c = 0; c < g->cascades; c++)
-  {
-    const ocean_settings& s = g->settings[c];
-    // spectrum.compute:189 — `2.0 * M_PI / planeSize` in fp32
-    fp.c[c].dk = 2.0f * 3.14159265358f / s.planeSize;
-    fp.c[c].time = s.time;
-    fp.c[c].g = s.g;
-    fp.c[c].h = s.h;
-  }
-  if (g->hslab)
-  {
-    hipError_t e = hslab_buffers(g);  // the current path's buffers (a path switch allocates here)
-    if (e != hipSuccess)
-      return fail(e == hipErrorOutOfMemory ? OCEAN_ERR_OOM : OCEAN_ERR_HIP,
-                  std::string("column pass buffers: ") + hipGetErrorString(e));
-  }
-  if (uses_gen4(g) || g->hslab)
-  {
-    // the column pass's stream (the put or step-1 stream of pipelined one-sided frames) runs after the
-    // last column pass on another stream (step 1 rewrites the parts its step 2 read; the strip-dealt
-    // pass reuses its H scratch) and after h0 writes
-    hipStream_t cs = col_stream ? col_stream : f->stream;
-    // both orderings, independently: after the last column pass (whatever stream it ran on), and after
-    // the h0 writes on the generator's stream when this pass runs elsewhere
-    if (g->cols_ev_valid)
-      HIP_TRY(hipStreamWaitEvent(cs, g->cols_ev, 0), "column pass: after the last column pass");
-    if (cs != f->stream && g->h0_dirty)
-    {
-      if (!g->put_h0)
-        HIP_TRY(hipEventCreateWithFlags(&g->put_h0, hipEventDisableTiming), "column pass: event");
-      HIP_TRY(hipEventRecord(g->put_h0, f->stream), "column pass: stream event");
-      HIP_TRY(hipStreamWaitEvent(cs, g->put_h0, 0), "column pass: stream order");
-      g->h0_dirty = false;  // only once the wait is enqueued
-    }
-    // profiling a put: kind 3 brackets the wait + put kernels inside the column pass (kind 1)
-    Gen4Put timed_put = put ? *put : Gen4Put{};
-    EventPair pp{3, nullptr, nullptr};
-    if (put && g->profiling)
-    {
-      pp.a = take_event(g);
-      pp.b = take_event(g);
-      timed_put.start = pp.a;
-    }
-    if (uses_gen4(g))
-      HIP_TRY(timed(g, 1, [&] {
-                return launch_gen4_columns(f->logn, fp, g->g4, g->h0, g->ranks > 1 ? g->h0row : nullptr,
-                                           put && put->parts ? put->parts : g->parts, out ? (void*)out : (void*)g->xbuf,
-                                           f->twiddles, f->tw2, cs, f->cus, put ? &timed_put : nullptr);
-              }, cs),
-              "column pass (half spectrum, four-step)");
-    else
-      HIP_TRY(timed(g, 1, [&] {
-                return launch_half_slab_columns(f->logn, fp, g->hsl, g->ranks, g->h0, g->ranks == 1, g->h0row,
-                                                out ? (void*)out : (void*)g->xbuf, f->twiddles, cs, f->cus, g->hs,
-                                                f->device_cus, put ? &timed_put : nullptr);
-              }, cs),
-              "column pass (half spectrum, strip-dealt)");
-    if (pp.a)
-    {
-      HIP_TRY(hipEventRecord(pp.b, put && put->stream ? put->stream : cs), "column pass: put event");
-      g->pending.push_back(pp);
-    }
-    for (hipEvent_t* ev : {&g->cols_ev, &g->h0r_ev})
-      if (!*ev)
-        HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming), "column pass: event");
-    HIP_TRY(hipEventRecord(g->cols_ev, cs), "column pass: end event");
-    // the h0 readers end on the put stream when step 2 runs there (it waited for step 1's handoff)
-    HIP_TRY(hipEventRecord(g->h0r_ev, put && put->stream ? put->stream : cs), "column pass: end event");
-    g->cols_ev_valid = true;
-  }
-  else if (put)
-    return fail(OCEAN_ERR_INVALID, "column pass: the one-sided exchange needs a half-spectrum slab path (N >= 1024)");
-  else if (g->half && g->overlap)
-  {
-    // frame overlap: this column pass on the side stream into field slot oslot, after the row pass
-    // that last read the slot, and after any h0 / seed-constant writes on the generator's stream
-    const int s = g->oslot;
-    if (g->h0_dirty)
-    {
-      HIP_TRY(hipEventRecord(g->oh0, f->stream), "overlap: h0 event");
-      HIP_TRY(hipStreamWaitEvent(g->side, g->oh0, 0), "overlap: h0 wait");
-      g->h0_dirty = false;
-    }
-    if (g->orows_valid[s])
-      HIP_TRY(hipStreamWaitEvent(g->side, g->orows[s], 0), "overlap: slot wait");
-    HIP_TRY(timed(g, 1, [&] {
-              return launch_half_columns(f->logn, fp, g->h0, s ? g->gab2 : g->gab, s ? g->gcd2 : g->gcd,
-                                         s ? g->ge2 : g->ge, s ? g->spec2 : g->spec, f->twiddles, g->side, f->cus,
-                                         g->hs, f->device_cus, seed, g->h0_block);
-            }, g->side),
-            "column pass (half spectrum, overlapped)");
-    HIP_TRY(hipEventRecord(g->ocols[s], g->side), "overlap: column event");
-  }
-  else if (g->half)
-    HIP_TRY(timed(g, 1, [&] {
-              return launch_half_columns(f->logn, fp, g->h0, g->gab, g->gcd, g->ge, g->spec, f->twiddles, f->stream,
-                                         f->cus, g->hs, f->device_cus, seed, g->h0_block);
-            }),
-            "column pass (half spectrum)");
-  else
-    HIP_TRY(timed(g, 1, [&] {
-              return launch_cols_evolve(f->logn, fp, g->geom, g->h0, out, f->twiddles, f->stream, f->cus,
-                                        default_keep(f->logn));
-            }),
-            "column pass");
-  g->frame = fp;
-  return OCEAN_OK;
-}
-
-static FoamParams current_foam(const ocean_generator* g)
-{
-  FoamParams foam{};
-  for (int c = 0; c < g->cascades; c++)
-    foam.displacement[c] = g->settings[c].displacement;
-  return foam;
-}
-
-// Second half: the x direction of both EncodeIFFTs + computeFoam (src/Generator.cpp:71-80). `frame_foam`:
-// the displacement of a pipelined slab frame's own settings (null: the current settings).
-// row_stream (half-spectrum slab paths; null: the generator's stream): the pipelined one-sided frame's rows.
-// row_cus (> 0): the CUs the row stream may use (a CU-masked stream), which sizes resident grids.
-static int generator_rows(ocean_generator* g, const float4* in, const FoamParams* frame_foam = nullptr,
-                          hipStream_t row_stream = nullptr, int row_cus = 0)
-{
-  ocean_fft* f = g->fft;
-  g->mips_fresh = false;  // every frame path's maps are written here
-  g->bounds_fresh = false;
-  const int rcus = row_cus > 0 && row_cus < f->cus ? row_cus : f->cus;
-  const FoamParams foam = frame_foam ? *frame_foam : current_foam(g);
-  if (uses_gen4(g))
-  {
-    hipStream_t rs = row_stream ? row_stream : f->stream;
-    HIP_TRY(timed(g, 2, [&] {
-              return launch_gen4_rows(f->logn, g->frame, g->g4, in ? (const void*)in : (const void*)g->xbuf, g->maps,
-                                      g->jac, foam, f->twiddles, f->tw2, rs, rcus);
-            }, rs),
-            "row pass (half spectrum, four-step)");
-  }
-  else if (g->hslab)
-  {
-    hipStream_t rs = row_stream ? row_stream : f->stream;
-    HIP_TRY(timed(g, 2, [&] {
-              return launch_half_slab_rows(f->logn, g->frame, g->hsl, in ? (const void*)in : (const void*)g->xbuf,
-                                           g->rm_ab, g->rm_de, g->rm_c, g->maps, g->jac, foam, f->twiddles,
-                                           f->tw2, rs, rcus);
-            }, rs),
-            "row pass (half spectrum, strip-dealt)");
-  }
-  else if (row_stream)
-    return fail(OCEAN_ERR_INVALID, "row pass: a row stream needs a half-spectrum slab path");
-  else if (g->half && g->overlap)
-  {
-    const int s = g->oslot;
-    HIP_TRY(hipStreamWaitEvent(f->stream, g->ocols[s], 0), "overlap: column wait");
-    HIP_TRY(timed(g, 2, [&] {
-              return launch_half_rows(f->logn, g->frame, s ? g->gab2 : g->gab, s ? g->gcd2 : g->gcd,
-                                      s ? g->ge2 : g->ge, s ? g->spec2 : g->spec, g->maps, g->jac, foam, f->twiddles,
-                                      f->stream, f->cus);
-            }),
-            "row pass (half spectrum, overlapped)");
-    HIP_TRY(hipEventRecord(g->orows[s], f->stream), "overlap: row event");
-    g->orows_valid[s] = true;
-    g->oslot = s ^ 1;
-  }
-  else if (g->half)
-    HIP_TRY(timed(g, 2, [&] {
-              return launch_half_rows(f->logn, g->frame, g->gab, g->gcd, g->ge, g->spec, g->maps, g->jac, foam,
-                                      f->twiddles, f->stream, f->cus);
-            }),
-            "row pass (half spectrum)");
-  else
-    HIP_TRY(timed(g, 2, [&] {
-              return launch_rows_final(f->logn, g->cascades, g->geom, in, g->scratch, g->maps, g->jac, foam,
-                                       f->twiddles, f->stream, f->cus);
-            }),
-            "row pass");
-  return OCEAN_OK;
-}
-
 int ocean_generator_set_half_spectrum(ocean_generator* g, int enable)
 {
   if (!g)
     return fail(OCEAN_ERR_INVALID, "ocean_generator_set_half_spectrum: null generator");
-  if (peers_pending(g->peers))
-  {
-    const int rc = ocean_peers_flush(g->peers);  // a pipelined one-sided frame in flight lands first
-    if (rc != OCEAN_OK)
-      return rc;
-  }
-  if (g->pending_slot >= 0)
-  {
-    // a pipelined slab frame's column pass wrote its blocks in the current path's layout: its row
-    // pass runs before the switch
-    const int rc = ocean_generator_slab_flush(g);
-    if (rc != OCEAN_OK)
-      return rc;
-  }
+  TRY(land_frames_in_flight(g));
   if (!enable && g->overlap)
-  {
-    const int rc = ocean_generator_set_frame_overlap(g, 0);
-    if (rc != OCEAN_OK)
-      return rc;
-  }
-  const int logn = g->fft->logn;
-  const bool blocked = !g->slab && half_spectrum_supported(logn);
-  const bool dealt = !blocked && half_slab_supported(logn) && (g->slab || logn > 12);
-  if (enable && !blocked && !dealt)
+    TRY(ocean_generator_set_frame_overlap(g, 0));
+  if (enable && g->half_kind == HalfKind::None)
     return fail(OCEAN_ERR_INVALID, "ocean_generator_set_half_spectrum: N = 1024 .. 16384 only");
-  const bool was_half = g->half, was_hslab = g->hslab;
-  g->half = enable && blocked;
-  g->hslab = enable && dealt;
-  hipError_t e = hipSuccess;
-  if (!enable)
-    e = full_buffers(g);
-  else if (blocked)
-    e = half_buffers(g);
-  else
-    e = hslab_buffers(g);
+  const bool was_on = g->half_on, was_slab_path = half_slab_path(g);
+  g->half_on = enable != 0;
+  const hipError_t e = path_buffers(g);
   if (e != hipSuccess)
   {
-    g->half = was_half;
-    g->hslab = was_hslab;
-    return fail(e == hipErrorOutOfMemory ? OCEAN_ERR_OOM : OCEAN_ERR_HIP,
-                std::string("ocean_generator_set_half_spectrum: ") + hipGetErrorString(e));
+    g->half_on = was_on;
+    return alloc_fail(e, "ocean_generator_set_half_spectrum");
   }
-  if ((was_hslab && g->ranks > 1) != (g->hslab && g->ranks > 1))
+  if ((was_slab_path && g->ranks > 1) != (half_slab_path(g) && g->ranks > 1))
     g->update_spectrum = true;  // a slab's h0 layout changes (its strips or columns <-> its column slab)
   return OCEAN_OK;
 }
@@ -1018,35 +998,27 @@ int ocean_generator_set_frame_overlap(ocean_generator* g, int enable)
 {
   if (!g)
     return fail(OCEAN_ERR_INVALID, "ocean_generator_set_frame_overlap: null generator");
-  if (enable && !g->half)
+  if (enable && frame_path(g) != FramePath::HalfBlocked)
     return fail(OCEAN_ERR_INVALID, "ocean_generator_set_frame_overlap: whole grids of N = 1024 .. 4096 on the "
                                    "half-spectrum path only");
   ocean_fft* f = g->fft;
   if (enable && !g->overlap)
   {
-    const size_t t = half_field_texels(f->logn) * g->cascades;
     hipError_t e = hipSuccess;
     if (!g->side)
       e = hipStreamCreateWithFlags(&g->side, hipStreamNonBlocking);
     for (hipEvent_t* ev : {&g->ocols[0], &g->ocols[1], &g->orows[0], &g->orows[1], &g->oh0})
       if (e == hipSuccess && !*ev)
         e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
-    if (e == hipSuccess && !g->gab2)
-      e = hipMalloc(&g->gab2, t * sizeof(float4));
-    if (e == hipSuccess && !g->gcd2)
-      e = hipMalloc(&g->gcd2, t * sizeof(float4));
-    if (e == hipSuccess && !g->ge2)
-      e = hipMalloc(&g->ge2, t * sizeof(float2));
-    if (e == hipSuccess && !g->spec2)
-      e = hipMalloc(&g->spec2, (size_t)g->cascades * 2 * f->n * sizeof(float4));
+    if (e == hipSuccess)
+      e = half_fields(g, 1);
     // the side stream starts after everything issued so far (the last column pass used slot 0 and hs)
     if (e == hipSuccess)
       e = hipEventRecord(g->oh0, f->stream);
     if (e == hipSuccess)
       e = hipStreamWaitEvent(g->side, g->oh0, 0);
     if (e != hipSuccess)
-      return fail(e == hipErrorOutOfMemory ? OCEAN_ERR_OOM : OCEAN_ERR_HIP,
-                  std::string("ocean_generator_set_frame_overlap: ") + hipGetErrorString(e));
+      return alloc_fail(e, "ocean_generator_set_frame_overlap");
     g->orows_valid[0] = g->orows_valid[1] = false;
     g->oslot = 0;
     g->h0_dirty = false;
@@ -1077,25 +1049,13 @@ int ocean_generator_set_four_step(ocean_generator* g, int enable)
 {
   if (!g)
     return fail(OCEAN_ERR_INVALID, "ocean_generator_set_four_step: null generator");
-  if (peers_pending(g->peers))
-  {
-    const int rc = ocean_peers_flush(g->peers);  // a pipelined one-sided frame in flight lands first
-    if (rc != OCEAN_OK)
-      return rc;
-  }
-  if (g->pending_slot >= 0)
-  {
-    const int rc = ocean_generator_slab_flush(g);  // as in ocean_generator_set_half_spectrum
-    if (rc != OCEAN_OK)
-      return rc;
-  }
+  TRY(land_frames_in_flight(g));
   g->four_step = enable != 0;  // h0 is re-laid out by the next frame if its strip width changes
-  if (g->hslab)
+  if (half_slab_path(g))
   {
     const hipError_t e = hslab_buffers(g);  // exchange_bytes reports the new path's size from here on
     if (e != hipSuccess)
-      return fail(e == hipErrorOutOfMemory ? OCEAN_ERR_OOM : OCEAN_ERR_HIP,
-                  std::string("ocean_generator_set_four_step: ") + hipGetErrorString(e));
+      return alloc_fail(e, "ocean_generator_set_four_step");
   }
   return OCEAN_OK;
 }
@@ -1104,27 +1064,33 @@ int ocean_generator_frame_bytes(const ocean_generator* g, double per_point[2])
 {
   if (!g || !per_point)
     return fail(OCEAN_ERR_INVALID, "ocean_generator_frame_bytes: null argument");
-  if (uses_gen4(g))
+  const double n = g->fft->n;
+  switch (const FramePath path = frame_path(g))
   {
-    // the kept columns u' in [0, N/2) and the Nyquist column: step 1 reads h0 (16) and writes 5
-    // complex fields (40), step 2 reads and writes them (40 + 40, into the exchange blocks) | the row
-    // pass reads them (40) and writes the maps + Jacobian (36)
-    const double n = g->fft->n, kept = (n / 2 + 1) / n;
-    per_point[0] = (16.0 + 40.0 + 80.0) * kept;
-    per_point[1] = 40.0 * kept + 36.0;
-  }
-  else if (g->half || g->hslab)
-  {
-    // h0 of the kept columns (half + the Nyquist strip) + 5 complex fields out; 5 fields in, maps +
-    // Jacobian; the strip-dealt path also moves the received fields to row-major (40 in + 40 out)
-    const double n = g->fft->n, kept = (n / 2 + spectrum_block(g->fft->logn)) / n;
-    per_point[0] = 16.0 * kept + 40.0 * kept;
-    per_point[1] = 40.0 * kept + 36.0 + (g->hslab ? 80.0 * kept : 0.0);
-  }
-  else
-  {
-    per_point[0] = 48.0;
-    per_point[1] = 68.0 + (rows_need_transpose(g->fft->logn) ? 64.0 : 0.0);  // B = 1: the tiled transpose
+    case FramePath::FourStep:
+    {
+      // the kept columns u' in [0, N/2) and the Nyquist column: step 1 reads h0 (16) and writes 5
+      // complex fields (40), step 2 reads and writes them (40 + 40, into the exchange blocks) | the row
+      // pass reads them (40) and writes the maps + Jacobian (36)
+      const double kept = (n / 2 + 1) / n;
+      per_point[0] = (16.0 + 40.0 + 80.0) * kept;
+      per_point[1] = 40.0 * kept + 36.0;
+      break;
+    }
+    case FramePath::HalfBlocked:
+    case FramePath::StripDealt:
+    {
+      // h0 of the kept columns (half + the Nyquist strip) + 5 complex fields out; 5 fields in, maps +
+      // Jacobian; the strip-dealt path also moves the received fields to row-major (40 in + 40 out)
+      const double kept = (n / 2 + spectrum_block(g->fft->logn)) / n;
+      per_point[0] = 16.0 * kept + 40.0 * kept;
+      per_point[1] = 40.0 * kept + 36.0 + (path == FramePath::StripDealt ? 80.0 * kept : 0.0);
+      break;
+    }
+    case FramePath::Full:
+      per_point[0] = 48.0;
+      per_point[1] = 68.0 + (rows_need_transpose(g->fft->logn) ? 64.0 : 0.0);  // B = 1: the tiled transpose
+      break;
   }
   return OCEAN_OK;
 }
@@ -1136,16 +1102,16 @@ int ocean_generator_calculate(ocean_generator* g, float timestep, int update_spe
   if (g->ranks != 1)
     return fail(OCEAN_ERR_INVALID, "ocean_generator_calculate: slab generators step with "
                                    "ocean_generator_slab_columns / exchange / ocean_generator_slab_rows");
-  float4* buf = g->hslab ? nullptr : g->inter;  // null: the strip-dealt path's own exchange buffer
-  int rc = generator_columns(g, timestep, update_spectrum, buf);
-  return rc != OCEAN_OK ? rc : generator_rows(g, buf);
+  float4* buf = own_exchange(g);
+  TRY(generator_columns(g, timestep, update_spectrum, buf));
+  return generator_rows(g, buf, current_frame(g));
 }
 
 size_t ocean_generator_exchange_bytes(const ocean_generator* g)
 {
   if (!g)
     return 0;
-  if (g->hslab)
+  if (half_slab_path(g))
     return hslab_xbuf_bytes(g);
   return (size_t)g->cascades * 2 * g->fft->n * g->geom.w * sizeof(float4);
 }
@@ -1154,857 +1120,14 @@ int ocean_generator_slab_columns(ocean_generator* g, float timestep, int update_
 {
   if (!g)
     return fail(OCEAN_ERR_INVALID, "ocean_generator_slab_columns: null generator");
-  return generator_columns(g, timestep, update_spectrum,
-                           send ? reinterpret_cast<float4*>(send) : (g->hslab ? nullptr : g->inter));
+  return generator_columns(g, timestep, update_spectrum, send ? reinterpret_cast<float4*>(send) : own_exchange(g));
 }
 
 int ocean_generator_slab_rows(ocean_generator* g, const float* recv)
 {
   if (!g)
     return fail(OCEAN_ERR_INVALID, "ocean_generator_slab_rows: null generator");
-  return generator_rows(g, recv ? reinterpret_cast<const float4*>(recv) : (g->hslab ? nullptr : g->inter));
-}
-
-// ---------------------------------------------------------------------------------------------
-// Slab exchange over RCCL: the equal-split all-to-all between the column and the row pass (SURVEY
-// §8e), as P grouped ncclSend / ncclRecv pairs of exchange_bytes / P on the generator's streams.
-// ---------------------------------------------------------------------------------------------
-}  // extern "C"
-
-struct ocean_comm
-{
-  ncclComm_t comm = nullptr;
-  int nranks = 0, rank = 0;
-  bool owned = false;
-};
-
-namespace
-{
-int nccl_fail(ncclResult_t r, const char* what)
-{
-  return fail(OCEAN_ERR_HIP, std::string(what) + ": " + ncclGetErrorString(r));
-}
-
-// The equal-split all-to-all of blk bytes per rank pair, enqueued on `stream`: one group of
-// ncclSend / ncclRecv pairs, each block in pieces of at most kExchangePiece bytes (RCCL 2.26 corrupted
-// a single send / receive above 1 GiB in a world-size-1 self exchange: tools/rccl_selfcheck.py,
-// profiles/r03_rccl_selfcheck.log; a whole 8192^2 block is 1.35 GB).
-constexpr size_t kExchangePiece = (size_t)512 << 20;
-
-int exchange_bytes_all_to_all(ocean_comm* c, const unsigned char* send, unsigned char* recv, size_t blk,
-                              hipStream_t stream)
-{
-  ncclResult_t r = ncclGroupStart();
-  for (int q = 0; q < c->nranks && r == ncclSuccess; q++)
-    for (size_t o = 0; o < blk && r == ncclSuccess; o += kExchangePiece)
-    {
-      const size_t len = std::min(kExchangePiece, blk - o);
-      r = ncclSend(send + q * blk + o, len, ncclUint8, q, c->comm, stream);
-      if (r == ncclSuccess)
-        r = ncclRecv(recv + q * blk + o, len, ncclUint8, q, c->comm, stream);
-    }
-  const ncclResult_t e = ncclGroupEnd();
-  if (r != ncclSuccess)
-    return nccl_fail(r, "slab exchange (ncclSend / ncclRecv)");
-  if (e != ncclSuccess)
-    return nccl_fail(e, "slab exchange (ncclGroupEnd)");
-  return OCEAN_OK;
-}
-
-// Enqueue this frame's all-to-all (send slot -> recv slot) on `stream`.
-int exchange_blocks(ocean_generator* g, ocean_comm* c, const unsigned char* send, unsigned char* recv,
-                    hipStream_t stream)
-{
-  return exchange_bytes_all_to_all(c, send, recv, ocean_generator_exchange_bytes(g) / g->ranks, stream);
-}
-
-// The two exchange slots, the comm stream and its events (first use, or after a path switch that
-// changed exchange_bytes).
-int frame_slots(ocean_generator* g)
-{
-  const size_t bytes = ocean_generator_exchange_bytes(g);
-  if (g->xslot_bytes < bytes)
-  {
-    if (g->pending_slot >= 0)
-      return fail(OCEAN_ERR_INVALID, "slab frame: the exchange size changed with a frame in flight (flush first)");
-    for (int k = 0; k < 2; k++)
-      for (unsigned char** p : {&g->xsend[k], &g->xrecv[k]})
-      {
-        if (*p)
-          (void)hipFree(*p);
-        *p = nullptr;
-      }
-    g->xslot_bytes = 0;
-    for (int k = 0; k < 2; k++)
-    {
-      HIP_TRY(hipMalloc(&g->xsend[k], bytes), "slab frame: exchange buffers");
-      HIP_TRY(hipMalloc(&g->xrecv[k], bytes), "slab frame: exchange buffers");
-    }
-    g->xslot_bytes = bytes;
-  }
-  if (!g->comm_stream)
-  {
-    HIP_TRY(hipStreamCreateWithFlags(&g->comm_stream, hipStreamNonBlocking), "slab frame: comm stream");
-    for (int k = 0; k < 2; k++)
-      for (hipEvent_t* ev : {&g->cols_done[k], &g->xchg_done[k], &g->rows_done[k]})
-        HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming), "slab frame: events");
-  }
-  return OCEAN_OK;
-}
-
-int check_comm(const ocean_generator* g, const ocean_comm* c, const char* who)
-{
-  if (!g || !c || !c->comm)
-    return fail(OCEAN_ERR_INVALID, std::string(who) + ": null generator or communicator");
-  if (c->nranks != g->ranks || c->rank != g->rank)
-    return fail(OCEAN_ERR_INVALID, std::string(who) + ": communicator rank " + std::to_string(c->rank) + " of " +
-                                       std::to_string(c->nranks) + " does not match slab rank " +
-                                       std::to_string(g->rank) + " of " + std::to_string(g->ranks));
-  return OCEAN_OK;
-}
-
-// Row pass of the frame in slot s (its own column-pass values: pipelined rows run after the next
-// frame's column pass).
-int slot_rows(ocean_generator* g, int s)
-{
-  ocean_fft* f = g->fft;
-  HIP_TRY(hipStreamWaitEvent(f->stream, g->xchg_done[s], 0), "slab frame: wait for the exchange");
-  const FrameParams newest = g->frame;
-  g->frame = g->slot_frame[s];
-  const int rc = generator_rows(g, reinterpret_cast<const float4*>(g->xrecv[s]), &g->slot_foam[s]);
-  g->frame = newest;
-  if (rc != OCEAN_OK)
-    return rc;
-  HIP_TRY(hipEventRecord(g->rows_done[s], f->stream), "slab frame: events");
-  g->rows_recorded[s] = true;
-  return OCEAN_OK;
-}
-
-// Column pass of frame f into slot f % 2 and its exchange on the comm stream.
-int slot_columns_and_exchange(ocean_generator* g, ocean_comm* c, float timestep, int update_spectrum, int& slot)
-{
-  ocean_fft* f = g->fft;
-  const int s = (int)(g->frames_issued % 2);
-  int rc = generator_columns(g, timestep, update_spectrum, reinterpret_cast<float4*>(g->xsend[s]));
-  if (rc != OCEAN_OK)
-    return rc;
-  g->slot_frame[s] = g->frame;
-  g->slot_foam[s] = current_foam(g);
-  HIP_TRY(hipEventRecord(g->cols_done[s], f->stream), "slab frame: events");
-  HIP_TRY(hipStreamWaitEvent(g->comm_stream, g->cols_done[s], 0), "slab frame: stream order");
-  if (g->rows_recorded[s])  // frame f - 2's row pass has finished reading recv[s]
-    HIP_TRY(hipStreamWaitEvent(g->comm_stream, g->rows_done[s], 0), "slab frame: stream order");
-  rc = exchange_blocks(g, c, g->xsend[s], g->xrecv[s], g->comm_stream);
-  if (rc != OCEAN_OK)
-    return rc;
-  HIP_TRY(hipEventRecord(g->xchg_done[s], g->comm_stream), "slab frame: events");
-  g->frames_issued++;
-  slot = s;
-  return OCEAN_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int ocean_comm_unique_id(unsigned char id[OCEAN_COMM_ID_BYTES])
-{
-  static_assert(OCEAN_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "RCCL unique id size");
-  if (!id)
-    return fail(OCEAN_ERR_INVALID, "ocean_comm_unique_id: null id");
-  ncclUniqueId u;
-  const ncclResult_t r = ncclGetUniqueId(&u);
-  if (r != ncclSuccess)
-    return nccl_fail(r, "ncclGetUniqueId");
-  std::memcpy(id, u.internal, NCCL_UNIQUE_ID_BYTES);
-  return OCEAN_OK;
-}
-
-int ocean_comm_create(ocean_comm** out, const unsigned char id[OCEAN_COMM_ID_BYTES], int nranks, int rank)
-{
-  if (!out || !id || nranks < 1 || rank < 0 || rank >= nranks)
-    return fail(OCEAN_ERR_INVALID, "ocean_comm_create: null argument or rank outside [0, nranks)");
-  *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(OCEAN_ERR_NO_DEVICE, "ocean_comm_create: no HIP device visible");
-  ncclUniqueId u;
-  std::memcpy(u.internal, id, NCCL_UNIQUE_ID_BYTES);
-  auto* c = new ocean_comm();
-  const ncclResult_t r = ncclCommInitRank(&c->comm, nranks, u, rank);
-  if (r != ncclSuccess)
-  {
-    delete c;
-    return nccl_fail(r, "ncclCommInitRank");
-  }
-  c->nranks = nranks;
-  c->rank = rank;
-  c->owned = true;
-  *out = c;
-  return OCEAN_OK;
-}
-
-int ocean_comm_wrap(ocean_comm** out, void* nccl_comm, int nranks, int rank)
-{
-  if (!out || !nccl_comm || nranks < 1 || rank < 0 || rank >= nranks)
-    return fail(OCEAN_ERR_INVALID, "ocean_comm_wrap: null argument or rank outside [0, nranks)");
-  *out = nullptr;
-  // the exchange addresses peers by these values: they must be the communicator's own
-  const ncclComm_t nc = static_cast<ncclComm_t>(nccl_comm);
-  int count = 0, user_rank = 0;
-  ncclResult_t r = ncclCommCount(nc, &count);
-  if (r == ncclSuccess)
-    r = ncclCommUserRank(nc, &user_rank);
-  if (r != ncclSuccess)
-    return nccl_fail(r, "ocean_comm_wrap: ncclCommCount / ncclCommUserRank");
-  if (count != nranks || user_rank != rank)
-    return fail(OCEAN_ERR_INVALID, "ocean_comm_wrap: the communicator is rank " + std::to_string(user_rank) + " of " +
-                                       std::to_string(count) + ", not rank " + std::to_string(rank) + " of " +
-                                       std::to_string(nranks));
-  auto* c = new ocean_comm();
-  c->comm = nc;
-  c->nranks = nranks;
-  c->rank = rank;
-  *out = c;
-  return OCEAN_OK;
-}
-
-int ocean_comm_destroy(ocean_comm* comm)
-{
-  if (!comm)
-    return OCEAN_OK;
-  ncclResult_t r = ncclSuccess;
-  if (comm->owned && comm->comm)
-    r = ncclCommDestroy(comm->comm);
-  delete comm;
-  return r == ncclSuccess ? OCEAN_OK : nccl_fail(r, "ncclCommDestroy");
-}
-
-int ocean_comm_all_to_all(ocean_comm* comm, const void* send, void* recv, size_t bytes, void* hip_stream)
-{
-  if (!comm || !comm->comm || (bytes > 0 && (!send || !recv)) || bytes % comm->nranks != 0)
-    return fail(OCEAN_ERR_INVALID, "ocean_comm_all_to_all: null argument or bytes not a multiple of the rank count");
-  return exchange_bytes_all_to_all(comm, static_cast<const unsigned char*>(send), static_cast<unsigned char*>(recv),
-                                   bytes / comm->nranks, (hipStream_t)hip_stream);
-}
-
-int ocean_generator_slab_frame(ocean_generator* g, ocean_comm* comm, float timestep, int update_spectrum)
-{
-  int rc = check_comm(g, comm, "ocean_generator_slab_frame");
-  if (rc == OCEAN_OK && g->pending_slot >= 0)
-    rc = ocean_generator_slab_flush(g);  // a pipelined frame in flight lands first
-  if (rc == OCEAN_OK)
-    rc = frame_slots(g);
-  int s = 0;
-  if (rc == OCEAN_OK)
-    rc = slot_columns_and_exchange(g, comm, timestep, update_spectrum, s);
-  return rc != OCEAN_OK ? rc : slot_rows(g, s);
-}
-
-int ocean_generator_slab_frame_pipelined(ocean_generator* g, ocean_comm* comm, float timestep, int update_spectrum)
-{
-  int rc = check_comm(g, comm, "ocean_generator_slab_frame_pipelined");
-  if (rc == OCEAN_OK)
-    rc = frame_slots(g);
-  int s = 0;
-  if (rc == OCEAN_OK)
-    rc = slot_columns_and_exchange(g, comm, timestep, update_spectrum, s);
-  if (rc != OCEAN_OK)
-    return rc;
-  if (g->pending_slot >= 0)
-  {
-    rc = slot_rows(g, g->pending_slot);
-    if (rc != OCEAN_OK)
-      return rc;
-  }
-  g->pending_slot = s;
-  return OCEAN_OK;
-}
-
-int ocean_generator_slab_flush(ocean_generator* g)
-{
-  if (!g)
-    return fail(OCEAN_ERR_INVALID, "ocean_generator_slab_flush: null generator");
-  if (g->pending_slot < 0)
-    return OCEAN_OK;
-  const int s = g->pending_slot;
-  g->pending_slot = -1;
-  return slot_rows(g, s);
-}
-
-// ---------------------------------------------------------------------------------------------
-// The one-sided slab exchange (ocean_peers): the four-step column pass stores block q into rank q's
-// receive slot through a peer mapping, and per-frame flag words replace the all-to-all (SURVEY §8e;
-// DESIGN.md §6 "one-sided exchange").
-// ---------------------------------------------------------------------------------------------
-}  // extern "C"
-
-namespace
-{
-constexpr int kMaxRanks = 16;
-constexpr int kReadyWord = 0, kFreedWord = 16, kReleaseCounter = 40, kErrWord = 48, kFlagWords = 64;
-constexpr uint32_t kPeerMagic = 0x4f505231;  // "OPR1"
-
-struct PeerHandle
-{
-  uint32_t magic;
-  int32_t rank, ranks;
-  uint32_t flags_uncached;
-  uint64_t slot_bytes;
-  hipIpcMemHandle_t data, flags;
-};
-static_assert(sizeof(PeerHandle) <= OCEAN_PEER_HANDLE_BYTES, "peer handle size");
-}  // namespace
-
-struct ocean_peers
-{
-  ocean_generator* g = nullptr;
-  int rank = 0, ranks = 1;
-  size_t blk = 0, slot = 0;        // block bytes, slot bytes (ranks * blk = the exchange bytes)
-  unsigned char* data = nullptr;   // this rank's two receive slots
-  uint32_t* flags = nullptr;       // this rank's flag words: ready[16] | freed[16] | .. | release counter @ 40 | err @ 48
-  bool flags_uncached = false;
-  unsigned char* peer_data[kMaxRanks] = {};
-  uint32_t* peer_flags[kMaxRanks] = {};
-  bool mapped[2 * kMaxRanks] = {};  // data / flags opened with hipIpcOpenMemHandle (closed on destroy)
-  bool connected = false;
-  uint64_t* table = nullptr;       // device: put destinations [2 slots][16], then the flag arrays [16]
-  // pipelined frames: step 1 on s1_stream into parts slot f % 2, the put on put_stream, the row pass
-  // on the generator's stream (ocean_peers_set_streams can replace the first two)
-  hipStream_t s1_stream = nullptr, put_stream = nullptr, row_stream = nullptr;
-  hipStream_t own_s1 = nullptr, own_put = nullptr, own_rows = nullptr;
-  int put_cus_per_xcd = 0;           // own streams CU-masked: the put on this many CUs of every XCD
-  int row_cus = 0;                   // the CUs the own row stream may use when masked (0: all)
-  int caller_row_cus = 0;            // ocean_peers_set_row_cus: the caller's row stream's CUs (0: all)
-  hipEvent_t rows_done = nullptr;    // pipelined rows on row_stream -> the generator's stream
-  hipEvent_t gen_ready = nullptr;    // the generator's stream -> pipelined rows (caller work on the maps)
-  bool failed = false;               // a wait timed out (ocean_peers_synchronize): frames are refused
-  unsigned char* parts2 = nullptr;   // step 1's second parts slot
-  hipEvent_t s1_done[2] = {nullptr, nullptr}, put_done[2] = {nullptr, nullptr};
-  bool put_done_valid[2] = {false, false};
-  long long deadline = 0;          // wall-clock ticks
-  int timeout_ms = 20000;
-  int put_cus = 0;
-  int64_t frames = 0;              // frames whose column pass was issued
-  int64_t rows = 0;                // frames whose row pass was issued
-  FrameParams slot_frame[2]{};
-  FoamParams slot_foam[2]{};
-};
-
-namespace
-{
-int peers_deadline(ocean_peers* p)
-{
-  int khz = 0;
-  HIP_TRY(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, p->g ? p->g->fft->device : 0),
-          "ocean_peers: wall clock rate");
-  p->deadline = (long long)(khz > 0 ? khz : 100000) * p->timeout_ms;
-  return OCEAN_OK;
-}
-
-int check_peers(const ocean_generator* g, const ocean_peers* p, const char* who)
-{
-  if (!g || !p || p->g != g)
-    return fail(OCEAN_ERR_INVALID, std::string(who) + ": null generator, or peers created for another generator");
-  if (!p->connected)
-    return fail(OCEAN_ERR_INVALID, std::string(who) + ": ocean_peers_connect has not run");
-  if (p->failed)
-    return fail(OCEAN_ERR_TIMEOUT, std::string(who) + ": a one-sided wait timed out earlier (ocean_peers_synchronize "
-                                                      "reported it); the ranks' flags are out of step: destroy and "
-                                                      "recreate the peers");
-  if (!g->hslab || hslab_xbuf_bytes(g) != p->slot)
-    return fail(OCEAN_ERR_INVALID, std::string(who) + ": the generator left the half-spectrum slab path (or its "
-                                                      "exchange size changed) since ocean_peers_create");
-  return OCEAN_OK;
-}
-
-// the device table: dst[s][q] = rank q's slot s + this rank's block offset, then the flag arrays
-int peers_table(ocean_peers* p)
-{
-  uint64_t host[3 * kMaxRanks] = {};
-  for (int s = 0; s < 2; s++)
-    for (int q = 0; q < p->ranks; q++)
-      host[s * kMaxRanks + q] = (uint64_t)(uintptr_t)(p->peer_data[q] + s * p->slot + (size_t)p->rank * p->blk);
-  for (int q = 0; q < p->ranks; q++)
-    host[2 * kMaxRanks + q] = (uint64_t)(uintptr_t)p->peer_flags[q];
-  HIP_TRY(hipMemcpy(p->table, host, sizeof(host), hipMemcpyHostToDevice), "ocean_peers: destination table");
-  p->connected = true;
-  return OCEAN_OK;
-}
-
-PeerWait peer_wait(ocean_peers* p, int word0, int64_t target)
-{
-  return PeerWait{p->flags, word0, p->ranks, (uint32_t)target, p->deadline, p->flags + kErrWord};
-}
-
-uint32_t* const* flag_table(const ocean_peers* p)
-{
-  return reinterpret_cast<uint32_t* const*>(p->table + 2 * kMaxRanks);
-}
-
-// Column pass of frame f = p->frames into every rank's slot f % 2, then this rank's "ready" word (f + 1)
-// in every rank's flags. The put waits until every rank has finished reading that slot (frame f - 2's
-// row pass). Serial: all on the generator's stream. Pipelined: step 1 on s1_stream into parts slot f % 2
-// (after the put of frame f - 2 read that slot), the put on put_stream after step 1, so step 1 of frame
-// f + 1 and the row pass of frame f - 1 run beside the put of frame f.
-int put_columns(ocean_generator* g, ocean_peers* p, float timestep, int update_spectrum, bool pipelined)
-{
-  ocean_fft* fs = g->fft;
-  const int64_t f = p->frames;
-  const int s = (int)(f % 2);
-  const PeerWait w = peer_wait(p, kFreedWord, f - 1);
-  Gen4Put put{p->table + s * kMaxRanks, f >= 2 ? &w : nullptr, p->put_cus};
-  hipStream_t cs = nullptr;
-  if (pipelined && uses_gen4(g))
-  {
-    if (!p->parts2)
-      HIP_TRY(hipMalloc(&p->parts2, gen4_parts_bytes(fs->logn, g->cascades, g->g4)), "one-sided exchange: parts slot");
-    cs = p->s1_stream;
-    put.parts = s ? p->parts2 : g->parts;
-    put.stream = p->put_stream;
-    put.handoff = p->s1_done[s];
-    if (p->put_done_valid[s])
-      HIP_TRY(hipStreamWaitEvent(cs, p->put_done[s], 0), "one-sided exchange: parts slot reuse");
-  }
-  else if (pipelined)
-    cs = p->put_stream;  // the strip-dealt pass stores its blocks itself: all of it on the put stream
-  else
-    for (int k = 0; k < 2; k++)  // a serial frame after pipelined ones: its step 1 rewrites parts slot 0
-      if (p->put_done_valid[k])
-      {
-        HIP_TRY(hipStreamWaitEvent(fs->stream, p->put_done[k], 0), "one-sided exchange: stream order");
-        p->put_done_valid[k] = false;
-      }
-  int rc = generator_columns(g, timestep, update_spectrum, nullptr, &put, cs);
-  if (rc != OCEAN_OK)
-    return rc;
-  hipStream_t ps = pipelined ? p->put_stream : fs->stream;
-  HIP_TRY(launch_peer_signal_release(flag_table(p), p->ranks, kReadyWord + p->rank, (uint32_t)(f + 1),
-                                     p->flags + kReleaseCounter, ps),
-          "one-sided exchange: ready signal");
-  if (pipelined)
-  {
-    HIP_TRY(hipEventRecord(p->put_done[s], ps), "one-sided exchange: events");
-    p->put_done_valid[s] = true;
-  }
-  p->slot_frame[s] = g->frame;
-  p->slot_foam[s] = current_foam(g);
-  p->frames = f + 1;
-  return OCEAN_OK;
-}
-
-// Row pass of the oldest frame whose rows are not issued yet: wait for every rank's blocks, rows, then
-// this rank's "freed" word (f + 1) in every rank's flags. Serial: on the generator's stream. Pipelined:
-// on the peers' row stream, which the generator's stream then waits for (the maps stay ordered on it).
-int put_rows(ocean_generator* g, ocean_peers* p, bool pipelined = false)
-{
-  ocean_fft* f = g->fft;
-  const int64_t fr = p->rows;
-  if (fr >= p->frames)
-    return fail(OCEAN_ERR_INVALID, "ocean_generator_slab_put_rows: no column pass issued for this frame");
-  const int s = (int)(fr % 2);
-  hipStream_t rs = pipelined ? p->row_stream : f->stream;
-  if (rs != f->stream)
-  {
-    // the row pass rewrites g->maps / jac: after the caller's work on the generator's stream (the
-    // header keeps the maps ordered there)
-    HIP_TRY(hipEventRecord(p->gen_ready, f->stream), "one-sided exchange: events");
-    HIP_TRY(hipStreamWaitEvent(rs, p->gen_ready, 0), "one-sided exchange: stream order");
-  }
-  HIP_TRY(launch_peer_wait(peer_wait(p, kReadyWord, fr + 1), rs), "one-sided exchange: ready wait");
-  const FrameParams newest = g->frame;
-  g->frame = p->slot_frame[s];
-  const int rc = generator_rows(g, reinterpret_cast<const float4*>(p->data + s * p->slot), &p->slot_foam[s], rs,
-                                rs == p->own_rows ? p->row_cus : p->caller_row_cus);
-  g->frame = newest;
-  if (rc != OCEAN_OK)
-    return rc;
-  HIP_TRY(launch_peer_signal(flag_table(p), p->ranks, kFreedWord + p->rank, (uint32_t)(fr + 1), rs),
-          "one-sided exchange: freed signal");
-  if (rs != f->stream)
-  {
-    HIP_TRY(hipEventRecord(p->rows_done, rs), "one-sided exchange: events");
-    HIP_TRY(hipStreamWaitEvent(f->stream, p->rows_done, 0), "one-sided exchange: stream order");
-  }
-  p->rows = fr + 1;
-  return OCEAN_OK;
-}
-
-// (Re)create the peers' own streams; with put_cus_per_xcd > 0 CU-masked: the put stream on that many
-// CUs of every XCD, the step-1 and row streams on the others. A hipExtStreamCreateWithCUMask bit c is
-// CU c / 8 of XCD c % 8, and an XCD whose bits are all clear runs on all its CUs (workgroups are dealt
-// to every XCD whatever the mask; tools/xcdmask, profiles/r05_xcdprobe.log): a mask can only split
-// each XCD, so the put takes the same share of each.
-int peers_streams(ocean_peers* p)
-{
-  for (hipStream_t* st : {&p->own_s1, &p->own_put, &p->own_rows})
-    if (*st)
-    {
-      HIP_TRY(hipStreamSynchronize(*st), "ocean_peers: streams");
-      HIP_TRY(hipStreamDestroy(*st), "ocean_peers: streams");
-      *st = nullptr;
-    }
-  const int cus = p->g->fft->device_cus;
-  if (p->put_cus_per_xcd > 0 && cus % 8 == 0 && p->put_cus_per_xcd < cus / 8)
-  {
-    std::vector<uint32_t> put((cus + 31) / 32, 0u), rest((cus + 31) / 32, 0u);
-    for (int c = 0; c < cus; c++)
-      (c / 8 < p->put_cus_per_xcd ? put : rest)[c / 32] |= 1u << (c % 32);
-    HIP_TRY(hipExtStreamCreateWithCUMask(&p->own_put, (uint32_t)put.size(), put.data()), "ocean_peers: put stream");
-    HIP_TRY(hipExtStreamCreateWithCUMask(&p->own_s1, (uint32_t)rest.size(), rest.data()), "ocean_peers: column stream");
-    HIP_TRY(hipExtStreamCreateWithCUMask(&p->own_rows, (uint32_t)rest.size(), rest.data()), "ocean_peers: row stream");
-    p->row_cus = cus - 8 * p->put_cus_per_xcd;  // resident row-pass grids sized to the masked stream
-  }
-  else
-  {
-    for (hipStream_t* st : {&p->own_s1, &p->own_put, &p->own_rows})
-      HIP_TRY(hipStreamCreateWithFlags(st, hipStreamNonBlocking), "ocean_peers: streams");
-    p->row_cus = 0;
-  }
-  p->s1_stream = p->own_s1;
-  p->put_stream = p->own_put;
-  p->row_stream = p->own_rows;
-  p->put_done_valid[0] = p->put_done_valid[1] = false;
-  return OCEAN_OK;
-}
-
-void peers_release(ocean_peers* p)
-{
-  for (hipStream_t st : {p->s1_stream, p->put_stream, p->row_stream})
-    if (st)
-      (void)hipStreamSynchronize(st);
-  if (p->g && p->g->fft)
-    (void)hipStreamSynchronize(p->g->fft->stream);
-  for (int q = 0; q < kMaxRanks; q++)
-  {
-    if (p->mapped[q] && p->peer_data[q])
-      (void)hipIpcCloseMemHandle(p->peer_data[q]);
-    if (p->mapped[kMaxRanks + q] && p->peer_flags[q])
-      (void)hipIpcCloseMemHandle(p->peer_flags[q]);
-    p->mapped[q] = p->mapped[kMaxRanks + q] = false;
-  }
-}
-}  // namespace
-
-// a column pass whose row pass is not issued yet (a pipelined frame in flight)
-static bool peers_pending(const ocean_peers* p) { return p && p->rows < p->frames; }
-
-// called by ocean_generator_destroy: a generator destroyed before its peers leaves them unusable
-static void peers_detach(ocean_peers* p)
-{
-  if (!p)
-    return;
-  for (hipStream_t st : {p->s1_stream, p->put_stream, p->row_stream})
-    if (st)
-      (void)hipStreamSynchronize(st);
-  p->g = nullptr;
-  p->connected = false;
-}
-
-extern "C" {
-
-int ocean_peers_create(ocean_peers** out, ocean_generator* g)
-{
-  if (!out || !g)
-    return fail(OCEAN_ERR_INVALID, "ocean_peers_create: null argument");
-  *out = nullptr;
-  if (!g->slab || !g->hslab)
-    return fail(OCEAN_ERR_INVALID, "ocean_peers_create: a slab generator on a half-spectrum path (N >= 1024)");
-  if (g->peers)
-    return fail(OCEAN_ERR_INVALID, "ocean_peers_create: the generator already has peers");
-  hipError_t e = hslab_buffers(g);
-  if (e != hipSuccess)
-    return hip_fail(e, "ocean_peers_create: generator buffers");
-  auto* p = new ocean_peers();
-  p->g = g;
-  p->rank = g->rank;
-  p->ranks = g->ranks;
-  p->slot = hslab_xbuf_bytes(g);
-  p->blk = p->slot / g->ranks;
-  e = hipMalloc(&p->data, 2 * p->slot);
-  // the flag words in uncached memory: polled by one wave, written by the peers over xGMI
-  if (e == hipSuccess)
-  {
-    if (hipExtMallocWithFlags((void**)&p->flags, kFlagWords * sizeof(uint32_t), hipDeviceMallocUncached) == hipSuccess)
-      p->flags_uncached = true;
-    else
-    {
-      (void)hipGetLastError();
-      e = hipMalloc(&p->flags, kFlagWords * sizeof(uint32_t));
-    }
-  }
-  if (e == hipSuccess)
-    e = hipMalloc(&p->table, 3 * kMaxRanks * sizeof(uint64_t));
-  if (e == hipSuccess)
-    e = hipMemset(p->flags, 0, kFlagWords * sizeof(uint32_t));
-  for (int k = 0; k < 2 && e == hipSuccess; k++)
-  {
-    e = hipEventCreateWithFlags(&p->s1_done[k], hipEventDisableTiming);
-    if (e == hipSuccess)
-      e = hipEventCreateWithFlags(&p->put_done[k], hipEventDisableTiming);
-  }
-  if (e == hipSuccess)
-    e = hipEventCreateWithFlags(&p->rows_done, hipEventDisableTiming);
-  if (e == hipSuccess)
-    e = hipEventCreateWithFlags(&p->gen_ready, hipEventDisableTiming);
-  if (e == hipSuccess)
-    e = hipDeviceSynchronize();
-  int rc = e == hipSuccess ? peers_deadline(p) : OCEAN_OK;
-  if (rc == OCEAN_OK && e == hipSuccess)
-    rc = peers_streams(p);
-  if (e != hipSuccess || rc != OCEAN_OK)
-  {
-    const int code = e == hipErrorOutOfMemory ? OCEAN_ERR_OOM : OCEAN_ERR_HIP;
-    p->g = nullptr;
-    ocean_peers_destroy(p);
-    return rc != OCEAN_OK ? rc : fail(code, std::string("ocean_peers_create: ") + hipGetErrorString(e));
-  }
-  p->peer_data[p->rank] = p->data;
-  p->peer_flags[p->rank] = p->flags;
-  g->peers = p;
-  *out = p;
-  return OCEAN_OK;
-}
-
-int ocean_peers_destroy(ocean_peers* p)
-{
-  if (!p)
-    return OCEAN_OK;
-  peers_release(p);
-  if (p->g)
-    p->g->peers = nullptr;
-  for (hipStream_t st : {p->own_s1, p->own_put, p->own_rows})
-    if (st)
-      (void)hipStreamDestroy(st);
-  for (int k = 0; k < 2; k++)
-    for (hipEvent_t ev : {p->s1_done[k], p->put_done[k]})
-      if (ev)
-        (void)hipEventDestroy(ev);
-  for (hipEvent_t ev : {p->rows_done, p->gen_ready})
-    if (ev)
-      (void)hipEventDestroy(ev);
-  for (void* q : {(void*)p->data, (void*)p->flags, (void*)p->table, (void*)p->parts2})
-    if (q)
-      (void)hipFree(q);
-  delete p;
-  return OCEAN_OK;
-}
-
-int ocean_peers_handle(const ocean_peers* p, unsigned char handle[OCEAN_PEER_HANDLE_BYTES])
-{
-  if (!p || !handle)
-    return fail(OCEAN_ERR_INVALID, "ocean_peers_handle: null argument");
-  PeerHandle h{};
-  h.magic = kPeerMagic;
-  h.rank = p->rank;
-  h.ranks = p->ranks;
-  h.flags_uncached = p->flags_uncached ? 1 : 0;
-  h.slot_bytes = p->slot;
-  HIP_TRY(hipIpcGetMemHandle(&h.data, p->data), "ocean_peers_handle: hipIpcGetMemHandle (slots)");
-  HIP_TRY(hipIpcGetMemHandle(&h.flags, p->flags), "ocean_peers_handle: hipIpcGetMemHandle (flags)");
-  std::memset(handle, 0, OCEAN_PEER_HANDLE_BYTES);
-  std::memcpy(handle, &h, sizeof(h));
-  return OCEAN_OK;
-}
-
-int ocean_peers_connect(ocean_peers* p, const unsigned char* handles)
-{
-  if (!p || !handles || !p->g)
-    return fail(OCEAN_ERR_INVALID, "ocean_peers_connect: null argument or detached peers");
-  if (p->connected)
-    return fail(OCEAN_ERR_INVALID, "ocean_peers_connect: already connected");
-  for (int q = 0; q < p->ranks; q++)
-  {
-    PeerHandle h;
-    std::memcpy(&h, handles + (size_t)q * OCEAN_PEER_HANDLE_BYTES, sizeof(h));
-    if (h.magic != kPeerMagic || h.rank != q || h.ranks != p->ranks || h.slot_bytes != p->slot)
-      return fail(OCEAN_ERR_INVALID, "ocean_peers_connect: handle " + std::to_string(q) + " is not rank " +
-                                         std::to_string(q) + " of " + std::to_string(p->ranks) +
-                                         " with this grid's slot size");
-    if (q == p->rank)
-      continue;
-    void* d = nullptr;
-    void* fl = nullptr;
-    hipError_t e = hipIpcOpenMemHandle(&d, h.data, hipIpcMemLazyEnablePeerAccess);
-    if (e == hipSuccess)
-    {
-      p->peer_data[q] = static_cast<unsigned char*>(d);
-      p->mapped[q] = true;
-      e = hipIpcOpenMemHandle(&fl, h.flags, hipIpcMemLazyEnablePeerAccess);
-    }
-    if (e == hipSuccess)
-    {
-      p->peer_flags[q] = static_cast<uint32_t*>(fl);
-      p->mapped[kMaxRanks + q] = true;
-    }
-    if (e != hipSuccess)
-    {
-      peers_release(p);
-      return hip_fail(e, ("ocean_peers_connect: hipIpcOpenMemHandle of rank " + std::to_string(q)).c_str());
-    }
-  }
-  return peers_table(p);
-}
-
-int ocean_peers_connect_local(ocean_peers* const* all, int ranks)
-{
-  if (!all || ranks < 1 || ranks > kMaxRanks)
-    return fail(OCEAN_ERR_INVALID, "ocean_peers_connect_local: null array or ranks outside [1, 16]");
-  for (int q = 0; q < ranks; q++)
-    if (!all[q] || !all[q]->g || all[q]->rank != q || all[q]->ranks != ranks || all[q]->slot != all[0]->slot ||
-        all[q]->connected)
-      return fail(OCEAN_ERR_INVALID, "ocean_peers_connect_local: entry " + std::to_string(q) +
-                                         " is not an unconnected rank " + std::to_string(q) + " of " +
-                                         std::to_string(ranks) + " of one grid");
-  for (int r = 0; r < ranks; r++)
-  {
-    for (int q = 0; q < ranks; q++)
-    {
-      all[r]->peer_data[q] = all[q]->data;
-      all[r]->peer_flags[q] = all[q]->flags;
-    }
-    const int rc = peers_table(all[r]);
-    if (rc != OCEAN_OK)
-      return rc;
-  }
-  return OCEAN_OK;
-}
-
-int ocean_peers_set_timeout(ocean_peers* p, int ms)
-{
-  if (!p || ms < 1)
-    return fail(OCEAN_ERR_INVALID, "ocean_peers_set_timeout: null peers or ms < 1");
-  p->timeout_ms = ms;
-  return peers_deadline(p);
-}
-
-int ocean_peers_set_put_cus(ocean_peers* p, int cus)
-{
-  if (!p || !p->g || cus < 0 || cus > p->g->fft->device_cus)
-    return fail(OCEAN_ERR_INVALID, "ocean_peers_set_put_cus: null peers or CUs outside [0, device CUs]");
-  p->put_cus = cus;
-  return OCEAN_OK;
-}
-
-int ocean_peers_set_streams(ocean_peers* p, void* column_stream, void* put_stream, void* row_stream)
-{
-  if (!p || !p->g)
-    return fail(OCEAN_ERR_INVALID, "ocean_peers_set_streams: null or detached peers");
-  if (p->rows < p->frames)
-    return fail(OCEAN_ERR_INVALID, "ocean_peers_set_streams: a pipelined frame is in flight (flush first)");
-  for (hipStream_t st : {p->s1_stream, p->put_stream, p->row_stream})
-    HIP_TRY(hipStreamSynchronize(st), "ocean_peers_set_streams");
-  p->s1_stream = column_stream ? (hipStream_t)column_stream : p->own_s1;
-  p->put_stream = put_stream ? (hipStream_t)put_stream : p->own_put;
-  p->row_stream = row_stream ? (hipStream_t)row_stream : p->own_rows;
-  p->put_done_valid[0] = p->put_done_valid[1] = false;  // the old streams are drained
-  return OCEAN_OK;
-}
-
-int ocean_peers_set_row_cus(ocean_peers* p, int cus)
-{
-  if (!p || !p->g || cus < 0)
-    return fail(OCEAN_ERR_INVALID, "ocean_peers_set_row_cus: null peers or negative CUs");
-  p->caller_row_cus = cus;
-  return OCEAN_OK;
-}
-
-int ocean_peers_set_put_cu_mask(ocean_peers* p, int cus_per_xcd)
-{
-  if (!p || !p->g || cus_per_xcd < 0 || cus_per_xcd >= p->g->fft->device_cus / 8)
-    return fail(OCEAN_ERR_INVALID, "ocean_peers_set_put_cu_mask: null peers or CUs per XCD outside [0, CUs / 8)");
-  if (p->rows < p->frames)
-    return fail(OCEAN_ERR_INVALID, "ocean_peers_set_put_cu_mask: a pipelined frame is in flight (flush first)");
-  const bool own = p->s1_stream == p->own_s1 && p->put_stream == p->own_put && p->row_stream == p->own_rows;
-  if (!own)
-    return fail(OCEAN_ERR_INVALID, "ocean_peers_set_put_cu_mask: the caller's streams are in use (ocean_peers_set_streams)");
-  p->put_cus_per_xcd = cus_per_xcd;
-  return peers_streams(p);
-}
-
-int ocean_generator_slab_put_columns(ocean_generator* g, ocean_peers* p, float timestep, int update_spectrum)
-{
-  int rc = check_peers(g, p, "ocean_generator_slab_put_columns");
-  if (rc == OCEAN_OK && g->pending_slot >= 0)
-    rc = ocean_generator_slab_flush(g);  // an RCCL pipelined frame in flight lands first
-  return rc != OCEAN_OK ? rc : put_columns(g, p, timestep, update_spectrum, false);
-}
-
-int ocean_generator_slab_put_rows(ocean_generator* g, ocean_peers* p)
-{
-  const int rc = check_peers(g, p, "ocean_generator_slab_put_rows");
-  return rc != OCEAN_OK ? rc : put_rows(g, p);
-}
-
-int ocean_generator_slab_frame_put(ocean_generator* g, ocean_peers* p, float timestep, int update_spectrum)
-{
-  int rc = check_peers(g, p, "ocean_generator_slab_frame_put");
-  if (rc == OCEAN_OK && g->pending_slot >= 0)
-    rc = ocean_generator_slab_flush(g);
-  while (rc == OCEAN_OK && p->rows < p->frames)  // a pipelined frame in flight lands first
-    rc = put_rows(g, p);
-  if (rc == OCEAN_OK)
-    rc = put_columns(g, p, timestep, update_spectrum, false);
-  return rc != OCEAN_OK ? rc : put_rows(g, p);
-}
-
-int ocean_generator_slab_frame_put_pipelined(ocean_generator* g, ocean_peers* p, float timestep, int update_spectrum)
-{
-  int rc = check_peers(g, p, "ocean_generator_slab_frame_put_pipelined");
-  if (rc == OCEAN_OK && g->pending_slot >= 0)
-    rc = ocean_generator_slab_flush(g);
-  if (rc == OCEAN_OK)
-    rc = put_columns(g, p, timestep, update_spectrum, true);
-  while (rc == OCEAN_OK && p->rows < p->frames - 1)  // frame f - 1's row pass beside frame f's columns
-    rc = put_rows(g, p, true);
-  return rc;
-}
-
-int ocean_peers_flush(ocean_peers* p)
-{
-  if (!p || !p->g)
-    return fail(OCEAN_ERR_INVALID, "ocean_peers_flush: null or detached peers");
-  int rc = OCEAN_OK;
-  while (rc == OCEAN_OK && p->rows < p->frames)
-    rc = put_rows(p->g, p, true);
-  return rc;
-}
-
-int ocean_peers_synchronize(ocean_peers* p)
-{
-  if (!p)
-    return fail(OCEAN_ERR_INVALID, "ocean_peers_synchronize: null peers");
-  HIP_TRY(hipStreamSynchronize(p->s1_stream), "ocean_peers_synchronize: column stream");
-  HIP_TRY(hipStreamSynchronize(p->put_stream), "ocean_peers_synchronize: put stream");
-  HIP_TRY(hipStreamSynchronize(p->row_stream), "ocean_peers_synchronize: row stream");
-  if (p->g)
-    HIP_TRY(hipStreamSynchronize(p->g->fft->stream), "ocean_peers_synchronize: generator stream");
-  uint32_t err = 0;
-  HIP_TRY(hipMemcpy(&err, p->flags + kErrWord, sizeof(err), hipMemcpyDeviceToHost), "ocean_peers_synchronize: status");
-  if (err != 0)
-  {
-    // The word is sticky on the device (every later wait returns at once). Now that the streams are
-    // drained it is cleared, and the peers refuse further frames (check_peers): after a timeout the
-    // ranks' ready / freed counts no longer agree, so the only way on is a new peers object.
-    p->failed = true;
-    HIP_TRY(hipMemset(p->flags + kErrWord, 0, sizeof(uint32_t)), "ocean_peers_synchronize: clear status");
-    HIP_TRY(hipDeviceSynchronize(), "ocean_peers_synchronize: clear status");
-    return fail(OCEAN_ERR_TIMEOUT, std::string("one-sided exchange: a wait for the peers' ") +
-                                       (err - 1 == kReadyWord ? "blocks (ready)" : "slot release (freed)") +
-                                       " timed out after " + std::to_string(p->timeout_ms) +
-                                       " ms; the frames since then are invalid, and this peers object refuses new "
-                                       "frames");
-  }
-  return p->failed ? fail(OCEAN_ERR_TIMEOUT, "one-sided exchange: an earlier wait timed out; recreate the peers")
-                   : OCEAN_OK;
-}
-
-int ocean_peers_debug_slot(const ocean_peers* p, int slot, void** ptr, size_t* bytes)
-{
-  if (!p || !ptr || !bytes || slot < 0 || slot > 1)
-    return fail(OCEAN_ERR_INVALID, "ocean_peers_debug_slot: null argument or slot outside {0, 1}");
-  *ptr = p->data + (size_t)slot * p->slot;
-  *bytes = p->slot;
-  return OCEAN_OK;
+  return generator_rows(g, recv ? reinterpret_cast<const float4*>(recv) : own_exchange(g), current_frame(g));
 }
 
 int ocean_slab_layout(size_t texture_size, int rank, int ranks, int half, int64_t out[6])

@@ -1,6 +1,7 @@
-// ocean_capi_internal.h — what the translation units of the C ABI (ocean_capi.cpp, ocean_capi_surface.cpp)
-// share: the plan and the generator behind the opaque handles of include/oceanfft.h, and the error string
-// with the helpers that set it.
+// ocean_capi_internal.h — what the translation units of the C ABI (ocean_capi.cpp, ocean_capi_exchange.cpp,
+// ocean_capi_surface.cpp) share: the plan and the generator behind the opaque handles of include/oceanfft.h,
+// the frame-path selector, the error string with the helpers that set it, and the generator unit's passes
+// that the exchanges drive.
 #pragma once
 
 #include "oceanfft.h"
@@ -19,6 +20,41 @@ struct __attribute__((visibility("hidden"))) EventPair
 {
   int kind;
   hipEvent_t a, b;
+};
+
+// A frame's own values: its column pass's per-cascade values (the row pass needs dk) and the displacement
+// of the settings it was issued with. They travel with the frame: a pipelined frame's row pass is issued
+// after the next frame's column pass.
+struct FrameState
+{
+  FrameParams frame{};
+  FoamParams foam{};
+};
+
+// One slot of the blocked half path's y-transformed fields (DESIGN.md's names)
+struct HalfFields
+{
+  float4* gab = nullptr;   // [cascade][strip][N][4]: (H, kz H) for u >= 0 + Nyquist strip
+  float4* gde = nullptr;   // (kz H/|k|, kz^2 H/|k|)
+  float2* gc = nullptr;    // H/|k|
+  float4* spec = nullptr;  // [cascade][2][N]: the Nyquist-row term R
+};
+
+// The half-spectrum path a generator's size and kind admit (half_kind_of), decided once at creation
+enum class HalfKind
+{
+  None,
+  Blocked,  // whole grids of N = 1024 .. 4096
+  Dealt     // slabs of N >= 1024 and whole grids of N = 8192 / 16384: strip-dealt or four-step
+};
+
+// The frame path a generator runs (frame_path)
+enum class FramePath
+{
+  Full,
+  HalfBlocked,
+  StripDealt,
+  FourStep
 };
 
 struct ocean_fft
@@ -53,18 +89,20 @@ struct ocean_generator
   float4* scratch = nullptr;    // [cascade][2][w][N] row-major, only when B == 1 (N = 16384)
   float4* maps = nullptr;       // [cascade][2][w][N]: heightMap, displacementMap rows (row-major)
   float* jac = nullptr;         // [cascade][w][N]
-  // half-spectrum path (ranks == 1, N = 1024 .. 4096; ocean_generator_set_half_spectrum)
-  bool half = false;
-  FrameParams frame{};    // the last column pass's per-cascade values (the row pass needs dk)
+  // The frame path (frame_path below) follows from these three: the half path of this size and kind,
+  // whether the half spectrum is enabled (ocean_generator_set_half_spectrum), and, at N = 8192 / 16384,
+  // the four-step column pass writing destination-block order (launch_gen4_columns / _rows, default) or
+  // the strip-dealt column pass + transposes (ocean_generator_set_four_step; kept while the half
+  // spectrum is off)
+  HalfKind half_kind = HalfKind::None;
+  bool half_on = false;
+  bool four_step = true;
+  FrameParams frame{};     // the newest column pass's per-cascade values
   float2* hs = nullptr;    // pass-1 H scratch, half_hs_bytes(logn, device CUs)
-  float4* gab = nullptr;  // [cascade][strip][N][4]: y-transformed (H, kz H) for u >= 0 + Nyquist strip
-  float4* gcd = nullptr;  // (kz H/|k|, kz^2 H/|k|)
-  float2* ge = nullptr;   // H/|k|
-  float4* spec = nullptr; // [cascade][2][N]: the Nyquist-row term R
-  // half-spectrum paths of slabs (N >= 1024) and of whole grids of N = 8192 / 16384: the four-step
-  // column pass (gen4, N = 8192 / 16384, default) or the strip-dealt one (hsl)
-  bool hslab = false;
+  // blocked half path: the fields; slot 1 only with frame overlap (frame f in slot f % 2)
+  HalfFields fields[2];
   bool slab = false;  // created by ocean_generator_create_slab (also with ranks == 1)
+  // half-spectrum slab paths: the strip-dealt geometry (hsl) and the four-step one (g4)
   HalfSlab hsl{};
   Gen4Geom g4{};
   float4* h0row = nullptr;                            // slabs: [cascade][N], row y = 0 of every column
@@ -79,9 +117,6 @@ struct ocean_generator
   std::vector<unsigned char> seedc_host; // what seedc holds
   bool h0_stale = false;                 // the h0 image is not written yet (materialise_h0)
   std::vector<ocean_settings> seed_settings;  // the settings the last fused re-seed evaluated
-  // N = 8192 / 16384: the four-step column pass writing destination-block order (launch_gen4_columns
-  // / _rows); off: the strip-dealt column pass + transposes. ocean_generator_set_four_step.
-  bool four_step = true;
   int h0_block = 0;                          // strip width the h0 image was last written with
   std::vector<ocean_settings> h0_settings;   // the settings it was written from
   // the settings h0 was last seeded from (written or fused): a requested re-seed with the same
@@ -97,8 +132,7 @@ struct ocean_generator
   hipEvent_t cols_done[2] = {nullptr, nullptr}, xchg_done[2] = {nullptr, nullptr}, rows_done[2] = {nullptr, nullptr};
   bool rows_recorded[2] = {false, false};
   int pending_slot = -1;           // slot whose row pass is still to be issued
-  FrameParams slot_frame[2]{};     // the column pass's per-cascade values of the frame in each slot
-  FoamParams slot_foam[2]{};       // and the settings' displacement its row pass uses
+  FrameState slot_state[2];        // the frame in each slot
   int64_t frames_issued = 0;
   // the one-sided exchange bound to this generator (ocean_peers_create), and the event that orders its
   // put stream after h0 writes on the generator's stream
@@ -117,8 +151,6 @@ struct ocean_generator
   // slot f % 2, beside frame f - 1's row pass on the generator's stream
   bool overlap = false;
   hipStream_t side = nullptr;
-  float4 *gab2 = nullptr, *gcd2 = nullptr, *spec2 = nullptr;
-  float2* ge2 = nullptr;
   hipEvent_t ocols[2] = {nullptr, nullptr}, orows[2] = {nullptr, nullptr}, oh0 = nullptr;
   bool orows_valid[2] = {false, false};
   int oslot = 0;
@@ -167,7 +199,77 @@ inline int hip_fail(hipError_t e, const char* what)
       return hip_fail(e_, what);                                                                   \
   } while (0)
 
-// After fused re-seed frames the h0 image is still to be written: writes it (ocean_capi.cpp)
-extern "C" int materialise_h0(ocean_generator* g);
+// A step that failed has set the message: its status is the entry point's
+#define TRY(expr)                                                                                  \
+  do                                                                                               \
+  {                                                                                                \
+    const int rc_ = (expr);                                                                        \
+    if (rc_ != OCEAN_OK)                                                                           \
+      return rc_;                                                                                  \
+  } while (0)
+
+// A failed allocation (or a HIP call beside one): out of memory has its own status
+inline int alloc_fail(hipError_t e, const std::string& who)
+{
+  return fail(e == hipErrorOutOfMemory ? OCEAN_ERR_OOM : OCEAN_ERR_HIP, who + ": " + hipGetErrorString(e));
+}
+
+// Allocates `ptr` if it is still null and no earlier step of the chain (`e`) has failed
+template <typename T>
+hipError_t alloc_if_null(T*& ptr, size_t bytes, hipError_t e = hipSuccess)
+{
+  if (e != hipSuccess || ptr)
+    return e;
+  e = hipMalloc(&ptr, bytes);
+  if (e != hipSuccess)
+    ptr = nullptr;
+  return e;
+}
+
+// The one rule for which half path a size and kind of generator has
+inline HalfKind half_kind_of(int logn, bool slab)
+{
+  if (!slab && half_spectrum_supported(logn))
+    return HalfKind::Blocked;
+  return half_slab_supported(logn) && (slab || logn > 12) ? HalfKind::Dealt : HalfKind::None;
+}
+
+inline FramePath frame_path(const ocean_generator* g)
+{
+  if (!g->half_on || g->half_kind == HalfKind::None)
+    return FramePath::Full;
+  if (g->half_kind == HalfKind::Blocked)
+    return FramePath::HalfBlocked;
+  return g->four_step && gen4_supported(g->fft->logn) ? FramePath::FourStep : FramePath::StripDealt;
+}
+
+// the strip-dealt or the four-step path: exchange blocks in their own layouts, one-sided exchange
+inline bool half_slab_path(const ocean_generator* g)
+{
+  const FramePath p = frame_path(g);
+  return p == FramePath::StripDealt || p == FramePath::FourStep;
+}
+
+// ---- ocean_capi.cpp, for the other units ----
+// After fused re-seed frames the h0 image is still to be written: writes it
+int materialise_h0(ocean_generator* g);
+// The buffers of the current half-spectrum slab path (a path switch allocates here) and its exchange bytes
+hipError_t hslab_buffers(ocean_generator* g);
+size_t hslab_xbuf_bytes(const ocean_generator* g);
+// The two halves of CalculateOcean. Columns: `put` (half-slab paths, the one-sided exchange) stores into
+// the peers' receive slots, on col_stream (null: the generator's stream). Rows: of the frame `fs`, on
+// row_stream (half-slab paths; null: the generator's stream) sized for row_cus CUs (0: the plan's budget).
+int generator_columns(ocean_generator* g, float timestep, int update_spectrum, float4* out,
+                      const Gen4Put* put = nullptr, hipStream_t col_stream = nullptr);
+int generator_rows(ocean_generator* g, const float4* in, const FrameState& fs, hipStream_t row_stream = nullptr,
+                   int row_cus = 0);
+// The newest column pass's frame, with the current settings' displacement
+FrameState current_frame(const ocean_generator* g);
+
+// ---- ocean_capi_exchange.cpp, for the generator ----
+// a column pass whose row pass is not issued yet (a pipelined one-sided frame in flight)
+bool peers_pending(const ocean_peers* p);
+// called by ocean_generator_destroy: a generator destroyed before its peers leaves them unusable
+void peers_detach(ocean_peers* p);
 
 #pragma GCC visibility pop

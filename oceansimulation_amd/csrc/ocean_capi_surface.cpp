@@ -1,7 +1,8 @@
 // ocean_capi_surface.cpp — the part of the C ABI (include/oceanfft.h) that consumes a generator's maps:
 // the map getters, ocean_surface_sample / _query / _sample_plane, the mip pyramids and the *_lod requests,
 // the rate maps and ocean_surface_velocity, the bounds and ocean_surface_raycast, and the hull sets.
-// The plans and generators themselves are in ocean_capi.cpp; ocean_capi_internal.h has what both share.
+// The plans and generators themselves are in ocean_capi.cpp, their exchanges in ocean_capi_exchange.cpp;
+// ocean_capi_internal.h has what the three share.
 //
 // Every request checks its arguments in the order its contract lists them, and every message starts with
 // the entry point's name (`who`); the checks more than one entry point makes are written once, below.
@@ -18,34 +19,15 @@
 #include "ocean_capi_internal.h"
 #include "ocean_internal.h"
 
-// A step that failed has set the message: its status is the entry point's
-#define TRY(expr)                                                                                  \
-  do                                                                                               \
-  {                                                                                                \
-    const int rc_ = (expr);                                                                        \
-    if (rc_ != OCEAN_OK)                                                                           \
-      return rc_;                                                                                  \
-  } while (0)
-
 namespace
 {
-
-int alloc_fail(hipError_t e, const std::string& who)
-{
-  return fail(e == hipErrorOutOfMemory ? OCEAN_ERR_OOM : OCEAN_ERR_HIP, who + ": " + hipGetErrorString(e));
-}
 
 // A generator's buffer that is allocated on first use
 template <typename T>
 int alloc_once(T*& ptr, size_t bytes, const std::string& who)
 {
-  if (ptr)
-    return OCEAN_OK;
-  const hipError_t e = hipMalloc(&ptr, bytes);
-  if (e == hipSuccess)
-    return OCEAN_OK;
-  ptr = nullptr;
-  return alloc_fail(e, who);
+  const hipError_t e = alloc_if_null(ptr, bytes);
+  return e == hipSuccess ? OCEAN_OK : alloc_fail(e, who);
 }
 
 // A generator that holds whole maps and, with `frame`, has calculated a frame

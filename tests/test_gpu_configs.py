@@ -374,6 +374,86 @@ def test_path_switch_lands_pending_pipelined_frame(ocean):
     fft.close()
 
 
+def test_half_spectrum_toggle_mid_run_equals_fixed_paths(ocean):
+    """ocean_generator_set_half_spectrum off and on again in the middle of a run, with no settings edits.
+    (a) Whole grids of 1024^2 x 2 cascades on one plan: a generator that runs half, full, full, half, then
+    half with frame overlap gives, after every frame, the bits (maps and Jacobian) of the generator held on
+    that path, and after every switch its frame_bytes and spectrum block. (b) Two slab ranks of one 1024^2
+    grid in one process: strip-dealt, full-spectrum and strip-dealt frames (each switch re-seeds the slab's
+    h0 in the new layout) give the rows of the whole-grid generator held on that path bit for bit, and each
+    rank's exchange_bytes is the host-computed ocean_slab_layout value of the path."""
+    from oceansimulation_amd import capi
+    from oceansimulation_amd.hip import DeviceBuffer
+    from oceansimulation_amd.slab import SlabGenerator, emulate_frame, slab_layout
+
+    L = capi.lib()
+    n, C = 1024, 2
+    steps = [0.25, 1.0 / 60.0, 0.5, 1.0 / 60.0, 2.0]
+    maps = ("height_map_host", "displacement_map_host", "jacobian_map_host")
+    fft = ocean.FFTCalculator(n)
+    half, full, sw = (ocean.Generator(fft, C) for _ in range(3))
+    for g in (half, full, sw):
+        for c, size in enumerate((17.0, 101.0)):
+            ocean.apply_settings(g.GetOceanSettings(c), planeSize=size)
+    full.set_half_spectrum(False)
+    fixed = {True: half, False: full}
+
+    def same_path(k, on_half):
+        want = fixed[on_half]
+        assert sw.frame_bytes() == want.frame_bytes(), (k, sw.frame_bytes(), want.frame_bytes())
+        blocks = [int(L.ocean_generator_spectrum_block(g.handle)) for g in (sw, want)]
+        assert blocks[0] == blocks[1], (k, blocks)
+
+    def same_frame(k, on_half):
+        for c in range(C):
+            for get in maps:
+                assert np.array_equal(getattr(sw, get)(c), getattr(fixed[on_half], get)(c)), (k, on_half, c, get)
+
+    script = [True, False, False, True, True]
+    for k, (dt, on_half) in enumerate(zip(steps, script)):
+        if k > 0 and on_half != script[k - 1]:
+            sw.set_half_spectrum(on_half)
+            same_path(k, on_half)
+        if k == 4:
+            sw.set_frame_overlap(True)
+            same_path(k, True)
+        for g in (half, full, sw):
+            g.CalculateOcean(dt)
+        same_frame(k, on_half)
+    sw.set_frame_overlap(False)
+    same_path(5, True)
+    same_frame(5, True)
+    sw.close()
+
+    # (b) one grid as two slab ranks, beside a whole grid held on each path
+    P, w = 2, n // 2
+    whole_half, whole_full = ocean.Generator(fft, 1), ocean.Generator(fft, 1)
+    whole_full.set_half_spectrum(False)
+    slabs = [SlabGenerator(fft, r, P) for r in range(P)]
+    for s in [g.GetOceanSettings() for g in slabs] + [whole_half.GetOceanSettings(0), whole_full.GetOceanSettings(0)]:
+        ocean.apply_settings(s, planeSize=17.0)
+    layout_bytes = {on: [slab_layout(n, r, P, half=int(on))[5] for r in range(P)] for on in (True, False)}
+    room = max(max(v) for v in layout_bytes.values())
+    sends, recvs = [DeviceBuffer(room) for _ in slabs], [DeviceBuffer(room) for _ in slabs]
+    for k, (dt, on_half) in enumerate(zip(steps[:3], (True, False, True))):
+        if k > 0:
+            for g in slabs:
+                g.set_half_spectrum(on_half)
+        assert [g.exchange_bytes for g in slabs] == layout_bytes[on_half], (k, on_half)
+        emulate_frame(slabs, sends, recvs, dt, update_ocean=(k == 0))
+        whole_half.CalculateOcean(dt)
+        whole_full.CalculateOcean(dt)
+        want = whole_half if on_half else whole_full
+        for get in maps:
+            got = np.concatenate([getattr(g, get)() for g in slabs])
+            assert got.shape[0] == P * w and np.array_equal(got, getattr(want, get)(0)), (k, on_half, get)
+    for buf in sends + recvs:
+        buf.free()
+    for g in slabs + [whole_half, whole_full, half, full]:
+        g.close()
+    fft.close()
+
+
 # ---- bench.py --gpus N on a one-GPU box ---------------------------------------------------------
 def test_bench_gpus_two_shared_gpu_reports_two_ranks(tmp_path):
     """`bench.py --gpus 2 --shared-gpu` (no launcher) starts 2 ranks under torch.distributed.run,
