@@ -646,6 +646,82 @@ int ocean_hulls_loads(ocean_hulls* hulls, ocean_generator* const* gens, const in
  * of at most 32 points share a wave (the same bits either way; tools/hulls_bench.py times both). */
 int ocean_debug_hulls_packing(int enable);
 
+/* ---- Persistent foam: per-cascade accumulation, coverage counts, sampler ------------------------
+ * The Jacobian map and slot 3 of the samplers say where the surface is folding now. Foam is a history:
+ * whitecaps are born where the surface compresses, ride with the water and fade over seconds. The
+ * reference declares that state (src/Generator.h:88-92: "we accumulate foam into a texture. This foam
+ * decays over time exponentially") and never builds it: computeFoam writes the instantaneous determinant
+ * and the fragment shader drops it. The maps are indexed by base point (a texel is the rest position of a
+ * water particle), so foam kept per texel rides with its particle: no advection pass. Like the Jacobian,
+ * foam is per cascade.
+ *
+ * Settings, per cascade; ocean_settings keeps its 64 bytes. The defaults (0.9, 8.0, 0.5, 0.5) are
+ * starting points, not measurements: the counts below exist to tune them.
+ *     bias   the Jacobian below which the surface feeds foam
+ *     gain   (1/s) foam per unit of (bias - J) per second
+ *     decay  (1/s) exponential decay rate
+ *     level  the foam value from which a texel counts as covered */
+typedef struct ocean_foam_settings {
+  float bias;
+  float gain;
+  float decay;
+  float level;
+} ocean_foam_settings;
+void ocean_default_foam_settings(ocean_foam_settings* out);
+/* Mutable, like ocean_generator_settings: read by the next ocean_generator_advance_foam. Null, with
+ * ocean_last_error set, for a null generator or a cascade out of range. */
+ocean_foam_settings* ocean_generator_foam_settings(ocean_generator* gen, int cascade);
+/* One step of every cascade's foam map. Contract, per cascade c and texel, with J the current Jacobian
+ * texel and F the foam texel (R32F, N*N, row-major, 0 at first), in unfused fp32:
+ *     a  = (float) exp(-(double)decay_c * (double)dt)      on the host, double libm exp, rounded once
+ *     s  = max(bias_c - J, 0.0f) * gain_c
+ *     t  = F * a + s * dt                                  three roundings: two products, one sum
+ *     F' = min(t, 1.0f)
+ *     breaking += (bias_c - J > 0);   covered += (F' >= level_c);   saturated += (t >= 1.0f)
+ * dt == 0 leaves F bit for bit unchanged (a = 1 and s * 0 = 0): the reference app's `Q` freeze. Maps
+ * holding NaN, and subnormal products, are unspecified.
+ * Enqueued on the generator's stream after the row pass that wrote the Jacobian it reads (the ordering
+ * of ocean_generator_build_bounds): two kernel launches, 12 B per point (J read, F read and written), no
+ * host synchronisation, no float and no integer atomics. It does not rewrite the maps, so mips, rates
+ * and bounds stay fresh. Foam is state, not a derived product: the next frame does not make it stale, and
+ * re-seeding h0 or editing settings does not clear it.
+ * The storage (4 B per point and cascade, the count table and 12 B per 2048 texels of partial counts) is
+ * allocated and zeroed on the first ocean_generator_advance_foam or ocean_generator_reset_foam
+ * (OCEAN_ERR_OOM when that fails) and freed by ocean_generator_destroy. Whole-grid generators only, every N
+ * in 16 .. 16384 and every frame path.
+ * OCEAN_ERR_INVALID, before any device call: a null generator; a slab generator; a generator that has
+ * calculated no frame yet; dt negative or non-finite; a cascade (named in the message) whose bias or level
+ * is non-finite or whose gain or decay is negative or non-finite. No reference counterpart. */
+int ocean_generator_advance_foam(ocean_generator* gen, float dt);
+/* Zeroes the foam maps and the counts, on the generator's stream. Allowed before any frame; allocates
+ * the storage on first use. OCEAN_ERR_INVALID for a null or a slab generator. */
+int ocean_generator_reset_foam(ocean_generator* gen);
+/* R32F N*N, row-major, device memory, valid until the generator is destroyed; the cascades' maps are
+ * consecutive. Null, with ocean_last_error set, for a null generator, a cascade out of range, and before
+ * the first ocean_generator_advance_foam or ocean_generator_reset_foam. */
+float* ocean_generator_foam_map(ocean_generator* gen, int cascade);
+/* Host copy of (breaking, covered, saturated) of one cascade's last step; all zeros after a reset.
+ * Synchronises the generator's stream. OCEAN_ERR_INVALID for a null generator or output, a cascade out of
+ * range, and before the first ocean_generator_advance_foam or ocean_generator_reset_foam. */
+int ocean_generator_foam_counts(ocean_generator* gen, int cascade, int64_t out[3]);
+/* The table [cascade][3] in device memory, valid until the generator is destroyed (the step's partial
+ * counts, uint32 [cascade][max(N*N / 2048, 1)][3], follow it). Null, with ocean_last_error set, for a null
+ * generator and before the first ocean_generator_advance_foam or ocean_generator_reset_foam. */
+const int64_t* ocean_generator_foam_counts_device(ocean_generator* gen);
+/* ocean_surface_sample / ocean_surface_sample_plane with the foam in slot 7, which those calls leave 0;
+ * the other seven floats are theirs bit for bit.
+ *     foam = sum over the pairs c, in order, of tap_c(F_c) / (float)count
+ * accumulated exactly as the fragment stage accumulates the Jacobian: at the displaced position, with
+ * the same taps and weights. Argument rules, (generator, cascade) rules and stream as
+ * ocean_surface_sample; the maps are sampled directly (no atlas). Every generator must have foam storage
+ * (an ocean_generator_advance_foam or ocean_generator_reset_foam): otherwise OCEAN_ERR_INVALID, naming the
+ * index of the generator in `gens`, before any device call. points == 0 launches nothing.
+ * No reference counterpart. */
+int ocean_surface_sample_foam(ocean_generator* const* gens, const int* cascades, int count, const float* xz,
+                              int64_t points, float* out);
+int ocean_surface_sample_plane_foam(ocean_generator* const* gens, const int* cascades, int count,
+                                    const float camera[5], int res, float* out);
+
 #ifdef __cplusplus
 }
 #endif

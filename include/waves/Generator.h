@@ -123,6 +123,19 @@ public:
   void BuildBounds();
   void GetBounds(float out[18]) const;
 
+  // Extension (the reference declares it, src/Generator.h:88-92, and never builds it): foam accumulated per
+  // texel and decaying exponentially (ocean_generator_advance_foam, oceanfft.h). AdvanceFoam(dt) enqueues
+  // one step from the current Jacobian map on the device's stream: call it after CalculateOcean(dt); dt = 0
+  // freezes the foam. ResetFoam zeroes it. GetFoamSettings is mutable like GetOceanSettings (bias, gain,
+  // decay, level; read by the next AdvanceFoam). GetFoamMap is an R32F N x N texture registered on first
+  // use; it throws before the first AdvanceFoam / ResetFoam. GetFoamCounts copies the last step's
+  // (breaking, covered, saturated) texel counts to the host (it waits for the stream).
+  void AdvanceFoam(float dt);
+  void ResetFoam();
+  ocean_foam_settings& GetFoamSettings();
+  Vision::ID GetFoamMap();
+  void GetFoamCounts(int64_t out[3]) const;
+
 private:
   Vision::RenderDevice* renderDevice = nullptr;
   FFTCalculator* fftCalc = nullptr;
@@ -137,6 +150,8 @@ private:
   // registered by the first CalculateRates
   Vision::ID heightRateMap = 0, displacementRateMap = 0;
   Vision::ID Rate(Vision::ID map) const;
+  // registered by the first GetFoamMap
+  Vision::ID foamMap = 0;
 };
 
 }  // namespace Waves

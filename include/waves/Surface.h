@@ -71,7 +71,15 @@ public:
   Vision::ID Raycast(const std::vector<Generator*>& generators, const float* raysDevice, int64_t rays, float step,
                      int maxSteps, int refine, int iterations, float tolerance, float slope, float pad);
 
+  // Sample with the persistent foam (ocean_surface_sample_plane_foam, oceanfft.h): the same mesh and the
+  // same texture layout as Sample, with the generators' averaged foam in the last float of each vertex,
+  // which Sample leaves 0. Every generator needs a Generator::AdvanceFoam() or ResetFoam() first. Its own
+  // texture, reused at the same res.
+  Vision::ID SampleFoam(const std::vector<Generator*>& generators, const float camera[5], int res);
+
 private:
+  Vision::ID verticesFoam = 0;
+  int verticesFoamRes = 0;
   Vision::ID rayHits = 0;
   int64_t rayCount = 0;
   Vision::RenderDevice* renderDevice = nullptr;

@@ -46,12 +46,27 @@ class OceanSettings(ctypes.Structure):
 
 assert ctypes.sizeof(OceanSettings) == 64
 
+
+class OceanFoamSettings(ctypes.Structure):
+    """ocean_foam_settings: one cascade's persistent-foam parameters, 16 bytes."""
+
+    _fields_ = [
+        ("bias", ctypes.c_float),
+        ("gain", ctypes.c_float),
+        ("decay", ctypes.c_float),
+        ("level", ctypes.c_float),
+    ]
+
+
+assert ctypes.sizeof(OceanFoamSettings) == 16
+
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _f = ctypes.c_float
 _sz = ctypes.c_size_t
 _fp = ctypes.POINTER(ctypes.c_float)
 _sp = ctypes.POINTER(OceanSettings)
+_fsp = ctypes.POINTER(OceanFoamSettings)
 
 # name -> (restype, argtypes); mirrors include/oceanfft.h one to one.
 SIGNATURES = {
@@ -106,6 +121,15 @@ SIGNATURES = {
     "ocean_generator_bounds": (_i, [_vp, _i, _fp]),
     "ocean_generator_bounds_device": (_vp, [_vp]),
     "ocean_surface_raycast": (_i, [_vp, _vp, _i, _vp, ctypes.c_int64, _f, _i, _i, _i, _f, _f, _f, _vp]),
+    "ocean_default_foam_settings": (None, [_fsp]),
+    "ocean_generator_foam_settings": (_fsp, [_vp, _i]),
+    "ocean_generator_advance_foam": (_i, [_vp, _f]),
+    "ocean_generator_reset_foam": (_i, [_vp]),
+    "ocean_generator_foam_map": (_vp, [_vp, _i]),
+    "ocean_generator_foam_counts": (_i, [_vp, _i, ctypes.POINTER(ctypes.c_int64)]),
+    "ocean_generator_foam_counts_device": (_vp, [_vp]),
+    "ocean_surface_sample_foam": (_i, [_vp, _vp, _i, _vp, ctypes.c_int64, _vp]),
+    "ocean_surface_sample_plane_foam": (_i, [_vp, _vp, _i, _vp, _i, _vp]),
     "ocean_hulls_create":(_i, [ctypes.POINTER(_vp), _vp, _vp, ctypes.c_int64, _vp, _i]),
     "ocean_hulls_destroy": (_i, [_vp]),
     "ocean_hulls_bodies": (_i, [_vp]),

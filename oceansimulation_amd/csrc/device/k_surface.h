@@ -68,6 +68,38 @@ __global__ __launch_bounds__(256) void k_surface(SurfaceParams p, SurfacePlane p
   }
 }
 
+// k_surface<false> with the persistent foam (ocean_surface_sample_foam, include/oceanfft.h) in slot 7: the
+// foam maps travel in an argument of their own, as the rate maps do; per tap and cascade one more dword
+// beside the nine of the two stages.
+__global__ __launch_bounds__(256) void k_surface_foam(SurfaceParams p, SurfaceFoam foam, SurfacePlane plane,
+                                                      const float2* __restrict__ xz, int64_t count,
+                                                      float4* __restrict__ out)
+{
+#pragma clang fp contract(off)
+  const SurfacePlaneTurn turn = surface_plane_turn(plane);
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < count;
+       idx += (int64_t)gridDim.x * blockDim.x)
+  {
+    float px, pz;
+    if (plane.res > 0)
+    {
+      float k;
+      surface_plane_point(plane, turn, idx, px, pz, k);
+    }
+    else
+    {
+      const float2 q = xz[idx];
+      px = q.x;
+      pz = q.y;
+    }
+    float py = 0.0f;
+    surface_vertex_stage<false>(p, px, py, pz);
+    const float4 f = surface_fragment_stage<false>(p, px, pz);
+    out[2 * idx] = make_float4(px, py, pz, f.w);
+    out[2 * idx + 1] = make_float4(f.x, f.y, f.z, surface_foam_stage(p, foam, px, pz));
+  }
+}
+
 // The inverse direction (ocean_surface_query, include/oceanfft.h): surface_base_point from a cold start
 // (one 16-B load per tap and cascade from the atlas, three dwords from the maps); the fragment stage runs
 // once, at the last V(p). A NaN residual keeps iterating and reaches slot 7.

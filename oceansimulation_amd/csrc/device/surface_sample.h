@@ -143,6 +143,21 @@ __device__ __forceinline__ float4 surface_fragment_stage(const SurfaceParams& p,
   return surface_normal(d[0], d[1], d[2], d[3], jac);
 }
 
+// The persistent foam at the displaced position (ocean_surface_sample_foam): the cascades' foam maps
+// accumulated exactly as the fragment stage above accumulates the Jacobian, same taps, weights and order
+__device__ __forceinline__ float surface_foam_stage(const SurfaceParams& p, const SurfaceFoam& f, float px, float pz)
+{
+#pragma clang fp contract(off)
+  float foam = 0.0f;
+  for (int c = 0; c < p.count; c++)
+  {
+    const float u = px / p.c[c].plane, v = pz / p.c[c].plane;
+    const LinearTaps k = linear_repeat_taps(p.n, u, v);
+    foam += linear_channel<1>(f.foam[c], k, 0) / (float)p.count;
+  }
+  return foam;
+}
+
 // The query's fixed point (ocean_surface_query, include/oceanfft.h): the base point p whose displaced
 // position V(p).xz is q, by p <- p + (q - V(p).xz), at most `iterations` steps, a lane stopping once
 // max|q - V(p).xz| <= tolerance. base_x, base_z enter as the start (q itself for a cold start) and leave as

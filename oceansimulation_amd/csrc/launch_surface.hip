@@ -1,5 +1,5 @@
 // launch_surface.hip — the point kernels of the surface consumer (device/k_surface.h): the atlas repack,
-// ocean_surface_sample[_plane], _query, _velocity and _sample[_plane]_lod, and the rules that decide when a
+// ocean_surface_sample[_plane], _sample[_plane]_foam, _query, _velocity and _sample[_plane]_lod, and the rules that decide when a
 // request samples the atlas.
 #include <cstdint>
 
@@ -49,6 +49,12 @@ hipError_t launch_surface(const SurfaceParams& p, const SurfacePlane& plane, con
                           float4* out, hipStream_t stream, int cus)
 {
   return launch_points_atlas(k_surface<true>, k_surface<false>, p, count, stream, cus, plane, xz, count, out);
+}
+
+hipError_t launch_surface_foam(const SurfaceParams& p, const SurfaceFoam& f, const SurfacePlane& plane, const float2* xz,
+                               int64_t count, float4* out, hipStream_t stream, int cus)
+{
+  return launch_points(k_surface_foam, count, stream, cus, p, f, plane, xz, count, out);
 }
 
 hipError_t launch_surface_query(const SurfaceParams& p, const float2* xz, int64_t count, int iterations,

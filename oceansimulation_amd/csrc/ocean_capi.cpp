@@ -449,6 +449,9 @@ int generator_alloc(ocean_generator** out, ocean_fft* fft, int cascades, int ran
   g->settings.resize(cascades);
   for (auto& s : g->settings)
     ocean_default_settings(&s);
+  g->foam_settings.resize(cascades);
+  for (auto& s : g->foam_settings)
+    ocean_default_foam_settings(&s);
   const size_t slab = (size_t)fft->n * g->geom.w;  // texels per cascade image slab
   g->slab = is_slab;
   g->half_kind = half_kind_of(fft->logn, is_slab);
@@ -946,7 +949,7 @@ int ocean_generator_destroy(ocean_generator* g)
                   (void*)g->xsend[1], (void*)g->xrecv[0], (void*)g->xrecv[1], (void*)f0.gab, (void*)f0.gde, (void*)f0.gc,
                   (void*)f0.spec, (void*)f1.gab, (void*)f1.gde, (void*)f1.gc, (void*)f1.spec, (void*)g->hs,
                   (void*)g->h0row, g->seedc, (void*)g->rm_ab, (void*)g->rm_de, (void*)g->rm_c, (void*)g->parts,
-                  (void*)g->xbuf, (void*)g->mips, (void*)g->rates, (void*)g->bounds})
+                  (void*)g->xbuf, (void*)g->mips, (void*)g->rates, (void*)g->bounds, (void*)g->foam, g->foam_counts})
     if (p)
       (void)hipFree(p);
   delete g;

@@ -167,6 +167,12 @@ struct ocean_generator
   // rows (bounds_floats), allocated on first use; fresh until the next call that rewrites the maps
   float* bounds = nullptr;
   bool bounds_fresh = false;
+  // persistent foam (ocean_generator_advance_foam): the settings of every cascade, the maps [cascade][N * N]
+  // and the counts (the int64 table [cascade][3], then stage 1's partial rows: foam_counts_bytes), allocated
+  // and zeroed on first use. State, not a derived product: no frame makes it stale
+  std::vector<ocean_foam_settings> foam_settings;
+  float* foam = nullptr;
+  void* foam_counts = nullptr;
   bool profiling = false;
   std::vector<EventPair> pending;
   std::vector<hipEvent_t> pool;

@@ -1,6 +1,7 @@
 // ocean_capi_surface.cpp — the part of the C ABI (include/oceanfft.h) that consumes a generator's maps:
 // the map getters, ocean_surface_sample / _query / _sample_plane, the mip pyramids and the *_lod requests,
-// the rate maps and ocean_surface_velocity, the bounds and ocean_surface_raycast, and the hull sets.
+// the rate maps and ocean_surface_velocity, the bounds and ocean_surface_raycast, the persistent foam with
+// ocean_surface_sample_foam, and the hull sets.
 // The plans and generators themselves are in ocean_capi.cpp, their exchanges in ocean_capi_exchange.cpp;
 // ocean_capi_internal.h has what the three share.
 //
@@ -471,6 +472,181 @@ int ocean_surface_raycast(ocean_generator* const* gens, const int* cascades, int
   HIP_TRY(launch_surface_raycast(p, r, reinterpret_cast<const float4*>(rays), n_rays, reinterpret_cast<float4*>(out),
                                  fft->stream, fft->cus),
           "ocean_surface_raycast");
+  return OCEAN_OK;
+}
+
+// ---- persistent foam: per-cascade accumulation, coverage counts, sampler ----
+void ocean_default_foam_settings(ocean_foam_settings* s)
+{
+  if (s)
+    *s = ocean_foam_settings{0.9f, 8.0f, 0.5f, 0.5f};
+}
+
+ocean_foam_settings* ocean_generator_foam_settings(ocean_generator* g, int c)
+{
+  if (!g || c < 0 || c >= g->cascades)
+  {
+    fail(OCEAN_ERR_INVALID, "ocean_generator_foam_settings: null generator or cascade out of range");
+    return nullptr;
+  }
+  return &g->foam_settings[c];
+}
+
+// The foam maps and counts of a whole-grid generator: allocated, and zeroed on its stream, on first use
+static int foam_storage(ocean_generator* g, const std::string& who)
+{
+  if (g->foam)
+    return OCEAN_OK;
+  ocean_fft* f = g->fft;
+  const size_t map_bytes = (size_t)g->cascades * f->n * f->n * sizeof(float);
+  const size_t count_bytes = foam_counts_bytes(f->n, g->cascades);
+  float* maps = nullptr;
+  void* counts = nullptr;
+  hipError_t e = alloc_if_null(maps, map_bytes);
+  e = alloc_if_null(counts, count_bytes, e);
+  if (e == hipSuccess)
+    e = hipMemsetAsync(maps, 0, map_bytes, f->stream);
+  if (e == hipSuccess)
+    e = hipMemsetAsync(counts, 0, count_bytes, f->stream);
+  if (e != hipSuccess)
+  {
+    if (maps || counts)
+      (void)hipStreamSynchronize(f->stream);  // a memset of the buffer about to be freed may be in flight
+    if (maps)
+      (void)hipFree(maps);
+    if (counts)
+      (void)hipFree(counts);
+    return alloc_fail(e, who);
+  }
+  g->foam = maps;
+  g->foam_counts = counts;
+  return OCEAN_OK;
+}
+
+int ocean_generator_advance_foam(ocean_generator* g, float dt)
+{
+  const std::string who = "ocean_generator_advance_foam";
+  TRY(whole_maps(g, true, who));
+  if (!(dt >= 0.0f) || !std::isfinite(dt))
+    return fail(OCEAN_ERR_INVALID, who + ": dt must be finite and >= 0");
+  FoamCascade fc[kMaxCascades];
+  for (int c = 0; c < g->cascades; c++)
+  {
+    const ocean_foam_settings& s = g->foam_settings[c];
+    if (!std::isfinite(s.bias) || !std::isfinite(s.level))
+      return fail(OCEAN_ERR_INVALID, who + ": cascade " + std::to_string(c) + " has a non-finite bias or level");
+    if (!(s.gain >= 0.0f) || !std::isfinite(s.gain) || !(s.decay >= 0.0f) || !std::isfinite(s.decay))
+      return fail(OCEAN_ERR_INVALID,
+                  who + ": cascade " + std::to_string(c) + " needs gain and decay finite and >= 0");
+    fc[c] = FoamCascade{(float)std::exp(-(double)s.decay * (double)dt), s.bias, s.gain, s.level, dt};
+  }
+  TRY(foam_storage(g, who));
+  ocean_fft* f = g->fft;
+  HIP_TRY(launch_foam_step(f->n, g->cascades, g->jac, g->foam, g->foam_counts, fc, f->stream, f->cus), who.c_str());
+  return OCEAN_OK;
+}
+
+int ocean_generator_reset_foam(ocean_generator* g)
+{
+  const std::string who = "ocean_generator_reset_foam";
+  TRY(whole_maps(g, false, who));
+  if (!g->foam)
+    return foam_storage(g, who);  // zeroed as allocated
+  ocean_fft* f = g->fft;
+  HIP_TRY(hipMemsetAsync(g->foam, 0, (size_t)g->cascades * f->n * f->n * sizeof(float), f->stream), who.c_str());
+  HIP_TRY(hipMemsetAsync(g->foam_counts, 0, foam_counts_bytes(f->n, g->cascades), f->stream), who.c_str());
+  return OCEAN_OK;
+}
+
+// A generator with foam storage, else null with a message
+static ocean_generator* generator_foam(ocean_generator* g, const char* who)
+{
+  if (!g)
+  {
+    fail(OCEAN_ERR_INVALID, std::string(who) + ": null generator");
+    return nullptr;
+  }
+  if (!g->foam)
+  {
+    fail(OCEAN_ERR_INVALID, std::string(who) + ": the generator has no foam yet (call ocean_generator_advance_foam or "
+                                               "ocean_generator_reset_foam)");
+    return nullptr;
+  }
+  return g;
+}
+
+float* ocean_generator_foam_map(ocean_generator* g, int c)
+{
+  if (!generator_foam(g, "ocean_generator_foam_map"))
+    return nullptr;
+  if (c < 0 || c >= g->cascades)
+  {
+    fail(OCEAN_ERR_INVALID, "ocean_generator_foam_map: cascade out of range");
+    return nullptr;
+  }
+  return g->foam + (size_t)g->fft->n * g->fft->n * c;
+}
+
+const int64_t* ocean_generator_foam_counts_device(ocean_generator* g)
+{
+  return generator_foam(g, "ocean_generator_foam_counts_device") ? static_cast<const int64_t*>(g->foam_counts) : nullptr;
+}
+
+int ocean_generator_foam_counts(ocean_generator* g, int cascade, int64_t out[3])
+{
+  if (!generator_foam(g, "ocean_generator_foam_counts"))
+    return OCEAN_ERR_INVALID;
+  if (cascade < 0 || cascade >= g->cascades || !out)
+    return fail(OCEAN_ERR_INVALID, "ocean_generator_foam_counts: cascade out of range or null output");
+  HIP_TRY(hipMemcpyAsync(out, static_cast<const int64_t*>(g->foam_counts) + (size_t)cascade * 3, 3 * sizeof(int64_t),
+                         hipMemcpyDeviceToHost, g->fft->stream),
+          "ocean_generator_foam_counts");
+  HIP_TRY(hipStreamSynchronize(g->fft->stream), "ocean_generator_foam_counts");
+  return OCEAN_OK;
+}
+
+// The foam maps of a request's cascades: every generator must have foam storage
+static int surface_foam(ocean_generator* const* gens, const int* cascades, int count, const ocean_fft* fft,
+                        SurfaceFoam& f, const char* who)
+{
+  f = SurfaceFoam{};
+  for (int i = 0; i < count; i++)
+  {
+    if (!gens[i]->foam)
+      return not_fresh(who, i, false, " has no foam (call", "", "ocean_generator_advance_foam or ocean_generator_reset_foam");
+    f.foam[i] = gens[i]->foam + (size_t)fft->n * fft->n * cascades[i];
+  }
+  return OCEAN_OK;
+}
+
+int ocean_surface_sample_foam(ocean_generator* const* gens, const int* cascades, int count, const float* xz,
+                              int64_t points, float* out)
+{
+  SurfaceParams p;
+  ocean_fft* fft;
+  SurfaceFoam f;
+  TRY(surface_params(gens, cascades, count, p, fft, "ocean_surface_sample_foam"));
+  TRY(surface_foam(gens, cascades, count, fft, f, "ocean_surface_sample_foam"));
+  TRY(check_points(points, xz, out, "ocean_surface_sample_foam"));
+  HIP_TRY(launch_surface_foam(p, f, SurfacePlane{}, reinterpret_cast<const float2*>(xz), points,
+                              reinterpret_cast<float4*>(out), fft->stream, fft->cus),
+          "ocean_surface_sample_foam");
+  return OCEAN_OK;
+}
+
+int ocean_surface_sample_plane_foam(ocean_generator* const* gens, const int* cascades, int count,
+                                    const float camera[5], int res, float* out)
+{
+  SurfaceParams p;
+  ocean_fft* fft;
+  SurfaceFoam f;
+  SurfacePlane plane;
+  int64_t pts;
+  TRY(surface_params(gens, cascades, count, p, fft, "ocean_surface_sample_plane_foam"));
+  TRY(surface_foam(gens, cascades, count, fft, f, "ocean_surface_sample_plane_foam"));
+  TRY(plane_request(camera, res, out, "ocean_surface_sample_plane_foam", plane, pts));
+  HIP_TRY(launch_surface_foam(p, f, plane, nullptr, pts, reinterpret_cast<float4*>(out), fft->stream, fft->cus),
+          "ocean_surface_sample_plane_foam");
   return OCEAN_OK;
 }
 

@@ -315,6 +315,37 @@ struct RaycastParams
 };
 hipError_t launch_surface_raycast(const SurfaceParams& p, const RaycastParams& rc, const float4* rays, int64_t n_rays,
                                   float4* out, hipStream_t stream, int cus);
+// Persistent foam (ocean_generator_advance_foam, include/oceanfft.h, device/k_foam.h). FoamParams above is
+// the displacement the row pass computes the Jacobian with; these are the step's values, per cascade.
+struct FoamCascade
+{
+  float a;  // exp(-decay * dt), rounded once on the host
+  float bias, gain, level, dt;
+};
+struct FoamStep
+{
+  const float* jac;   // [cascade][nn]
+  float* foam;        // [cascade][nn], stepped in place
+  uint32_t* partial;  // [cascade][tiles][3]
+  int64_t* table;     // [cascade][3]: breaking, covered, saturated
+  int nn;             // texels per map (a power of two >= 256)
+  int tiles;          // stage-1 items per cascade: max(nn / 2048, 1)
+  int cascades;
+  FoamCascade c[kMaxCascades];
+};
+int foam_tiles(int n);  // stage-1 items per cascade
+// Bytes of the counts: the int64 table [cascade][3], then stage 1's partial rows
+size_t foam_counts_bytes(int n, int cascades);
+// One step of every cascade's foam map from its Jacobian map: two launches. counts: foam_counts_bytes.
+hipError_t launch_foam_step(int n, int cascades, const float* jac, float* foam, void* counts, const FoamCascade* c,
+                            hipStream_t stream, int cus);
+// ocean_surface_sample_foam / _plane_foam: the cascades' foam maps beside SurfaceParams' maps (same order)
+struct SurfaceFoam
+{
+  const float* foam[kMaxSurfaceCascades];
+};
+hipError_t launch_surface_foam(const SurfaceParams& p, const SurfaceFoam& f, const SurfacePlane& plane, const float2* xz,
+                               int64_t count, float4* out, hipStream_t stream, int cus);
 // ocean_hulls (include/oceanfft.h, device/k_hulls.h): the tables ocean_hulls_create builds and one call
 constexpr int kHullTilePoints = 64;  // points per work item: the lanes of one wave
 // One tile of one body: points [first, first + count) of the hull set's points, point_out rows from

@@ -34,7 +34,7 @@ Generator::~Generator()
   for (const auto* mips : {&heightMips, &displacementMips, &jacobianMips})
     for (Vision::ID id : *mips)
       renderDevice->DestroyTexture2D(id);
-  for (Vision::ID id : {heightRateMap, displacementRateMap})
+  for (Vision::ID id : {heightRateMap, displacementRateMap, foamMap})
     if (id)
       renderDevice->DestroyTexture2D(id);
   ocean_generator_destroy(gen);
@@ -110,6 +110,37 @@ void Generator::GetBounds(float out[18]) const
 {
   if (ocean_generator_bounds(gen, 0, out) != OCEAN_OK)
     throw std::runtime_error(std::string("Waves::Generator::GetBounds: ") + ocean_last_error());
+}
+
+void Generator::AdvanceFoam(float dt)
+{
+  if (ocean_generator_advance_foam(gen, dt) != OCEAN_OK)
+    throw std::runtime_error(std::string("Waves::Generator::AdvanceFoam: ") + ocean_last_error());
+}
+
+void Generator::ResetFoam()
+{
+  if (ocean_generator_reset_foam(gen) != OCEAN_OK)
+    throw std::runtime_error(std::string("Waves::Generator::ResetFoam: ") + ocean_last_error());
+}
+
+ocean_foam_settings& Generator::GetFoamSettings() { return *ocean_generator_foam_settings(gen, 0); }
+
+Vision::ID Generator::GetFoamMap()
+{
+  if (foamMap)
+    return foamMap;
+  float* map = ocean_generator_foam_map(gen, 0);
+  if (!map)
+    throw std::runtime_error(std::string("Waves::Generator::GetFoamMap: ") + ocean_last_error());
+  foamMap = renderDevice->RegisterTexture2D(map, textureSize, textureSize, Vision::PixelType::R32Float);
+  return foamMap;
+}
+
+void Generator::GetFoamCounts(int64_t out[3]) const
+{
+  if (ocean_generator_foam_counts(gen, 0, out) != OCEAN_OK)
+    throw std::runtime_error(std::string("Waves::Generator::GetFoamCounts: ") + ocean_last_error());
 }
 
 void Generator::LoadShaders(bool) {}

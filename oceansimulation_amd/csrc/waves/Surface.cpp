@@ -1,5 +1,5 @@
 // Waves::SurfaceSampler over ocean_surface_sample_plane / ocean_surface_query /
-// ocean_surface_sample_plane_lod / ocean_surface_velocity, and Waves::HullSet over ocean_hulls
+// ocean_surface_sample_plane_lod / ocean_surface_velocity / ocean_surface_sample_plane_foam, and Waves::HullSet over ocean_hulls
 // (include/oceanfft.h).
 #include "waves/Surface.h"
 
@@ -21,6 +21,8 @@ SurfaceSampler::~SurfaceSampler()
     renderDevice->DestroyTexture2D(velocities);
   if (rayHits)
     renderDevice->DestroyTexture2D(rayHits);
+  if (verticesFoam)
+    renderDevice->DestroyTexture2D(verticesFoam);
 }
 
 Vision::ID SurfaceSampler::Sample(const std::vector<Generator*>& generators, const float camera[5], int res)
@@ -170,6 +172,34 @@ Vision::ID SurfaceSampler::Raycast(const std::vector<Generator*>& generators, co
   if (rc != OCEAN_OK)
     throw std::runtime_error(std::string("SurfaceSampler::Raycast: ") + ocean_last_error());
   return rayHits;
+}
+
+Vision::ID SurfaceSampler::SampleFoam(const std::vector<Generator*>& generators, const float camera[5], int res)
+{
+  if (!verticesFoam || verticesFoamRes != res)
+  {
+    if (verticesFoam)
+      renderDevice->DestroyTexture2D(verticesFoam);
+    verticesFoam = 0;
+    Vision::Texture2DDesc desc;
+    desc.Width = 2 * (res + 1);
+    desc.Height = res + 1;
+    desc.PixelType = Vision::PixelType::RGBA32Float;
+    verticesFoam = renderDevice->CreateTexture2D(desc);
+    verticesFoamRes = res;
+  }
+  std::vector<ocean_generator*> gens;
+  std::vector<int> cascades;
+  for (auto* g : generators)
+  {
+    gens.push_back(g->GetHandle());
+    cascades.push_back(0);
+  }
+  const int rc = ocean_surface_sample_plane_foam(gens.data(), cascades.data(), (int)gens.size(), camera, res,
+                                                 static_cast<float*>(renderDevice->GetTexturePointer(verticesFoam)));
+  if (rc != OCEAN_OK)
+    throw std::runtime_error(std::string("SurfaceSampler::SampleFoam: ") + ocean_last_error());
+  return verticesFoam;
 }
 
 HullSet::HullSet(Vision::RenderDevice* device, FFTCalculator* fft, const float* points, int64_t nPoints,

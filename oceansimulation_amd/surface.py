@@ -62,6 +62,35 @@ class SurfaceSampler:
         self.fft.synchronize()
         return out.to_host((pts, FLOATS_PER_VERTEX)) if pts else np.zeros((0, FLOATS_PER_VERTEX), np.float32)
 
+    # ---- persistent foam in slot 7 (Generator.AdvanceFoam or ResetFoam first) ----
+    def sample_foam_device(self, xz_ptr: int, points: int, out_ptr: int) -> None:
+        check(lib().ocean_surface_sample_foam(self._gens, self._cas, len(self.pairs), ctypes.c_void_p(xz_ptr),
+                                              ctypes.c_int64(points), ctypes.c_void_p(out_ptr)),
+              "ocean_surface_sample_foam")
+
+    def sample_plane_foam_device(self, camera, res: int, out_ptr: int) -> None:
+        cam = (ctypes.c_float * 5)(*[float(v) for v in camera])
+        check(lib().ocean_surface_sample_plane_foam(self._gens, self._cas, len(self.pairs), cam, int(res),
+                                                    ctypes.c_void_p(out_ptr)), "ocean_surface_sample_plane_foam")
+
+    def sample_foam(self, xz: np.ndarray) -> np.ndarray:
+        """Per base point (x, z): ocean_surface_sample's 8 floats with the cascades' averaged foam in slot 7."""
+        xz = np.ascontiguousarray(xz, np.float32).reshape(-1, 2)
+        pts = xz.shape[0]
+        src = DeviceBuffer.from_array(xz) if pts else None
+        out = DeviceBuffer(pts * FLOATS_PER_VERTEX * 4) if pts else None
+        self.sample_foam_device(src.ptr if pts else 0, pts, out.ptr if pts else 0)
+        self.fft.synchronize()
+        return out.to_host((pts, FLOATS_PER_VERTEX)) if pts else np.zeros((0, FLOATS_PER_VERTEX), np.float32)
+
+    def sample_plane_foam(self, camera, res: int) -> np.ndarray:
+        """The plane mesh through the camera warp, foam in slot 7 -> ((res + 1)^2, 8)."""
+        pts = (res + 1) * (res + 1)
+        out = DeviceBuffer(pts * FLOATS_PER_VERTEX * 4)
+        self.sample_plane_foam_device(camera, res, out.ptr)
+        self.fft.synchronize()
+        return out.to_host((pts, FLOATS_PER_VERTEX))
+
     # ---- footprint-aware sampling of the mip pyramids (Generator.build_mips first) ----
     def sample_lod(self, xzf_ptr: int, points: int, out_ptr: int) -> None:
         check(lib().ocean_surface_sample_lod(self._gens, self._cas, len(self.pairs), ctypes.c_void_p(xzf_ptr),

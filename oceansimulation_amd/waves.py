@@ -11,7 +11,7 @@ import ctypes
 import numpy as np
 
 from . import capi, hip
-from .capi import OceanSettings, check, lib
+from .capi import OceanFoamSettings, OceanSettings, check, lib
 
 
 def default_settings(**overrides) -> OceanSettings:
@@ -28,6 +28,21 @@ def apply_settings(s: OceanSettings, **overrides) -> OceanSettings:
             s.seed[0], s.seed[1] = int(v[0]), int(v[1])
         else:
             setattr(s, k, v)
+    return s
+
+
+def default_foam_settings(**overrides) -> OceanFoamSettings:
+    """ocean_foam_settings defaults (bias 0.9, gain 8, decay 0.5, level 0.5) with keyword overrides."""
+    s = OceanFoamSettings()
+    lib().ocean_default_foam_settings(ctypes.byref(s))
+    return apply_foam_settings(s, **overrides)
+
+
+def apply_foam_settings(s: OceanFoamSettings, **overrides) -> OceanFoamSettings:
+    for k, v in overrides.items():
+        if k not in ("bias", "gain", "decay", "level"):
+            raise AttributeError(f"ocean_foam_settings has no field {k!r}")
+        setattr(s, k, v)
     return s
 
 
@@ -244,6 +259,57 @@ class Generator:
         ptr = lib().ocean_generator_bounds_device(self._h)
         if not ptr:
             raise capi.OceanError(capi.OCEAN_ERR_INVALID, "ocean_generator_bounds_device")
+        return int(ptr)
+
+    # ---- persistent foam (ocean_generator_advance_foam, include/oceanfft.h) ----
+    def AdvanceFoam(self, dt: float) -> None:
+        """Enqueue one step of every cascade's foam map from the current Jacobian maps; call it after
+        CalculateOcean(dt)."""
+        check(lib().ocean_generator_advance_foam(self._h, ctypes.c_float(dt)), "ocean_generator_advance_foam")
+
+    advance_foam = AdvanceFoam
+
+    def ResetFoam(self) -> None:
+        """Enqueue the zeroing of the foam maps and the counts."""
+        check(lib().ocean_generator_reset_foam(self._h), "ocean_generator_reset_foam")
+
+    reset_foam = ResetFoam
+
+    def GetFoamSettings(self, cascade: int = 0) -> OceanFoamSettings:
+        p = lib().ocean_generator_foam_settings(self._h, cascade)
+        if not p:
+            raise capi.OceanError(capi.OCEAN_ERR_INVALID, "ocean_generator_foam_settings")
+        return p.contents
+
+    get_foam_settings = GetFoamSettings
+
+    def GetFoamMap(self, cascade: int = 0) -> int:
+        """The R32F N x N foam map in device memory (OceanError before the first AdvanceFoam / ResetFoam)."""
+        ptr = lib().ocean_generator_foam_map(self._h, int(cascade))
+        if not ptr:
+            raise capi.OceanError(capi.OCEAN_ERR_INVALID, "ocean_generator_foam_map")
+        return int(ptr)
+
+    def foam_map_host(self, cascade: int = 0) -> np.ndarray:
+        ptr = self.GetFoamMap(cascade)
+        self.fft.synchronize()
+        return hip.to_host(ptr, (self.n, self.n))
+
+    def GetFoamCounts(self, cascade: int = 0) -> np.ndarray:
+        """(3,) int64: texels of the last step that were breaking (J < bias), covered (foam >= level) and
+        saturated (clamped at 1)."""
+        out = np.zeros(3, np.int64)
+        check(lib().ocean_generator_foam_counts(self._h, int(cascade), out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))),
+              "ocean_generator_foam_counts")
+        return out
+
+    get_foam_counts = GetFoamCounts
+
+    def foam_counts_device(self) -> int:
+        """The int64 table [cascade][3] in device memory (OceanError before the first AdvanceFoam / ResetFoam)."""
+        ptr = lib().ocean_generator_foam_counts_device(self._h)
+        if not ptr:
+            raise capi.OceanError(capi.OCEAN_ERR_INVALID, "ocean_generator_foam_counts_device")
         return int(ptr)
 
     # ---- instrumentation ----
