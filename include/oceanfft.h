@@ -496,6 +496,88 @@ float* ocean_generator_displacement_rate_map(ocean_generator* gen, int cascade);
 int ocean_surface_velocity(ocean_generator* const* gens, const int* cascades, int count, const float* xz,
                            int64_t points, float* out);
 
+/* ---- Depth layers: water velocity and pressure head below the surface ---------------------------
+ * The calls above describe the surface particle; a keel 3 m down, a mooring line, an ROV or an underwater
+ * camera sits in water whose orbital motion has decayed, in deep water as e^{-kd} and in finite depth by
+ * a cosh / sinh profile, differently for every wavenumber (more than a factor of 10 over 1 m for the 5 m
+ * cascade, little for the 101 m one). The factor is per wavenumber, so it is applied in k space, before
+ * the transform: a generator holds a short list of rest depths ("depth layers") and, per depth, two maps
+ * per cascade with the water velocity and the pressure head under every texel.
+ *
+ * ocean_generator_set_depth_layers: `depths` is a host array of 1..8 floats, the rest depths in metres
+ * below the mean water level: finite, >= 0 and strictly ascending, else OCEAN_ERR_INVALID. The list is
+ * per generator and shared by its cascades. Setting it marks the layers stale; a change of the layer
+ * count frees their storage after the generator's stream has drained. Whole-grid generators only.
+ * ocean_generator_depth_layers returns the count (0: none set, or a null generator) and copies the
+ * depths to `out` when it is not null.
+ *
+ * ocean_generator_calculate_kinematics: the rules of ocean_generator_calculate_rates (whole-grid
+ * generators only, every N in 16 .. 16384, every frame path, after at least one frame, on the
+ * generator's stream, no host synchronisation) and a depth list set. One launch of the packing kernel
+ * (16 B read and 32 * layers B written per point), then one batched EncodeIFFT over the
+ * 2 * layers * cascades images. The storage, [cascade][layer][2][N * N] RGBA32F, 32 B per point, cascade
+ * and layer, is allocated on first use (OCEAN_ERR_OOM when that fails) and freed by
+ * ocean_generator_destroy. The layers are fresh until the next frame call or the next
+ * ocean_generator_set_depth_layers; the library tracks that on the host.
+ *
+ * Contract of the packed images, per cascade, texel and layer depth d, in fp32: k, w, the phase, g and h
+ * are those of the last column pass, H the frame's evolved amplitude and Hd = dH/dt as in
+ * ocean_generator_calculate_rates, and with dc = min(d, h)
+ *     A_h = cosh(k (h - dc)) / cosh(k h),      A_v = sinh(k (h - dc)) / sinh(k h)   (0 when h == 0),
+ * evaluated as  e1 = exp(-(k dc)), e2 = exp(-((2k)(h - dc))), e3 = exp(-((2k) h)),
+ *     A_h = e1 * ((1 + e2) / (1 + e3)),        A_v = e1 * (expm1(-((2k)(h - dc))) / expm1(-((2k) h))),
+ * which is exactly 1.0f for both at d == 0 (h > 0). The layers keep prepareFFT's own lanes
+ * (spectrum.compute:236-237), each complex lane times a real factor:
+ *     image 0 = ( A_v * lane xy of the height packing of Hd,        A_h * lane zw of the height packing of Hd )
+ *     image 1 = ( A_h * lane xy of the displacement packing of Hd,  A_h * lane xy of the height packing of H )
+ * A real multiple keeps a lane's (field, partner) structure, so the Nyquist-row defect of the reference's
+ * spectrum is attenuated at its own wavenumber, and at d == 0 the lanes are those of the rate maps and of
+ * the height map bit for bit. (A packing of the physical fields alone, (Dx + i eta, Dz + i P), differs
+ * from what the library shows at the surface by 3 .. 50 % per channel because of that defect.) After
+ * EncodeIFFT:
+ *     image 0:  .x = vertical velocity in m/s,  .y = its x-slope,  .w = d/dt of Dx at depth
+ *     image 1:  .x = d/dt of Dz at depth,  .z = pressure head in metres,  .w = its x-slope
+ * and the other channels hold the frame's partner fields. Horizontal velocities are scale * d/dt (Dx, Dz),
+ * as everywhere in the library. Both profiles are normalised to 1 at the surface: in finite depth that
+ * follows the library's own surface, whose Dx / Dz carry no coth(k h), and not textbook linear theory,
+ * whose horizontal profile is cosh(k (h - d)) / sinh(k h). At d >= h the vertical velocity is 0.
+ * No reference counterpart. */
+int ocean_generator_set_depth_layers(ocean_generator* gen, const float* depths, int layers);
+int ocean_generator_depth_layers(const ocean_generator* gen, float out[8]);
+int ocean_generator_calculate_kinematics(ocean_generator* gen);
+/* RGBA32F N*N, row-major, holding what the last ocean_generator_calculate_kinematics wrote; valid until
+ * the generator is destroyed or its layer count changes. Null, with ocean_last_error set, for a null
+ * generator, a cascade out of range, layers that were never calculated, and a layer or image (0, 1) out
+ * of range. */
+float* ocean_generator_kinematics_map(ocean_generator* gen, int cascade, int layer, int image);
+/* What the water is doing at world positions. xyz: points x 3 floats (X, Y, Z; Y up, 0 the mean water
+ * level), out: points x 12 floats, both device memory. (generator, cascade) rules, argument rules and
+ * stream as ocean_surface_query; no atlas. Every generator's layers must be calculated, fresh, and of a
+ * depth list bit-identical to gens[0]'s: otherwise OCEAN_ERR_INVALID, naming the index of the generator in
+ * `gens`, before any device call. points == 0 launches nothing.
+ *
+ * Per point, in unfused fp32, with D[0 .. L-1] the depths:
+ *     Q = ocean_surface_query's vertex-stage fixed point at q = (X, Z):  p = (Q0, Q2), eta = Q1, res = Q7
+ *     s = eta - Y;  wet = s > 0;  d = max(s, 0), NaN -> 0
+ *     if   !(d > D[0])  : l = 0,     f = 0
+ *     elif d >= D[L-1]  : l = L - 1, f = 0
+ *     else l = largest index with D[l] <= d,  f = (d - D[l]) / (D[l+1] - D[l])
+ *     px, pz = p;  ux = uy = uz = P = 0
+ *     for c in cascades:      taps at (px / planeSize_c, pz / planeSize_c), GL_LINEAR + GL_REPEAT; sc = displacement_c
+ *         a0, a1 = layer l's image 0 / 1 samples;  when f != 0: b0, b1 = layer l+1's, v = a + f * (b - a); else v = a
+ *         ux += sc * v0.w;  uy += v0.x;  uz += sc * v1.x;  P += v1.z
+ *         H, Dm = heightMap, displacementMap samples;  px += sc * H.w;  pz += sc * Dm.x     (the vertex stage's chain)
+ *     out = (p.x, eta, p.z, res,   ux, uy, uz, P,   d, (float)l, f, wet ? 1 : 0)
+ * Velocities in m/s, P the dynamic pressure head in metres of water. The rest depth of a point is taken
+ * as its depth under the instantaneous surface (the deep-water limit of Wheeler stretching).
+ * Approximations: the column under a surface particle is sampled at that particle's base point;
+ * ocean_surface_velocity's grad . u terms are not carried below the surface; above the first layer and
+ * below the last the nearest layer is held; the blend is linear in depth, so space the layers
+ * geometrically. With D[0] = 0 a point at or above the water gets the surface particle's velocity without
+ * the chain terms. No reference counterpart. */
+int ocean_water_kinematics(ocean_generator* const* gens, const int* cascades, int count, const float* xyz,
+                           int64_t points, int iterations, float tolerance, float* out);
+
 /* ---- Bounds of the maps and ray casting against the displaced surface --------------------------
  * The calls above map base points and world positions to the water; these answer the line-of-sight
  * question, where a ray meets it (lidar / radar / camera sensor models, picking, impacts, "is the camera

@@ -114,6 +114,19 @@ public:
   Vision::ID GetHeightRateMap() const { return Rate(heightRateMap); }
   Vision::ID GetDisplacementRateMap() const { return Rate(displacementRateMap); }
 
+  // Extension (no reference counterpart): the water below the surface (ocean_generator_set_depth_layers,
+  // ocean_generator_calculate_kinematics, oceanfft.h). SetDepthLayers takes 1..8 rest depths in metres below
+  // the mean water level (finite, >= 0, strictly ascending). CalculateKinematics enqueues, per depth, two
+  // RGBA32F N x N maps on the device's stream: image 0 = (vertical velocity, its x-slope, partner, d/dt Dx),
+  // image 1 = (d/dt Dz, partner, pressure head in m, its x-slope), each wavenumber attenuated by linear wave
+  // theory's profile for that depth, both profiles 1 at the surface. Call it after CalculateOcean and before
+  // SurfaceSampler::Kinematics. GetKinematicsMap throws before the first CalculateKinematics and for a layer
+  // or image out of range; its IDs are registered anew after a change of the layer count.
+  void SetDepthLayers(const float* depths, int layers);
+  int GetDepthLayers(float out[8]) const { return ocean_generator_depth_layers(gen, out); }
+  void CalculateKinematics();
+  Vision::ID GetKinematicsMap(int layer, int image) const;
+
   // Extension (no reference counterpart): the minimum and maximum of the nine map channels
   // (ocean_generator_build_bounds, oceanfft.h): culling boxes, the slab SurfaceSampler::Raycast clips its
   // rays to, and min jacobian > 0 as the sign that SurfaceSampler::Query converges everywhere. BuildBounds
@@ -150,6 +163,9 @@ private:
   // registered by the first CalculateRates
   Vision::ID heightRateMap = 0, displacementRateMap = 0;
   Vision::ID Rate(Vision::ID map) const;
+  // [layer][image], registered by the first CalculateKinematics after a change of the layer count
+  std::vector<Vision::ID> kinematicsMaps;
+  void DropKinematicsMaps();
   // registered by the first GetFoamMap
   Vision::ID foamMap = 0;
 };

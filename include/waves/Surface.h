@@ -77,7 +77,21 @@ public:
   // texture, reused at the same res.
   Vision::ID SampleFoam(const std::vector<Generator*>& generators, const float camera[5], int res);
 
+  // What the water is doing at world positions, under the surface too (ocean_water_kinematics, oceanfft.h):
+  // keels, mooring lines, ROVs, submerged sensors. xyzDevice: points x 3 floats (x, y, z; y up) in device
+  // memory. Query's fixed point finds the water column above or below each point; the velocity and the
+  // pressure head are read from the generators' depth layers at the point's depth under the surface, blended
+  // linearly between the two nearest layers. Every generator needs the same Generator::SetDepthLayers() list
+  // and a Generator::CalculateKinematics() since its last CalculateOcean. Returns a buffer texture of
+  // 3*points x 1 RGBA32F texels: per point (base x, water height, base z, residual), (velocity x, y, z in
+  // m/s, pressure head in m), (depth under the surface, layer, blend factor, wet 0 / 1). Enqueued on the
+  // device's stream; its own texture, reused while `points` stays the same.
+  Vision::ID Kinematics(const std::vector<Generator*>& generators, const float* xyzDevice, int64_t points,
+                        int iterations, float tolerance);
+
 private:
+  Vision::ID waterPoints = 0;
+  int64_t waterPointCount = 0;
   Vision::ID verticesFoam = 0;
   int verticesFoamRes = 0;
   Vision::ID rayHits = 0;

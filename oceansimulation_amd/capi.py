@@ -117,6 +117,11 @@ SIGNATURES = {
     "ocean_generator_height_rate_map": (_vp, [_vp, _i]),
     "ocean_generator_displacement_rate_map": (_vp, [_vp, _i]),
     "ocean_surface_velocity": (_i, [_vp, _vp, _i, _vp, ctypes.c_int64, _vp]),
+    "ocean_generator_set_depth_layers": (_i, [_vp, _fp, _i]),
+    "ocean_generator_depth_layers": (_i, [_vp, _fp]),
+    "ocean_generator_calculate_kinematics": (_i, [_vp]),
+    "ocean_generator_kinematics_map": (_vp, [_vp, _i, _i, _i]),
+    "ocean_water_kinematics": (_i, [_vp, _vp, _i, _vp, ctypes.c_int64, _i, ctypes.c_float, _vp]),
     "ocean_generator_build_bounds": (_i, [_vp]),
     "ocean_generator_bounds": (_i, [_vp, _i, _fp]),
     "ocean_generator_bounds_device": (_vp, [_vp]),

@@ -163,6 +163,12 @@ struct ocean_generator
   // displacement-rate][N * N], allocated on first use; fresh until the next column pass
   float4* rates = nullptr;
   bool rates_fresh = false;
+  // the depth layers (ocean_generator_set_depth_layers / _calculate_kinematics): the rest depths shared by
+  // the cascades and the maps [cascade][layer][2][N * N], allocated on first use for the current layer
+  // count; fresh until the next column pass or the next set_depth_layers
+  KinematicsDepths depths{};
+  float4* kin = nullptr;
+  bool kin_fresh = false;
   // the bounds of the maps (ocean_generator_build_bounds): the table [cascade][18], then stage 1's partial
   // rows (bounds_floats), allocated on first use; fresh until the next call that rewrites the maps
   float* bounds = nullptr;

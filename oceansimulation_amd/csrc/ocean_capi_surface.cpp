@@ -1,6 +1,6 @@
 // ocean_capi_surface.cpp — the part of the C ABI (include/oceanfft.h) that consumes a generator's maps:
 // the map getters, ocean_surface_sample / _query / _sample_plane, the mip pyramids and the *_lod requests,
-// the rate maps and ocean_surface_velocity, the bounds and ocean_surface_raycast, the persistent foam with
+// the rate maps and ocean_surface_velocity, the depth layers and ocean_water_kinematics, the bounds and ocean_surface_raycast, the persistent foam with
 // ocean_surface_sample_foam, and the hull sets.
 // The plans and generators themselves are in ocean_capi.cpp, their exchanges in ocean_capi_exchange.cpp;
 // ocean_capi_internal.h has what the three share.
@@ -13,6 +13,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -378,6 +379,117 @@ int ocean_surface_velocity(ocean_generator* const* gens, const int* cascades, in
   HIP_TRY(launch_surface_velocity(p, r, reinterpret_cast<const float2*>(xz), points, reinterpret_cast<float4*>(out),
                                   fft->stream, fft->cus),
           "ocean_surface_velocity");
+  return OCEAN_OK;
+}
+
+// ---- depth layers: water velocity and pressure head below the surface ----
+int ocean_generator_set_depth_layers(ocean_generator* g, const float* depths, int layers)
+{
+  // the list's own rules first: they need no generator
+  if (!depths || layers < 1 || layers > kMaxDepthLayers)
+    return fail(OCEAN_ERR_INVALID, "ocean_generator_set_depth_layers: need 1..8 depths");
+  for (int l = 0; l < layers; l++)
+    if (!std::isfinite(depths[l]) || !(depths[l] >= 0.0f) || (l > 0 && !(depths[l] > depths[l - 1])))
+      return fail(OCEAN_ERR_INVALID,
+                  "ocean_generator_set_depth_layers: depths must be finite, >= 0 and strictly ascending");
+  TRY(whole_maps(g, false, "ocean_generator_set_depth_layers"));
+  if (g->kin && layers != g->depths.layers)
+  {
+    // an earlier calculate_kinematics or ocean_water_kinematics may still use the old storage
+    HIP_TRY(hipStreamSynchronize(g->fft->stream), "ocean_generator_set_depth_layers");
+    HIP_TRY(hipFree(g->kin), "ocean_generator_set_depth_layers");
+    g->kin = nullptr;
+  }
+  g->depths = KinematicsDepths{};
+  g->depths.layers = layers;
+  for (int l = 0; l < layers; l++)
+    g->depths.d[l] = depths[l];
+  g->kin_fresh = false;
+  return OCEAN_OK;
+}
+
+int ocean_generator_depth_layers(const ocean_generator* g, float out[8])
+{
+  if (!g)
+    return 0;
+  for (int l = 0; out && l < g->depths.layers; l++)
+    out[l] = g->depths.d[l];
+  return g->depths.layers;
+}
+
+int ocean_generator_calculate_kinematics(ocean_generator* g)
+{
+  TRY(whole_maps(g, true, "ocean_generator_calculate_kinematics"));
+  if (g->depths.layers < 1)
+    return fail(OCEAN_ERR_INVALID,
+                "ocean_generator_calculate_kinematics: no depth layers set (ocean_generator_set_depth_layers)");
+  ocean_fft* f = g->fft;
+  const size_t nn = (size_t)f->n * f->n;
+  const int images = 2 * g->depths.layers * g->cascades;
+  TRY(alloc_once(g->kin, (size_t)images * nn * sizeof(float4), "ocean_generator_calculate_kinematics"));
+  g->kin_fresh = false;
+  TRY(materialise_h0(g));  // as ocean_generator_calculate_rates
+  HIP_TRY(launch_kinematics_pack(f->logn, g->frame, g->depths, g->h0_block, g->h0, g->kin, f->stream, f->cus),
+          "ocean_generator_calculate_kinematics");
+  TRY(ocean_fft_encode_ifft_batch(f, reinterpret_cast<float*>(g->kin), images));
+  g->kin_fresh = true;
+  return OCEAN_OK;
+}
+
+float* ocean_generator_kinematics_map(ocean_generator* g, int c, int layer, int image)
+{
+  const char* who = "ocean_generator_kinematics_map";
+  if (!g || c < 0 || c >= g->cascades)
+  {
+    fail(OCEAN_ERR_INVALID, std::string(who) + ": null generator or cascade out of range");
+    return nullptr;
+  }
+  if (!g->kin)
+  {
+    fail(OCEAN_ERR_INVALID,
+         std::string(who) + ": the depth layers were never calculated (ocean_generator_calculate_kinematics)");
+    return nullptr;
+  }
+  if (layer < 0 || layer >= g->depths.layers || image < 0 || image > 1)
+  {
+    fail(OCEAN_ERR_INVALID, std::string(who) + ": layer or image out of range");
+    return nullptr;
+  }
+  const size_t nn = (size_t)g->fft->n * g->fft->n;
+  return reinterpret_cast<float*>(g->kin + nn * (((size_t)c * g->depths.layers + layer) * 2 + image));
+}
+
+int ocean_water_kinematics(ocean_generator* const* gens, const int* cascades, int count, const float* xyz,
+                           int64_t points, int iterations, float tolerance, float* out)
+{
+  const char* who = "ocean_water_kinematics";
+  SurfaceParams p;
+  ocean_fft* fft;
+  TRY(surface_params(gens, cascades, count, p, fft, who));
+  TRY(check_fixed_point(iterations, tolerance, who));
+  WaterLayers w{};
+  const KinematicsDepths& first = gens[0]->depths;
+  const size_t nn = (size_t)fft->n * fft->n;
+  for (int i = 0; i < count; i++)
+  {
+    ocean_generator* g = gens[i];
+    if (!g->kin || !g->kin_fresh)
+      return not_fresh(who, i, g->kin, " has no depth layers (call",
+                       " has stale depth layers (a frame was calculated or the depths were set since",
+                       "ocean_generator_calculate_kinematics");
+    if (g->depths.layers != first.layers ||
+        std::memcmp(g->depths.d, first.d, sizeof(float) * (size_t)first.layers) != 0)
+      return fail(OCEAN_ERR_INVALID, std::string(who) + ": generator " + std::to_string(i) +
+                                         " has other depth layers than generator 0 (ocean_generator_set_depth_layers)");
+    w.map[i] = g->kin + nn * ((size_t)cascades[i] * first.layers * 2);
+  }
+  w.layers = first.layers;
+  for (int l = 0; l < first.layers; l++)
+    w.d[l] = first.d[l];
+  TRY(check_points(points, xyz, out, who));
+  HIP_TRY(launch_water_kinematics(p, w, xyz, points, iterations, tolerance, reinterpret_cast<float4*>(out),
+                                  fft->stream, fft->cus),
+          who);
   return OCEAN_OK;
 }
 

@@ -297,6 +297,28 @@ struct SurfaceRates
 };
 hipError_t launch_surface_velocity(const SurfaceParams& p, const SurfaceRates& r, const float2* xz, int64_t count,
                                    float4* out, hipStream_t stream, int cus);
+// Depth layers (ocean_generator_calculate_kinematics, include/oceanfft.h, device/k_kinematics.h): the rest
+// depths of a generator's layers, ascending from >= 0, and the packed images of every cascade and layer,
+// [cascade][layer][2][N * N], row-major and still in k space, from the h0 image as launch_rates_pack reads
+// it. The batched EncodeIFFT over the 2 * layers * cascades images follows (the caller's).
+constexpr int kMaxDepthLayers = 8;
+struct KinematicsDepths
+{
+  int layers;
+  float d[kMaxDepthLayers];
+};
+hipError_t launch_kinematics_pack(int logn, const FrameParams& fp, const KinematicsDepths& kd, int h0_blk,
+                                  const float4* h0, float4* out, hipStream_t stream, int cus);
+// ocean_water_kinematics: the cascades' layer maps ([layer][2][N * N] each) beside SurfaceParams' maps
+// (same order) with the depths they share; xyz [count][3], out [count][3].
+struct WaterLayers
+{
+  const float4* map[kMaxSurfaceCascades];
+  int layers;
+  float d[kMaxDepthLayers];
+};
+hipError_t launch_water_kinematics(const SurfaceParams& p, const WaterLayers& w, const float* xyz, int64_t count,
+                                   int iterations, float tolerance, float4* out, hipStream_t stream, int cus);
 // The bounds of a whole-grid generator's maps (device/k_bounds.h): per cascade 18 floats, (min, max) of
 // heightMap x, y, z, w, displacementMap x, y, z, w and the Jacobian, at the start of `bounds`
 // (bounds_floats(n, cascades) floats: the table, then stage 1's partial rows). Two launches.

@@ -34,6 +34,7 @@ Generator::~Generator()
   for (const auto* mips : {&heightMips, &displacementMips, &jacobianMips})
     for (Vision::ID id : *mips)
       renderDevice->DestroyTexture2D(id);
+  DropKinematicsMaps();
   for (Vision::ID id : {heightRateMap, displacementRateMap, foamMap})
     if (id)
       renderDevice->DestroyTexture2D(id);
@@ -98,6 +99,45 @@ Vision::ID Generator::Rate(Vision::ID map) const
   if (!map)
     throw std::runtime_error("Waves::Generator: the rates were never calculated (CalculateRates)");
   return map;
+}
+
+void Generator::DropKinematicsMaps()
+{
+  for (Vision::ID id : kinematicsMaps)
+    renderDevice->DestroyTexture2D(id);
+  kinematicsMaps.clear();
+}
+
+void Generator::SetDepthLayers(const float* depths, int layers)
+{
+  const int before = ocean_generator_depth_layers(gen, nullptr);
+  if (ocean_generator_set_depth_layers(gen, depths, layers) != OCEAN_OK)
+    throw std::runtime_error(std::string("Waves::Generator::SetDepthLayers: ") + ocean_last_error());
+  if (layers != before)  // the library freed the storage the IDs name
+    DropKinematicsMaps();
+}
+
+void Generator::CalculateKinematics()
+{
+  if (ocean_generator_calculate_kinematics(gen) != OCEAN_OK)
+    throw std::runtime_error(std::string("Waves::Generator::CalculateKinematics: ") + ocean_last_error());
+  if (!kinematicsMaps.empty())
+    return;
+  const std::size_t n = textureSize;
+  const int layers = ocean_generator_depth_layers(gen, nullptr);
+  for (int layer = 0; layer < layers; layer++)
+    for (int image = 0; image < 2; image++)
+      kinematicsMaps.push_back(renderDevice->RegisterTexture2D(ocean_generator_kinematics_map(gen, 0, layer, image), n, n,
+                                                               Vision::PixelType::RGBA32Float));
+}
+
+Vision::ID Generator::GetKinematicsMap(int layer, int image) const
+{
+  if (kinematicsMaps.empty())
+    throw std::runtime_error("Waves::Generator: the depth layers were never calculated (CalculateKinematics)");
+  if (layer < 0 || (std::size_t)layer >= kinematicsMaps.size() / 2 || image < 0 || image > 1)
+    throw std::runtime_error("Waves::Generator: depth layer or image out of range");
+  return kinematicsMaps[(std::size_t)layer * 2 + image];
 }
 
 void Generator::BuildBounds()

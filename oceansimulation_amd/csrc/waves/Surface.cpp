@@ -1,5 +1,6 @@
 // Waves::SurfaceSampler over ocean_surface_sample_plane / ocean_surface_query /
-// ocean_surface_sample_plane_lod / ocean_surface_velocity / ocean_surface_sample_plane_foam, and Waves::HullSet over ocean_hulls
+// ocean_surface_sample_plane_lod / ocean_surface_velocity / ocean_surface_sample_plane_foam /
+// ocean_water_kinematics, and Waves::HullSet over ocean_hulls
 // (include/oceanfft.h).
 #include "waves/Surface.h"
 
@@ -23,6 +24,8 @@ SurfaceSampler::~SurfaceSampler()
     renderDevice->DestroyTexture2D(rayHits);
   if (verticesFoam)
     renderDevice->DestroyTexture2D(verticesFoam);
+  if (waterPoints)
+    renderDevice->DestroyTexture2D(waterPoints);
 }
 
 Vision::ID SurfaceSampler::Sample(const std::vector<Generator*>& generators, const float camera[5], int res)
@@ -200,6 +203,37 @@ Vision::ID SurfaceSampler::SampleFoam(const std::vector<Generator*>& generators,
   if (rc != OCEAN_OK)
     throw std::runtime_error(std::string("SurfaceSampler::SampleFoam: ") + ocean_last_error());
   return verticesFoam;
+}
+
+Vision::ID SurfaceSampler::Kinematics(const std::vector<Generator*>& generators, const float* xyzDevice,
+                                      int64_t points, int iterations, float tolerance)
+{
+  if (points < 1)
+    throw std::runtime_error("SurfaceSampler::Kinematics: need at least one point");
+  if (!waterPoints || waterPointCount != points)
+  {
+    if (waterPoints)
+      renderDevice->DestroyTexture2D(waterPoints);
+    waterPoints = 0;
+    Vision::Texture2DDesc desc;
+    desc.Width = 3 * (std::size_t)points;
+    desc.Height = 1;
+    desc.PixelType = Vision::PixelType::RGBA32Float;
+    waterPoints = renderDevice->CreateTexture2D(desc);
+    waterPointCount = points;
+  }
+  std::vector<ocean_generator*> gens;
+  std::vector<int> cascades;
+  for (auto* g : generators)
+  {
+    gens.push_back(g->GetHandle());
+    cascades.push_back(0);
+  }
+  const int rc = ocean_water_kinematics(gens.data(), cascades.data(), (int)gens.size(), xyzDevice, points, iterations,
+                                        tolerance, static_cast<float*>(renderDevice->GetTexturePointer(waterPoints)));
+  if (rc != OCEAN_OK)
+    throw std::runtime_error(std::string("SurfaceSampler::Kinematics: ") + ocean_last_error());
+  return waterPoints;
 }
 
 HullSet::HullSet(Vision::RenderDevice* device, FFTCalculator* fft, const float* points, int64_t nPoints,

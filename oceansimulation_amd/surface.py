@@ -1,8 +1,9 @@
 """Surface consumer of the generator maps: resources/waveShader.glsl's vertex
 displacement (:101-110) and fragment slope normal / Jacobian (:127-144), per mesh vertex, through
 ocean_surface_sample / ocean_surface_sample_plane, and the opposite direction, the water surface above
-world positions, through ocean_surface_query, and the loads on floating bodies built on both,
-ocean_hulls_loads (include/oceanfft.h)."""
+world positions, through ocean_surface_query, the water below the surface at world positions through
+ocean_water_kinematics, and the loads on floating bodies built on both, ocean_hulls_loads
+(include/oceanfft.h)."""
 from __future__ import annotations
 
 import ctypes
@@ -16,6 +17,7 @@ from .hip import DeviceBuffer
 FLOATS_PER_VERTEX = 8  # x, y, z, jacobian, nx, ny, nz, 0 (query: base x, height, base z, ..., residual)
 FLOATS_PER_RAY = 8     # ox, oy, oz, tmin, dx, dy, dz, tmax
 FLOATS_PER_HIT = 16    # ocean_surface_raycast's four rows
+FLOATS_PER_WATER_POINT = 12  # ocean_water_kinematics' three rows
 RAY_HIT, RAY_OUTSIDE, RAY_EXIT, RAY_STEP_LIMIT = 0, 1, 2, 3
 
 
@@ -133,6 +135,24 @@ class SurfaceSampler:
         self.velocity(src.ptr if pts else 0, pts, out.ptr if pts else 0)
         self.fft.synchronize()
         return out.to_host((pts, FLOATS_PER_VERTEX)) if pts else np.zeros((0, FLOATS_PER_VERTEX), np.float32)
+
+    # ---- the water below the surface (Generator.set_depth_layers and calculate_kinematics first) ----
+    def kinematics(self, xyz_ptr: int, points: int, iterations: int, tolerance: float, out_ptr: int) -> None:
+        """Enqueue ocean_water_kinematics: device positions (n, 3) -> device rows (n, 12)."""
+        check(lib().ocean_water_kinematics(self._gens, self._cas, len(self.pairs), ctypes.c_void_p(xyz_ptr),
+                                           ctypes.c_int64(points), int(iterations), ctypes.c_float(tolerance),
+                                           ctypes.c_void_p(out_ptr)), "ocean_water_kinematics")
+
+    def kinematics_host(self, xyz: np.ndarray, iterations: int = 8, tolerance: float = 0.0) -> np.ndarray:
+        """Per world position (x, y, z): (base x, water height, base z, residual, velocity x, y, z in m/s,
+        pressure head in m, depth under the surface, layer, blend factor, wet)."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        pts = xyz.shape[0]
+        src = DeviceBuffer.from_array(xyz) if pts else None
+        out = DeviceBuffer(pts * FLOATS_PER_WATER_POINT * 4) if pts else None
+        self.kinematics(src.ptr if pts else 0, pts, iterations, tolerance, out.ptr if pts else 0)
+        self.fft.synchronize()
+        return out.to_host((pts, FLOATS_PER_WATER_POINT)) if pts else np.zeros((0, FLOATS_PER_WATER_POINT), np.float32)
 
     # ---- ray casting against the displaced surface (Generator.BuildBounds first) ----
     def raycast(self, rays_ptr: int, n_rays: int, out_ptr: int, step: float = 0.25, max_steps: int = 256,

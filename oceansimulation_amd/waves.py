@@ -238,6 +238,36 @@ class Generator:
         """d/dt (Dz, dDx/dx, dDz/dz, dDx/dz)"""
         return self._rate_host("ocean_generator_displacement_rate_map", cascade)
 
+    # ---- depth layers (ocean_generator_set_depth_layers / _calculate_kinematics, include/oceanfft.h) ----
+    def set_depth_layers(self, depths) -> None:
+        """The rest depths in metres below the mean water level: 1..8, finite, >= 0, strictly ascending."""
+        d = np.ascontiguousarray(depths, np.float32).reshape(-1)
+        check(lib().ocean_generator_set_depth_layers(self._h, d.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                                     int(d.shape[0])), "ocean_generator_set_depth_layers")
+
+    def depth_layers(self) -> np.ndarray:
+        out = np.zeros(8, np.float32)
+        count = int(lib().ocean_generator_depth_layers(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+        return out[:count]
+
+    def calculate_kinematics(self) -> None:
+        """Enqueue the water velocity and pressure head of every cascade at every depth layer, at the time of
+        the last frame."""
+        check(lib().ocean_generator_calculate_kinematics(self._h), "ocean_generator_calculate_kinematics")
+
+    def GetKinematicsMap(self, cascade: int = 0, layer: int = 0, image: int = 0) -> int:
+        ptr = lib().ocean_generator_kinematics_map(self._h, int(cascade), int(layer), int(image))
+        if not ptr:
+            raise capi.OceanError(capi.OCEAN_ERR_INVALID, "ocean_generator_kinematics_map")
+        return int(ptr)
+
+    def kinematics_map_host(self, cascade: int = 0, layer: int = 0, image: int = 0) -> np.ndarray:
+        """image 0: (vertical velocity, its x-slope, partner, d/dt Dx); image 1: (d/dt Dz, partner, pressure
+        head, its x-slope), at depth layer `layer`."""
+        ptr = self.GetKinematicsMap(cascade, layer, image)
+        self.fft.synchronize()
+        return hip.to_host(ptr, (self.n, self.n, 4))
+
     # ---- bounds of the maps (ocean_generator_build_bounds, include/oceanfft.h) ----
     def BuildBounds(self) -> None:
         """Enqueue the (min, max) of the nine map channels of every cascade from the current maps."""
