@@ -804,6 +804,85 @@ int ocean_surface_sample_foam(ocean_generator* const* gens, const int* cascades,
 int ocean_surface_sample_plane_foam(ocean_generator* const* gens, const int* cascades, int count,
                                     const float camera[5], int res, float* out);
 
+/* ---- Spray emitters: ordered compaction of breaking texels into records -------------------------
+ * The Jacobian map says where the surface is folding now, the foam keeps its history, and
+ * ocean_surface_velocity gives the position and velocity of the water particle under a base point. A
+ * consumer that spawns something at breaking crests (spray, whitecap sprites, splash sounds, radar
+ * sea-clutter scatterers) wants those joined: a list of emitters, each the point where the surface breaks
+ * now with the velocity that throws the particle. ocean_spray_emit builds that list on the device: dense,
+ * in a fixed order, thinned by a per-texel probability, with a count that stays on the device.
+ *
+ * Settings, per (generator, cascade) pair of a call. The defaults (0.9, 8.0, 0) are starting points, not
+ * measurements.
+ *     threshold  a texel can emit where threshold - J > 0
+ *     rate       (1/s) emission probability per second per unit of (threshold - J); 0: the pair never emits
+ *     seed       of the pair's random numbers */
+typedef struct ocean_spray_settings {
+  float threshold;
+  float rate;
+  uint32_t seed;
+} ocean_spray_settings;
+void ocean_default_spray_settings(ocean_spray_settings* out);
+/* An emitter is its own object, like a hull set: it owns the scratch of the compaction (12 B per 2048
+ * texels for 16 pairs of the plan's N, and the count table), which is allocated on the first
+ * ocean_spray_emit (OCEAN_ERR_OOM when that fails). Calls run on the stream of `fft`.
+ * OCEAN_ERR_INVALID for a null out or fft. */
+typedef struct ocean_spray ocean_spray;
+int ocean_spray_create(ocean_spray** out, ocean_fft* fft);
+/* Waits for the plan's stream, then frees the emitter. */
+int ocean_spray_destroy(ocean_spray* spray);
+/* settings: host, one per pair. tiles: host, count x 2 int32 (tx, tz), or null for all zero: pair i's
+ * texels stand for the copy of its periodic plane shifted by (tx, tz) plane sizes. out: device,
+ * capacity x 8 floats.
+ *
+ * Contract, in unfused fp32. For each pair i in order, with J its Jacobian map, L its planeSize,
+ * s = settings[i], and each texel (x, y) in row-major order:
+ *     d = s.threshold - J[y*N + x]
+ *     p = fminf((fmaxf(d, 0.0f) * s.rate) * dt, 1.0f)                  two products
+ *     n = hash(hash(x, y) ^ s.seed, step)                             hash: the generator's counter hash,
+ *     u = (float)((n >> 1) & 0x7FFFFFFF) / (float)0x7FFFFFFF           resources/spectrum.compute:109-115
+ *     emits = d > 0 && (p >= 1.0f || u < p)
+ * u can round to 1.0, hence the p >= 1 arm: a large finite rate emits every breaking texel. The emitting
+ * texels form one list ordered by (pair, y*N + x) ascending; found is its length and
+ * written = min(found, capacity). Record r < written is 8 floats:
+ *     cell = L / (float)N
+ *     bx = ((float)x + 0.5f) * cell + (float)tiles[i][0] * L          two products, one sum
+ *     bz = ((float)y + 0.5f) * cell + (float)tiles[i][1] * L
+ *     velocity != 0:  (px, py, pz, 0, ux, uy, uz, 0) = ocean_surface_velocity over all pairs at (bx, bz)
+ *     velocity == 0:  (px, py, pz) = ocean_surface_sample's vertex stage over all pairs; ux = uy = uz = +0
+ *     out[r] = (px, py, pz, d,  ux, uy, uz, bits of the uint32 (i << 28 | y*N + x))
+ * So slots 0-2 and 4-6 are ocean_surface_velocity's (velocity == 0: slots 0-2 ocean_surface_sample's) bits
+ * at the texel's centre, slot 3 is positive, and slot 7 names the pair and the texel (pairs <= 16 and
+ * N*N <= 2^28). Records from `written` on are not touched. A pair with rate == 0 emits nothing and its map
+ * is not read; it still takes part in every record's position and velocity.
+ * Counts: int64[18] in device memory: [0] written, [1] found, [2 + i] pair i's share of found (0 for
+ * i >= count). capacity == 0 with out == null is a counting-only call.
+ * Maps holding NaN, and (d * rate) * dt that is not finite, are unspecified. Subsequent calls overwrite
+ * the counts; the scratch serves one call at a time, in stream order.
+ *
+ * (generator, cascade) rules and stream as ocean_hulls_loads: whole-grid generators, all of the plan's N,
+ * 1..16 pairs, gens[0] on the emitter's plan. At most four kernel launches (count per 2048-texel item,
+ * scan of the items, scatter of (d, id), dense fill of the records; two for a counting-only call), the
+ * kernel boundaries being the only ordering: no host synchronisation, no float and no integer atomics, no
+ * allocation after the first call. The same call on the same maps gives the same bytes on every run and
+ * under every CU budget. The count pass reads 4 B per texel of the emitting pairs, the scatter at most
+ * 4 B per texel; a record costs 32 B written and its taps.
+ * OCEAN_ERR_INVALID, before any device call, naming the index in `gens` where one applies: a null
+ * emitter; null gens / cascades or count outside 1..16; null settings; a negative capacity; a null out
+ * with capacity > 0; dt negative or non-finite; a non-finite threshold; a rate that is negative or
+ * non-finite; the (generator, cascade) rules; a generator that has calculated no frame yet; with
+ * velocity != 0, rates that were never calculated or are stale (the rule of ocean_surface_velocity).
+ * No reference counterpart. */
+int ocean_spray_emit(ocean_spray* spray, ocean_generator* const* gens, const int* cascades, int count,
+                     const ocean_spray_settings* settings, const int32_t* tiles, float dt, uint32_t step,
+                     int velocity, int64_t capacity, float* out);
+/* Host copy of the last call's counts; synchronises the plan's stream. OCEAN_ERR_INVALID for a null
+ * emitter or output and before the first ocean_spray_emit. */
+int ocean_spray_counts(ocean_spray* spray, int64_t out[18]);
+/* The counts in device memory, valid until the emitter is destroyed. Null, with ocean_last_error set, for
+ * a null emitter and before the first ocean_spray_emit. */
+const int64_t* ocean_spray_counts_device(ocean_spray* spray);
+
 #ifdef __cplusplus
 }
 #endif

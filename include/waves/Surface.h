@@ -144,4 +144,38 @@ private:
   Vision::ID pointRows = 0;
 };
 
+// Emitters at breaking crests (ocean_spray, oceanfft.h): spray, whitecap sprites, splash sounds. Per call the
+// texels of the generators' Jacobian maps under their thresholds, thinned by rate * dt, become one ordered,
+// dense list of records with the position and velocity of their water particles; the count stays on the
+// device, and a call is replayable bit for bit.
+class SprayEmitter
+{
+public:
+  SprayEmitter(Vision::RenderDevice* device, FFTCalculator* fft);
+  ~SprayEmitter();
+  SprayEmitter(const SprayEmitter&) = delete;
+  SprayEmitter& operator=(const SprayEmitter&) = delete;
+
+  ocean_spray* GetHandle() const { return spray; }
+
+  // settings: one per generator (host). tiles: generators x 2 host int32 plane offsets, or null. `step`
+  // numbers the call: the same step draws the same emitters. velocity needs Generator::CalculateRates() since
+  // each generator's last CalculateOcean; without it the velocities are 0. Returns a buffer texture of
+  // 2*capacity x 1 RGBA32F texels: per record (x, y, z, threshold - jacobian), (velocity x, y, z in m/s, id as
+  // uint32 bits: generator << 28 | texel); records from GetCounts()[0] on are not written. Enqueued on the
+  // device's stream; the texture is owned by the emitter and reused while `capacity` stays the same.
+  Vision::ID Emit(const std::vector<Generator*>& generators, const ocean_spray_settings* settings, const int32_t* tiles,
+                  float dt, uint32_t step, bool velocity, int64_t capacity);
+  // (written, found, found per generator ..) of the last Emit; waits for the device's stream
+  void GetCounts(int64_t out[18]) const;
+  // The same table in device memory
+  const int64_t* GetCountsDevice() const;
+
+private:
+  Vision::RenderDevice* renderDevice = nullptr;
+  ocean_spray* spray = nullptr;
+  Vision::ID records = 0;
+  int64_t recordCapacity = 0;
+};
+
 }  // namespace Waves

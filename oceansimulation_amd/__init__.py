@@ -5,9 +5,11 @@ Drop-in for the h0 -> h(k,t) -> 2D iFFT path of James51332/OceanSimulation
 include/oceanfft.h); this package is its ctypes binding plus a Python mirror of the reference
 classes used by the tests and bench.py.
 """
-from .capi import OceanError, OceanFoamSettings, OceanSettings, lib  # noqa: F401
+from .capi import OceanError, OceanFoamSettings, OceanSettings, OceanSpraySettings, lib  # noqa: F401
 from .waves import (FFTCalculator, Generator, default_settings, apply_settings,  # noqa: F401
-                    default_foam_settings, apply_foam_settings)
+                    default_foam_settings, apply_foam_settings, default_spray_settings, apply_spray_settings)
+from .surface import SprayEmitter  # noqa: F401
 
-__all__ = ["FFTCalculator", "Generator", "OceanSettings", "OceanFoamSettings", "OceanError", "default_settings",
-           "apply_settings", "default_foam_settings", "apply_foam_settings", "lib"]
+__all__ = ["FFTCalculator", "Generator", "OceanSettings", "OceanFoamSettings", "OceanSpraySettings", "OceanError",
+           "default_settings", "apply_settings", "default_foam_settings", "apply_foam_settings",
+           "default_spray_settings", "apply_spray_settings", "SprayEmitter", "lib"]

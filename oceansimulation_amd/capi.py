@@ -60,6 +60,19 @@ class OceanFoamSettings(ctypes.Structure):
 
 assert ctypes.sizeof(OceanFoamSettings) == 16
 
+
+class OceanSpraySettings(ctypes.Structure):
+    """ocean_spray_settings: one (generator, cascade) pair's emission parameters, 12 bytes."""
+
+    _fields_ = [
+        ("threshold", ctypes.c_float),
+        ("rate", ctypes.c_float),
+        ("seed", ctypes.c_uint32),
+    ]
+
+
+assert ctypes.sizeof(OceanSpraySettings) == 12
+
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _f = ctypes.c_float
@@ -141,6 +154,13 @@ SIGNATURES = {
     "ocean_hulls_instance_points": (ctypes.c_int64, [_vp]),
     "ocean_debug_hulls_packing": (_i, [_i]),
     "ocean_hulls_loads": (_i, [_vp, _vp, _vp, _i, _vp, _f, _i, _f, _i, _vp, _vp]),
+    "ocean_default_spray_settings": (None, [ctypes.POINTER(OceanSpraySettings)]),
+    "ocean_spray_create": (_i, [ctypes.POINTER(_vp), _vp]),
+    "ocean_spray_destroy": (_i, [_vp]),
+    "ocean_spray_emit": (_i, [_vp, _vp, _vp, _i, ctypes.POINTER(OceanSpraySettings), _vp, _f, ctypes.c_uint32, _i,
+                              ctypes.c_int64, _vp]),
+    "ocean_spray_counts": (_i, [_vp, ctypes.POINTER(ctypes.c_int64)]),
+    "ocean_spray_counts_device": (_vp, [_vp]),
     "ocean_generator_set_half_spectrum": (_i, [_vp, _i]),
     "ocean_generator_set_four_step": (_i, [_vp, _i]),
     "ocean_generator_set_h0_memo": (_i, [_vp, _i]),

@@ -1,7 +1,7 @@
 // ocean_capi_surface.cpp — the part of the C ABI (include/oceanfft.h) that consumes a generator's maps:
 // the map getters, ocean_surface_sample / _query / _sample_plane, the mip pyramids and the *_lod requests,
 // the rate maps and ocean_surface_velocity, the depth layers and ocean_water_kinematics, the bounds and ocean_surface_raycast, the persistent foam with
-// ocean_surface_sample_foam, and the hull sets.
+// ocean_surface_sample_foam, the hull sets and the spray emitters.
 // The plans and generators themselves are in ocean_capi.cpp, their exchanges in ocean_capi_exchange.cpp;
 // ocean_capi_internal.h has what the three share.
 //
@@ -958,6 +958,141 @@ int ocean_hulls_loads(ocean_hulls* h, ocean_generator* const* gens, const int* c
   call.rho_g = rho_g;
   HIP_TRY(launch_hulls_loads(p, r, water_velocity != 0, call, h->folds, h->n_folds, fft->stream, fft->cus),
           "ocean_hulls_loads");
+  return OCEAN_OK;
+}
+
+// ---- spray emitters: ordered compaction of breaking texels into records ----
+void ocean_default_spray_settings(ocean_spray_settings* s)
+{
+  if (s)
+    *s = ocean_spray_settings{0.9f, 8.0f, 0u};
+}
+
+struct ocean_spray
+{
+  ocean_fft* fft = nullptr;
+  void* scratch = nullptr;  // spray_scratch_bytes(fft->n), allocated by the first emit
+};
+
+int ocean_spray_create(ocean_spray** out, ocean_fft* fft)
+{
+  if (!out || !fft)
+    return fail(OCEAN_ERR_INVALID, "ocean_spray_create: null argument");
+  auto* s = new ocean_spray();
+  s->fft = fft;
+  *out = s;
+  return OCEAN_OK;
+}
+
+int ocean_spray_destroy(ocean_spray* s)
+{
+  if (!s)
+    return OCEAN_OK;
+  if (s->scratch)
+  {
+    (void)hipStreamSynchronize(s->fft->stream);
+    (void)hipFree(s->scratch);
+  }
+  delete s;
+  return OCEAN_OK;
+}
+
+int ocean_spray_emit(ocean_spray* spray, ocean_generator* const* gens, const int* cascades, int count,
+                     const ocean_spray_settings* settings, const int32_t* tiles, float dt, uint32_t step, int velocity,
+                     int64_t capacity, float* out)
+{
+  const std::string who = "ocean_spray_emit";
+  // the rules that need no generator first
+  if (!spray)
+    return fail(OCEAN_ERR_INVALID, who + ": null emitter");
+  if (!gens || !cascades || count < 1 || count > kMaxSurfaceCascades)
+    return fail(OCEAN_ERR_INVALID, who + ": need 1..16 (generator, cascade) pairs");
+  if (!settings)
+    return fail(OCEAN_ERR_INVALID, who + ": null settings");
+  if (capacity < 0 || (capacity > 0 && !out))
+    return fail(OCEAN_ERR_INVALID, who + ": negative capacity, or null output with capacity > 0");
+  if (!(dt >= 0.0f) || !std::isfinite(dt))
+    return fail(OCEAN_ERR_INVALID, who + ": dt must be finite and >= 0");
+  for (int i = 0; i < count; i++)
+  {
+    if (!std::isfinite(settings[i].threshold))
+      return fail(OCEAN_ERR_INVALID, who + ": pair " + std::to_string(i) + " has a non-finite threshold");
+    if (!(settings[i].rate >= 0.0f) || !std::isfinite(settings[i].rate))
+      return fail(OCEAN_ERR_INVALID, who + ": pair " + std::to_string(i) + " needs a rate finite and >= 0");
+  }
+  SurfaceParams p;
+  ocean_fft* fft;
+  TRY(surface_params(gens, cascades, count, p, fft, who.c_str()));
+  if (gens[0]->fft != spray->fft)
+    return fail(OCEAN_ERR_INVALID, who + ": the first generator is on another plan than the emitter");
+  for (int i = 0; i < count; i++)
+  {
+    if (gens[i]->slab)
+      return fail(OCEAN_ERR_INVALID,
+                  who + ": generator " + std::to_string(i) + " is a slab generator: row slabs, not whole maps");
+    if (gens[i]->frame.cascades != gens[i]->cascades)
+      return fail(OCEAN_ERR_INVALID, who + ": generator " + std::to_string(i) +
+                                         " has no frame calculated yet (ocean_generator_calculate)");
+  }
+  SurfaceRates r{};
+  if (velocity)
+    TRY(surface_rates(gens, cascades, count, fft, r, who.c_str()));
+  TRY(alloc_once(spray->scratch, spray_scratch_bytes(fft->n), who));
+  SprayCall s{};
+  spray_scratch(spray->scratch, fft->n, s);
+  s.out = out;
+  s.capacity = capacity;
+  s.n = fft->n;
+  s.logn = fft->logn;
+  s.nn = fft->n * fft->n;
+  s.tiles = foam_tiles(fft->n);
+  s.dt = dt;
+  s.step = step;
+  SprayTiles t{};
+  for (int i = 0; i < count; i++)
+  {
+    if (tiles)
+    {
+      t.t[i][0] = tiles[2 * i];
+      t.t[i][1] = tiles[2 * i + 1];
+    }
+    if (settings[i].rate != 0.0f)  // a pair that never emits has no items
+      s.c[s.pairs++] = SprayPair{p.c[i].jac, settings[i].threshold, settings[i].rate, settings[i].seed, i};
+  }
+  HIP_TRY(launch_spray_emit(s, p, r, t, velocity != 0, fft->stream, fft->cus), who.c_str());
+  return OCEAN_OK;
+}
+
+// An emitter that has emitted, else null with a message
+static ocean_spray* spray_emitted(ocean_spray* s, const char* who)
+{
+  if (!s)
+  {
+    fail(OCEAN_ERR_INVALID, std::string(who) + ": null emitter");
+    return nullptr;
+  }
+  if (!s->scratch)
+  {
+    fail(OCEAN_ERR_INVALID, std::string(who) + ": the emitter has no counts yet (call ocean_spray_emit)");
+    return nullptr;
+  }
+  return s;
+}
+
+const int64_t* ocean_spray_counts_device(ocean_spray* s)
+{
+  return spray_emitted(s, "ocean_spray_counts_device") ? static_cast<const int64_t*>(s->scratch) : nullptr;
+}
+
+int ocean_spray_counts(ocean_spray* s, int64_t out[18])
+{
+  if (!spray_emitted(s, "ocean_spray_counts"))
+    return OCEAN_ERR_INVALID;
+  if (!out)
+    return fail(OCEAN_ERR_INVALID, "ocean_spray_counts: null output");
+  HIP_TRY(hipMemcpyAsync(out, s->scratch, 18 * sizeof(int64_t), hipMemcpyDeviceToHost, s->fft->stream),
+          "ocean_spray_counts");
+  HIP_TRY(hipStreamSynchronize(s->fft->stream), "ocean_spray_counts");
   return OCEAN_OK;
 }
 

@@ -412,6 +412,44 @@ struct HullCall
 // p.atlas non-null: sampled from the atlas, which the caller has repacked (launch_surface_atlas).
 hipError_t launch_hulls_loads(const SurfaceParams& p, const SurfaceRates& r, bool velocity, const HullCall& h,
                               const HullFold* folds, int n_folds, hipStream_t stream, int cus);
+// Spray emitters (ocean_spray_emit, include/oceanfft.h, device/k_spray.h): the ordered compaction of the
+// emitting texels of the pairs' Jacobian maps into 8-float records. One emitting pair (rate != 0) of the
+// launch: its map and settings, and its index in the request (the id's top four bits).
+struct SprayPair
+{
+  const float* jac;
+  float threshold, rate;
+  uint32_t seed;
+  int index;
+};
+// The scratch behind an ocean_spray: table int64[18] (written, found, found per pair), then per stage-1
+// item its exclusive prefix (int64: found reaches 2^32) and its count (spray_scratch_bytes).
+struct SprayCall
+{
+  int64_t* table;
+  int64_t* offset;    // [pairs * tiles]
+  uint32_t* partial;  // [pairs * tiles]
+  float* out;         // [capacity][8] or null
+  int64_t capacity;
+  int n, logn, nn;    // map side, its log2, texels per map
+  int tiles;          // stage-1 items per pair: foam_tiles(n)
+  int pairs;          // emitting pairs, 0 .. 16
+  float dt;
+  uint32_t step;
+  SprayPair c[kMaxSurfaceCascades];
+};
+// Stage 4's own values: the request's tile offsets per pair (all pairs, emitting or not)
+struct SprayTiles
+{
+  int32_t t[kMaxSurfaceCascades][2];
+};
+size_t spray_scratch_bytes(int n);
+// The pointers of a scratch buffer of spray_scratch_bytes(n) bytes into s
+void spray_scratch(void* scratch, int n, SprayCall& s);
+// At most four launches: count, scan, and with capacity > 0 scatter and fill (p and r over all pairs of the
+// request; r is read with velocity only).
+hipError_t launch_spray_emit(const SprayCall& s, const SurfaceParams& p, const SurfaceRates& r, const SprayTiles& tiles,
+                             bool velocity, hipStream_t stream, int cus);
 void launch_surface_atlas(const SurfaceParams& p, hipStream_t stream, int cus);
 size_t surface_atlas_texels(const SurfaceParams& p);
 bool surface_use_atlas(const SurfaceParams& p, int64_t points);

@@ -285,4 +285,63 @@ Vision::ID HullSet::Loads(const std::vector<Generator*>& generators, const float
   return loads;
 }
 
+SprayEmitter::SprayEmitter(Vision::RenderDevice* device, FFTCalculator* fft) : renderDevice(device)
+{
+  if (ocean_spray_create(&spray, fft ? fft->GetPlan() : nullptr) != OCEAN_OK)
+    throw std::runtime_error(std::string("SprayEmitter: ") + ocean_last_error());
+}
+
+SprayEmitter::~SprayEmitter()
+{
+  ocean_spray_destroy(spray);
+  if (records)
+    renderDevice->DestroyTexture2D(records);
+}
+
+Vision::ID SprayEmitter::Emit(const std::vector<Generator*>& generators, const ocean_spray_settings* settings,
+                              const int32_t* tiles, float dt, uint32_t step, bool velocity, int64_t capacity)
+{
+  if (capacity < 1)
+    throw std::runtime_error("SprayEmitter::Emit: need room for at least one record");
+  if (!records || recordCapacity != capacity)
+  {
+    if (records)
+      renderDevice->DestroyTexture2D(records);
+    records = 0;
+    Vision::Texture2DDesc desc;
+    desc.Width = 2 * (std::size_t)capacity;
+    desc.Height = 1;
+    desc.PixelType = Vision::PixelType::RGBA32Float;
+    records = renderDevice->CreateTexture2D(desc);
+    recordCapacity = capacity;
+  }
+  std::vector<ocean_generator*> gens;
+  std::vector<int> cascades;
+  for (auto* g : generators)
+  {
+    gens.push_back(g->GetHandle());
+    cascades.push_back(0);
+  }
+  const int rc = ocean_spray_emit(spray, gens.data(), cascades.data(), (int)gens.size(), settings, tiles, dt, step,
+                                  velocity ? 1 : 0, capacity,
+                                  static_cast<float*>(renderDevice->GetTexturePointer(records)));
+  if (rc != OCEAN_OK)
+    throw std::runtime_error(std::string("SprayEmitter::Emit: ") + ocean_last_error());
+  return records;
+}
+
+void SprayEmitter::GetCounts(int64_t out[18]) const
+{
+  if (ocean_spray_counts(spray, out) != OCEAN_OK)
+    throw std::runtime_error(std::string("SprayEmitter::GetCounts: ") + ocean_last_error());
+}
+
+const int64_t* SprayEmitter::GetCountsDevice() const
+{
+  const int64_t* table = ocean_spray_counts_device(spray);
+  if (!table)
+    throw std::runtime_error(std::string("SprayEmitter::GetCountsDevice: ") + ocean_last_error());
+  return table;
+}
+
 }  // namespace Waves

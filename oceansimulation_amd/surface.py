@@ -11,7 +11,7 @@ import ctypes
 import numpy as np
 
 from . import hip
-from .capi import check, lib
+from .capi import OCEAN_ERR_INVALID, OceanError, OceanSpraySettings, check, lib
 from .hip import DeviceBuffer
 
 FLOATS_PER_VERTEX = 8  # x, y, z, jacobian, nx, ny, nz, 0 (query: base x, height, base z, ..., residual)
@@ -239,6 +239,92 @@ class HullSet:
             pass
 
 
+SPRAY_COUNTS = 18  # written, found, found per pair
+
+
+class SprayEmitter:
+    """Emitters at breaking crests (ocean_spray, include/oceanfft.h): the texels of a sampler's pairs whose
+    Jacobian is under the pair's threshold, thinned by rate * dt, as an ordered list of 8-float records
+    (displaced x, y, z, threshold - J, velocity x, y, z in m/s, id = pair << 28 | texel as uint32 bits)."""
+
+    def __init__(self, fft):
+        self.fft = fft
+        h = ctypes.c_void_p()
+        check(lib().ocean_spray_create(ctypes.byref(h), fft.handle), "ocean_spray_create")
+        self._h = h
+
+    @property
+    def handle(self):
+        return self._h
+
+    @staticmethod
+    def _settings(settings, count):
+        if isinstance(settings, (OceanSpraySettings, dict)):
+            settings = [settings] * count
+        arr = (OceanSpraySettings * len(settings))()
+        for i, s in enumerate(settings):
+            if isinstance(s, dict):
+                lib().ocean_default_spray_settings(ctypes.byref(arr[i]))
+                for k, v in s.items():
+                    if k not in ("threshold", "rate", "seed"):
+                        raise AttributeError(f"ocean_spray_settings has no field {k!r}")
+                    setattr(arr[i], k, v)
+            else:
+                arr[i] = OceanSpraySettings(s.threshold, s.rate, s.seed)
+        return arr
+
+    def emit(self, sampler: SurfaceSampler, settings, dt: float, step: int, out_ptr: int = 0, capacity: int = 0,
+             velocity: bool = True, tiles=None) -> None:
+        """Enqueue one call on the plan's stream: device records (capacity, 8), or with capacity 0 the counts
+        alone. settings: one OceanSpraySettings or dict of its fields for every pair, or a list of them;
+        tiles: (pairs, 2) int32 plane offsets or None."""
+        n = len(sampler.pairs)
+        arr = self._settings(settings, n)
+        if len(arr) != n:
+            raise ValueError("one ocean_spray_settings per (generator, cascade) pair")
+        t = None
+        if tiles is not None:
+            t = np.ascontiguousarray(tiles, np.int32).reshape(n, 2)
+        check(lib().ocean_spray_emit(self._h, sampler._gens, sampler._cas, n, arr,
+                                     ctypes.c_void_p(t.ctypes.data if t is not None else 0), ctypes.c_float(dt),
+                                     ctypes.c_uint32(step), int(velocity), ctypes.c_int64(capacity),
+                                     ctypes.c_void_p(out_ptr)), "ocean_spray_emit")
+
+    def emit_host(self, sampler: SurfaceSampler, settings, dt: float, step: int, capacity: int, velocity: bool = True,
+                  tiles=None):
+        """(records (written, 8) float32, counts (18,) int64) of one call with room for `capacity` records."""
+        out = DeviceBuffer(capacity * FLOATS_PER_VERTEX * 4) if capacity else None
+        self.emit(sampler, settings, dt, step, out.ptr if capacity else 0, capacity, velocity, tiles)
+        counts = self.counts()
+        if not capacity:
+            return np.zeros((0, FLOATS_PER_VERTEX), np.float32), counts
+        return out.to_host((capacity, FLOATS_PER_VERTEX))[:int(counts[0])].copy(), counts
+
+    def counts(self) -> np.ndarray:
+        """The last call's counts on the host; synchronises the plan's stream."""
+        out = (ctypes.c_int64 * SPRAY_COUNTS)()
+        check(lib().ocean_spray_counts(self._h, out), "ocean_spray_counts")
+        return np.array(out[:], np.int64)
+
+    def counts_device(self) -> int:
+        """The int64[18] count table in device memory (OceanError before the first emit)."""
+        ptr = lib().ocean_spray_counts_device(self._h)
+        if not ptr:
+            raise OceanError(OCEAN_ERR_INVALID, "ocean_spray_counts_device")
+        return int(ptr)
+
+    def close(self) -> None:
+        if self._h:
+            lib().ocean_spray_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def host_cascades(pairs):
     """[(height, disp, jac, planeSize, displacement)] host copies, for the CPU oracle."""
     out = []
@@ -249,4 +335,4 @@ def host_cascades(pairs):
     return out
 
 
-__all__ = ["SurfaceSampler", "HullSet", "host_cascades", "FLOATS_PER_VERTEX", "hip"]
+__all__ = ["SurfaceSampler", "HullSet", "SprayEmitter", "host_cascades", "FLOATS_PER_VERTEX", "hip"]

@@ -11,7 +11,7 @@ import ctypes
 import numpy as np
 
 from . import capi, hip
-from .capi import OceanFoamSettings, OceanSettings, check, lib
+from .capi import OceanFoamSettings, OceanSettings, OceanSpraySettings, check, lib
 
 
 def default_settings(**overrides) -> OceanSettings:
@@ -42,6 +42,21 @@ def apply_foam_settings(s: OceanFoamSettings, **overrides) -> OceanFoamSettings:
     for k, v in overrides.items():
         if k not in ("bias", "gain", "decay", "level"):
             raise AttributeError(f"ocean_foam_settings has no field {k!r}")
+        setattr(s, k, v)
+    return s
+
+
+def default_spray_settings(**overrides) -> OceanSpraySettings:
+    """ocean_spray_settings defaults (threshold 0.9, rate 8, seed 0) with keyword overrides."""
+    s = OceanSpraySettings()
+    lib().ocean_default_spray_settings(ctypes.byref(s))
+    return apply_spray_settings(s, **overrides)
+
+
+def apply_spray_settings(s: OceanSpraySettings, **overrides) -> OceanSpraySettings:
+    for k, v in overrides.items():
+        if k not in ("threshold", "rate", "seed"):
+            raise AttributeError(f"ocean_spray_settings has no field {k!r}")
         setattr(s, k, v)
     return s
 
