@@ -17,7 +17,7 @@
 // Usage: waveapp_headless [--n 256] [--frames 600] [--dt 0.0166667] [--freeze A:B]...
 //                         [--edit F:G.field=value]... [--reseed reference|on-edit]
 //                         [--mesh RES (0 = no surface step)] [--probes K] [--velocity] [--mips] [--bodies K]
-//                         [--rays K] [--dump DIR]
+//                         [--rays K] [--image WxH] [--dump DIR]
 // Prints one JSON line. --dump DIR writes height_G.npy, disp_G.npy, jac_G.npy (G = 0..2),
 // surface.npy ((RES+1)^2 x 8 floats) and scene.json for the last frame.
 // --probes K (default 0: nothing changes): after the last frame, the water surface above K points on a
@@ -43,6 +43,11 @@
 // (Generator::BuildBounds) and casts the ring (SurfaceSampler::Raycast: step 0.25, 256 steps, 10 bisections,
 // 4 iterations, tolerance 1e-3, fixed steps, pad 0). The JSON line gains "rays" and "ray_hits"; --dump adds
 // rays.npy (K x 8), hits.npy (K x 16) and bounds.npy (3 x 18) of the last frame.
+// --image WxH (default off: nothing changes): the picture of the reference's camera (ocean_default_camera,
+// shading and march). Every frame builds the generators' bounds (Generator::BuildBounds) and renders the image
+// (SurfaceSampler::Render). The JSON line gains "image_hits" (pixels whose ray hit the water); --dump adds
+// image.npy (H x W x 4), image_aux.npy (H x W x 4: t, depth, jacobian, status) and image8.npy (H x W x 4, uint8)
+// of the last frame.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -85,7 +90,7 @@ bool set_field(Waves::GeneratorSettings& s, const std::string& f, float v)
   return true;
 }
 
-// numpy .npy v1.0, little-endian float32 (or another 4-byte type: descr), C order
+// numpy .npy v1.0, little-endian float32 (or another 4-byte or 1-byte type: descr), C order
 bool write_npy(const std::string& path, const void* data, const std::vector<size_t>& shape, const char* descr = "<f4")
 {
   std::string dims;
@@ -108,7 +113,7 @@ bool write_npy(const std::string& path, const void* data, const std::vector<size
   const uint16_t hl = (uint16_t)header.size();
   bool ok = std::fwrite(magic, 1, 8, f) == 8 && std::fwrite(&hl, 2, 1, f) == 1 &&
             std::fwrite(header.data(), 1, header.size(), f) == header.size() &&
-            std::fwrite(data, sizeof(float), count, f) == count;
+            std::fwrite(data, descr[2] == '1' ? 1 : sizeof(float), count, f) == count;
   return std::fclose(f) == 0 && ok;
 }
 
@@ -116,14 +121,14 @@ void usage()
 {
   std::fprintf(stderr, "usage: waveapp_headless [--n N] [--frames K] [--dt S] [--freeze A:B]... "
                        "[--edit F:G.field=value]... [--reseed reference|on-edit] [--mesh RES] [--probes K] "
-                       "[--velocity] [--mips] [--bodies K] [--rays K] [--dump DIR]\n");
+                       "[--velocity] [--mips] [--bodies K] [--rays K] [--image WxH] [--dump DIR]\n");
 }
 
 }  // namespace
 
 int main(int argc, char** argv)
 {
-  int n = 256, frames = 600, mesh = 1024, probes = 0, bodies = 0, rays = 0;
+  int n = 256, frames = 600, mesh = 1024, probes = 0, bodies = 0, rays = 0, imageW = 0, imageH = 0;
   float dt = 1.0f / 60.0f;
   bool reseed_every_frame = true, mips = false, velocity = false;
   std::string dump;
@@ -150,6 +155,14 @@ int main(int argc, char** argv)
     else if (a == "--probes") probes = std::atoi(v);
     else if (a == "--bodies") bodies = std::atoi(v);
     else if (a == "--rays") rays = std::atoi(v);
+    else if (a == "--image")
+    {
+      if (std::sscanf(v, "%dx%d", &imageW, &imageH) != 2 || imageW < 1 || imageH < 1)
+      {
+        usage();
+        return 2;
+      }
+    }
     else if (a == "--dump") dump = v;
     else if (a == "--reseed") reseed_every_frame = std::string(v) != "on-edit";
     else if (a == "--freeze")
@@ -269,6 +282,15 @@ int main(int argc, char** argv)
       }
     }
 
+    // the reference's camera
+    ocean_camera imageCamera;
+    ocean_shading imageShading;
+    ocean_march imageMarch;
+    ocean_default_camera(&imageCamera);
+    ocean_default_shading(&imageShading);
+    ocean_default_march(&imageMarch);
+    Vision::ID image = 0;
+
     device.BeginCommandBuffer();
     device.SubmitCommandBuffer();
     const auto t0 = std::chrono::steady_clock::now();
@@ -321,6 +343,13 @@ int main(int argc, char** argv)
           g->BuildBounds();
         rayHits = sampler.Raycast(generators, raysDevice, rays, 0.25f, 256, 10, 4, 1e-3f, INFINITY, 0.0f);
       }
+      if (imageW > 0)
+      {
+        if (rays <= 0)
+          for (auto* g : generators)
+            g->BuildBounds();
+        image = sampler.Render(generators, imageCamera, imageShading, imageMarch, imageW, imageH);
+      }
       device.SubmitCommandBuffer();
     }
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -348,6 +377,22 @@ int main(int argc, char** argv)
         generators[i]->GetBounds(&boundsHost[18 * (size_t)i]);
       for (int k = 0; k < rays; k++)
         rayHitCount += rayHitsHost[16 * (size_t)k + 12] == 0.0f;
+    }
+
+    std::vector<float> imageHost, imageAuxHost;
+    std::vector<uint8_t> imageBytesHost;
+    int imageHits = 0;
+    if (imageW > 0 && frames > 0)
+    {
+      const size_t px = (size_t)imageW * imageH;
+      imageHost.resize(px * 4);
+      imageAuxHost.resize(px * 4);
+      imageBytesHost.resize(px * 4);
+      device.GetTexture2DDataRaw(image, imageHost.data());
+      device.GetTexture2DDataRaw(sampler.GetRenderAux(), imageAuxHost.data());
+      device.GetTexture2DDataRaw(sampler.GetRenderBytes(), imageBytesHost.data());
+      for (size_t k = 0; k < px; k++)
+        imageHits += imageAuxHost[4 * k + 3] == 0.0f;
     }
 
     // the ring of buoys: which water is above each of them now (not part of the timed frames)
@@ -507,6 +552,14 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "cannot write %s\n", dump.c_str());
         return 1;
       }
+      if (!imageHost.empty() &&
+          !(write_npy(dump + "/image.npy", imageHost.data(), {(size_t)imageH, (size_t)imageW, 4}) &&
+            write_npy(dump + "/image_aux.npy", imageAuxHost.data(), {(size_t)imageH, (size_t)imageW, 4}) &&
+            write_npy(dump + "/image8.npy", imageBytesHost.data(), {(size_t)imageH, (size_t)imageW, 4}, "|u1")))
+      {
+        std::fprintf(stderr, "cannot write %s\n", dump.c_str());
+        return 1;
+      }
       if (probes > 0 && !(write_npy(dump + "/probes.npy", probeOut.data(), {(size_t)probes, 8}) &&
                           write_npy(dump + "/probe_xz.npy", probeXZ.data(), {(size_t)probes, 2})))
       {
@@ -555,6 +608,8 @@ int main(int argc, char** argv)
     }
     if (!rayHitsHost.empty())
       probeJson += ", \"rays\": " + std::to_string(rays) + ", \"ray_hits\": " + std::to_string(rayHitCount);
+    if (!imageHost.empty())
+      probeJson += ", \"image_hits\": " + std::to_string(imageHits);
     std::printf("{\"app\": \"waveapp_headless\", \"n\": %d, \"cascades\": 3, \"frames\": %d, \"frozen_frames\": %d, "
                 "\"reseeded_frames\": %d, \"reseed\": \"%s\", \"mesh_vertices\": %lld, \"seconds\": %.6f, "
                 "\"ms_per_frame\": %.6f, \"frames_per_s\": %.3f, \"height_field_points_per_s\": %.6e, "

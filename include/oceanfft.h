@@ -658,6 +658,96 @@ int ocean_surface_raycast(ocean_generator* const* gens, const int* cascades, int
                           int64_t n_rays, float step, int max_steps, int refine, int iterations, float tolerance,
                           float slope, float pad, float* out);
 
+/* ---- Camera images: ray-cast pixels shaded with the reference's water, sky and fog ----------------
+ * The last step of a camera model: one fused kernel, one lane per pixel, camera ray -> the march of
+ * ocean_surface_raycast -> fragment stage (on the mip pyramid by the pixel's footprint when lod_scale > 0)
+ * -> the water colour of resources/waveShader.glsl:146-160 -> the fog of :221-233 -> the sky of :41-63.
+ * No rasteriser: the picture is what the rays see. Not reproduced: the reference's double 8-bit
+ * quantisation (a BGRA8 framebuffer, then the post pass) and its finite warped mesh; here the water reaches
+ * far_plane. The 45 degree field of view of ocean_default_camera is this library's choice (the reference's
+ * value lives in its engine, not in its tree).
+ *
+ * ocean_camera: position and a world-space basis (viewInverse columns 0, 1 and -column 2); near_plane and
+ * far_plane are depth planes as in the rasteriser; lod_scale 0 samples level 0 and needs no pyramid.
+ * ocean_shading: WaveRenderData of the reference's src/Renderer.h, and the fog density of
+ * waveShader.glsl:230. ocean_march: ocean_surface_raycast's parameters.
+ *
+ * Contract, per pixel (i, j) (row 0 is the top row, x fastest), in unfused fp32:
+ *   ray:  aspect = (float)width / (float)height;  T = tan_half_fov_y
+ *         x = (((2*(i + 0.5)) / (float)width) - 1) * (aspect * T)
+ *         y = (1 - ((2*(j + 0.5)) / (float)height)) * T
+ *         len = sqrt((x*x + y*y) + 1)
+ *         d.k = ((x*right.k + y*up.k) + forward.k) / len
+ *         ray = (position, near_plane*len, d, far_plane*len)       ocean_camera_rays writes exactly these
+ *   march: ocean_surface_raycast's contract on that ray: status, t, the point V of the final evaluation
+ *         and the fragment stage at V.xz; view depth z = t / len. With lod_scale > 0 the fragment stage is
+ *         ocean_surface_sample_lod's at V.xz with footprint = lod_scale * (z * ((2*T) / (float)height)),
+ *         the world size of a pixel at that depth; the march itself always runs on level 0.
+ *   host constants, in double, rounded once: L = light_direction / |light_direction|,
+ *         cthr = cos(sun_view_angle * 0.0174533), cfade = cos((sun_view_angle + max(sun_falloff_angle, 0.01))
+ *         * 0.0174533)
+ *   dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z;  normalize(v) = v / sqrt(dot(v, v));  min and max return NaN
+ *         when either operand is NaN
+ *   sky(v): u = normalize(v);  s = dot(L, u)
+ *         e = min(max((s - cfade) / (cthr - cfade), 0), 1);  w = (e*e) * (3 - 2*e);  w = w * (w*w)
+ *         m = 0.8 - u.y / 0.8;  m = m*m
+ *         box.c = sky_color.c*(1 - m) + light_color.c*m
+ *         sky.c = (1 - w)*box.c + (2*w)*light_color.c
+ *   water (status 0 only; hits from below are shaded the same):
+ *         n = the fragment stage's normal;  P = V;  I = -normalize(position - P)
+ *         k = 2*dot(n, I);  r = I - k*n
+ *         diffuse = max(dot(n, L), 0) * 0.3
+ *         sp = max(dot(r, L), 0);  sp = sp*sp five times;  specular = sp * 0.5
+ *         scatter = max(P.y * 0.1, 0);  light = (diffuse + 0.5) + specular
+ *         col.c = ((light * wave_color.c) * sky(r).c) + scatter * scatter_color.c
+ *         f = max(1 - expf(-((z - fog_begin) * fog_density)), 0)
+ *         out.c = col.c*(1 - f) + sky(d).c*f
+ *   every other status: out = sky(d)
+ *   image = (out, 1);  aux = (t, z, the fragment stage's jacobian, status), OUTSIDE gives (0, 0, 0, 1)
+ *   image8: per channel !(c > 0) ? 0 : (uint8)(min(c, 1)*255 + 0.5), alpha 255, RGBA order
+ * image and aux are width*height x 4 floats, image8 width*height x 4 bytes, all device memory; any of them
+ * may be null, not all. (generator, cascade) rules, stream and the freshness of the bounds as
+ * ocean_surface_raycast; with lod_scale > 0 every generator's pyramid must be built and fresh, as
+ * ocean_surface_sample_lod asks. One kernel launch (a 16 x 16 pixel tile per work item), no allocation, no
+ * host synchronisation, no atomics: a call replays bit for bit.
+ * OCEAN_ERR_INVALID, before any device call: null gens / cascades / camera / shading / march; width or
+ * height outside 1..16384; a non-finite camera entry; tan_half_fov_y <= 0; near_plane < 0 or near_plane >=
+ * far_plane; lod_scale negative or non-finite; a non-finite shading entry; a zero light_direction; a negative
+ * sun_view_angle, sun_falloff_angle or fog_density; the march's rules as ocean_surface_raycast states them;
+ * all three outputs null. */
+typedef struct ocean_camera
+{
+  float position[3];
+  float right[3], up[3], forward[3]; /* world-space basis: viewInverse columns 0, 1 and -column 2 */
+  float tan_half_fov_y, near_plane, far_plane;
+  float lod_scale; /* 0: level-0 sampling, no pyramid needed */
+} ocean_camera;
+typedef struct ocean_shading /* WaveRenderData of the reference's src/Renderer.h */
+{
+  float wave_color[3], scatter_color[3], sky_color[3], light_color[3], light_direction[3];
+  float sun_view_angle, sun_falloff_angle, fog_begin, fog_density;
+} ocean_shading;
+typedef struct ocean_march
+{
+  float step;
+  int max_steps, refine, iterations;
+  float tolerance, slope, pad;
+} ocean_march;
+/* Position (0, 5, 0), pitch -5 and yaw -135 degrees, near 1, far 1500 (src/Renderer.cpp:14-16), with
+ * forward = (cos p sin y, sin p, -cos p cos y), right = (cos y, 0, sin y), up = right x forward evaluated in
+ * double and rounded once; a 45 degree vertical field of view; lod_scale 0. */
+void ocean_default_camera(ocean_camera* camera);
+/* src/Renderer.h:22-29 as written there, fog_density 0.0025 (waveShader.glsl:230). */
+void ocean_default_shading(ocean_shading* shading);
+/* step 0.25, 256 steps, 10 bisections, 4 iterations, tolerance 1e-3, slope 1, pad 0. */
+void ocean_default_march(ocean_march* march);
+/* The rays of the contract above: rays is width*height x 8 floats in device memory, enqueued on hip_stream
+ * (a hipStream_t; null: the default stream). The camera's rules as ocean_camera_render; null rays refused. */
+int ocean_camera_rays(const ocean_camera* camera, int width, int height, float* rays, void* hip_stream);
+int ocean_camera_render(ocean_generator* const* gens, const int* cascades, int count, const ocean_camera* camera,
+                        const ocean_shading* shading, const ocean_march* march, int width, int height, float* image,
+                        float* aux, uint8_t* image8);
+
 /* ---- Hull sets: net wave force and torque on batches of floating bodies -------------------------
  * The consumer of the three sections above: a floating body is a set of hull points, each carrying a
  * displaced volume and drag coefficients; per step the caller hands in the bodies' poses and gets one

@@ -19,7 +19,8 @@ using ID = uint32_t;  // 0 = none, as in the reference (src/Generator.h:61-92)
 enum class PixelType
 {
   RGBA32Float,  // 16 B texels (heightMap, displacementMap, spectra)
-  R32Float      // 4 B texels (jacobian)
+  R32Float,     // 4 B texels (jacobian)
+  RGBA8         // 4 B texels (camera images, 8 bits per channel)
 };
 
 enum class MinMagFilter { Nearest, Linear };

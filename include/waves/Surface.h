@@ -71,6 +71,20 @@ public:
   Vision::ID Raycast(const std::vector<Generator*>& generators, const float* raysDevice, int64_t rays, float step,
                      int maxSteps, int refine, int iterations, float tolerance, float slope, float pad);
 
+  // The picture a camera sees (ocean_camera_render, oceanfft.h): per pixel the camera's ray is marched as
+  // Raycast marches it and the hit is shaded with the reference's water colour, fog and sky
+  // (resources/waveShader.glsl), in one fused pass; there is no rasteriser, and the water reaches the far
+  // plane. Every generator needs Generator::BuildBounds() since its last CalculateOcean, and with
+  // camera.lod_scale > 0 (the fragment stage then reads the mip level of each pixel's footprint) also
+  // Generator::GenerateMips(). Returns the image, width x height RGBA32F texels, row 0 on top;
+  // GetRenderAux() is (t, view depth, jacobian, status as Raycast's) per pixel and GetRenderBytes() the
+  // image as RGBA8. Enqueued on the device's stream; the three textures are owned by the sampler and reused
+  // while the size stays the same.
+  Vision::ID Render(const std::vector<Generator*>& generators, const ocean_camera& camera, const ocean_shading& shading,
+                    const ocean_march& march, int width, int height);
+  Vision::ID GetRenderAux() const { return renderAux; }
+  Vision::ID GetRenderBytes() const { return renderBytes; }
+
   // Sample with the persistent foam (ocean_surface_sample_plane_foam, oceanfft.h): the same mesh and the
   // same texture layout as Sample, with the generators' averaged foam in the last float of each vertex,
   // which Sample leaves 0. Every generator needs a Generator::AdvanceFoam() or ResetFoam() first. Its own
@@ -90,6 +104,8 @@ public:
                         int iterations, float tolerance);
 
 private:
+  Vision::ID renderImage = 0, renderAux = 0, renderBytes = 0;
+  int renderWidth = 0, renderHeight = 0;
   Vision::ID waterPoints = 0;
   int64_t waterPointCount = 0;
   Vision::ID verticesFoam = 0;

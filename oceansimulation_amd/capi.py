@@ -73,6 +73,54 @@ class OceanSpraySettings(ctypes.Structure):
 
 assert ctypes.sizeof(OceanSpraySettings) == 12
 
+
+class OceanCamera(ctypes.Structure):
+    """ocean_camera: position, world-space basis (viewInverse columns 0, 1 and -column 2), lens, 64 bytes."""
+
+    _fields_ = [
+        ("position", ctypes.c_float * 3),
+        ("right", ctypes.c_float * 3),
+        ("up", ctypes.c_float * 3),
+        ("forward", ctypes.c_float * 3),
+        ("tan_half_fov_y", ctypes.c_float),
+        ("near_plane", ctypes.c_float),
+        ("far_plane", ctypes.c_float),
+        ("lod_scale", ctypes.c_float),
+    ]
+
+
+class OceanShading(ctypes.Structure):
+    """ocean_shading: WaveRenderData of the reference's src/Renderer.h and the fog density, 76 bytes."""
+
+    _fields_ = [
+        ("wave_color", ctypes.c_float * 3),
+        ("scatter_color", ctypes.c_float * 3),
+        ("sky_color", ctypes.c_float * 3),
+        ("light_color", ctypes.c_float * 3),
+        ("light_direction", ctypes.c_float * 3),
+        ("sun_view_angle", ctypes.c_float),
+        ("sun_falloff_angle", ctypes.c_float),
+        ("fog_begin", ctypes.c_float),
+        ("fog_density", ctypes.c_float),
+    ]
+
+
+class OceanMarch(ctypes.Structure):
+    """ocean_march: ocean_surface_raycast's parameters, 28 bytes."""
+
+    _fields_ = [
+        ("step", ctypes.c_float),
+        ("max_steps", ctypes.c_int),
+        ("refine", ctypes.c_int),
+        ("iterations", ctypes.c_int),
+        ("tolerance", ctypes.c_float),
+        ("slope", ctypes.c_float),
+        ("pad", ctypes.c_float),
+    ]
+
+
+assert ctypes.sizeof(OceanCamera) == 64 and ctypes.sizeof(OceanShading) == 76 and ctypes.sizeof(OceanMarch) == 28
+
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _f = ctypes.c_float
@@ -139,6 +187,12 @@ SIGNATURES = {
     "ocean_generator_bounds": (_i, [_vp, _i, _fp]),
     "ocean_generator_bounds_device": (_vp, [_vp]),
     "ocean_surface_raycast": (_i, [_vp, _vp, _i, _vp, ctypes.c_int64, _f, _i, _i, _i, _f, _f, _f, _vp]),
+    "ocean_default_camera": (None, [ctypes.POINTER(OceanCamera)]),
+    "ocean_default_shading": (None, [ctypes.POINTER(OceanShading)]),
+    "ocean_default_march": (None, [ctypes.POINTER(OceanMarch)]),
+    "ocean_camera_rays": (_i, [ctypes.POINTER(OceanCamera), _i, _i, _vp, _vp]),
+    "ocean_camera_render": (_i, [_vp, _vp, _i, ctypes.POINTER(OceanCamera), ctypes.POINTER(OceanShading),
+                                 ctypes.POINTER(OceanMarch), _i, _i, _vp, _vp, _vp]),
     "ocean_default_foam_settings": (None, [_fsp]),
     "ocean_generator_foam_settings": (_fsp, [_vp, _i]),
     "ocean_generator_advance_foam": (_i, [_vp, _f]),

@@ -1,7 +1,7 @@
 // ocean_capi_surface.cpp — the part of the C ABI (include/oceanfft.h) that consumes a generator's maps:
 // the map getters, ocean_surface_sample / _query / _sample_plane, the mip pyramids and the *_lod requests,
 // the rate maps and ocean_surface_velocity, the depth layers and ocean_water_kinematics, the bounds and ocean_surface_raycast, the persistent foam with
-// ocean_surface_sample_foam, the hull sets and the spray emitters.
+// ocean_surface_sample_foam, the camera images (ocean_camera_render), the hull sets and the spray emitters.
 // The plans and generators themselves are in ocean_capi.cpp, their exchanges in ocean_capi_exchange.cpp;
 // ocean_capi_internal.h has what the three share.
 //
@@ -58,6 +58,24 @@ int check_fixed_point(int iterations, float tolerance, const std::string& who)
     return fail(OCEAN_ERR_INVALID, who + ": iterations outside 0..64");
   if (!(tolerance >= 0.0f) || !std::isfinite(tolerance))
     return fail(OCEAN_ERR_INVALID, who + ": tolerance must be finite and >= 0");
+  return OCEAN_OK;
+}
+
+// The scalar rules of a march (ocean_surface_raycast, ocean_camera_render)
+int check_march(float step, int max_steps, int refine, int iterations, float tolerance, float slope, float pad,
+                const std::string& who)
+{
+  if (!std::isfinite(step) || !(step > 0.0f))
+    return fail(OCEAN_ERR_INVALID, who + ": step must be finite and > 0");
+  if (max_steps < 1 || max_steps > 65535)
+    return fail(OCEAN_ERR_INVALID, who + ": max_steps outside 1..65535");
+  if (refine < 0 || refine > 32)
+    return fail(OCEAN_ERR_INVALID, who + ": refine outside 0..32");
+  TRY(check_fixed_point(iterations, tolerance, who));
+  if (!(pad >= 0.0f) || !std::isfinite(pad))
+    return fail(OCEAN_ERR_INVALID, who + ": pad must be finite and >= 0");
+  if (!(slope >= 0.0f))
+    return fail(OCEAN_ERR_INVALID, who + ": slope must be >= 0 (+inf: fixed steps)");
   return OCEAN_OK;
 }
 
@@ -542,6 +560,21 @@ int ocean_generator_bounds(ocean_generator* g, int cascade, float out[18])
   return OCEAN_OK;
 }
 
+// The bounds rows of a request's cascades, which must be built and not older than the maps
+static int surface_bounds_rows(ocean_generator* const* gens, const int* cascades, int count, RaycastParams& r,
+                               const char* who)
+{
+  for (int i = 0; i < count; i++)
+  {
+    ocean_generator* g = gens[i];
+    if (!g->bounds || !g->bounds_fresh)
+      return not_fresh(who, i, g->bounds, " has no bounds (call", " has stale bounds (its maps were rewritten since",
+                       "ocean_generator_build_bounds");
+    r.bounds[i] = g->bounds + (size_t)cascades[i] * 18;
+  }
+  return OCEAN_OK;
+}
+
 int ocean_surface_raycast(ocean_generator* const* gens, const int* cascades, int count, const float* rays,
                           int64_t n_rays, float step, int max_steps, int refine, int iterations, float tolerance,
                           float slope, float pad, float* out)
@@ -549,31 +582,14 @@ int ocean_surface_raycast(ocean_generator* const* gens, const int* cascades, int
   // the scalar rules first: they need no generator
   if (!gens || !cascades)
     return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: null gens / cascades");
-  if (!std::isfinite(step) || !(step > 0.0f))
-    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: step must be finite and > 0");
-  if (max_steps < 1 || max_steps > 65535)
-    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: max_steps outside 1..65535");
-  if (refine < 0 || refine > 32)
-    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: refine outside 0..32");
-  TRY(check_fixed_point(iterations, tolerance, "ocean_surface_raycast"));
-  if (!(pad >= 0.0f) || !std::isfinite(pad))
-    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: pad must be finite and >= 0");
-  if (!(slope >= 0.0f))
-    return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: slope must be >= 0 (+inf: fixed steps)");
+  TRY(check_march(step, max_steps, refine, iterations, tolerance, slope, pad, "ocean_surface_raycast"));
   if (n_rays < 0 || (n_rays > 0 && (!rays || !out)))
     return fail(OCEAN_ERR_INVALID, "ocean_surface_raycast: null rays/output or negative count");
   SurfaceParams p;
   ocean_fft* fft;
   TRY(surface_params(gens, cascades, count, p, fft, "ocean_surface_raycast"));
   RaycastParams r{};
-  for (int i = 0; i < count; i++)
-  {
-    ocean_generator* g = gens[i];
-    if (!g->bounds || !g->bounds_fresh)
-      return not_fresh("ocean_surface_raycast", i, g->bounds, " has no bounds (call",
-                       " has stale bounds (its maps were rewritten since", "ocean_generator_build_bounds");
-    r.bounds[i] = g->bounds + (size_t)cascades[i] * 18;
-  }
+  TRY(surface_bounds_rows(gens, cascades, count, r, "ocean_surface_raycast"));
   r.step = step;
   r.max_steps = max_steps;
   r.refine = refine;
@@ -584,6 +600,160 @@ int ocean_surface_raycast(ocean_generator* const* gens, const int* cascades, int
   HIP_TRY(launch_surface_raycast(p, r, reinterpret_cast<const float4*>(rays), n_rays, reinterpret_cast<float4*>(out),
                                  fft->stream, fft->cus),
           "ocean_surface_raycast");
+  return OCEAN_OK;
+}
+
+// ---- camera images: ray-cast pixels shaded with the reference's water, sky and fog ----
+void ocean_default_camera(ocean_camera* c)
+{
+  if (!c)
+    return;
+  const double deg = 3.14159265358979323846 / 180.0;
+  const double p = -5.0 * deg, y = -135.0 * deg;  // src/Renderer.cpp:16
+  const double f[3] = {std::cos(p) * std::sin(y), std::sin(p), -std::cos(p) * std::cos(y)};
+  const double r[3] = {std::cos(y), 0.0, std::sin(y)};
+  const double u[3] = {r[1] * f[2] - r[2] * f[1], r[2] * f[0] - r[0] * f[2], r[0] * f[1] - r[1] * f[0]};
+  *c = ocean_camera{};
+  c->position[1] = 5.0f;
+  for (int k = 0; k < 3; k++)
+  {
+    c->right[k] = (float)r[k];
+    c->up[k] = (float)u[k];
+    c->forward[k] = (float)f[k];
+  }
+  c->tan_half_fov_y = (float)std::tan(22.5 * deg);  // a 45 degree vertical field of view: this library's choice
+  c->near_plane = 1.0f;
+  c->far_plane = 1500.0f;
+  c->lod_scale = 0.0f;
+}
+
+void ocean_default_shading(ocean_shading* s)
+{
+  if (s)  // src/Renderer.h:22-29, waveShader.glsl:230
+    *s = ocean_shading{{0.0f, 0.33f, 0.47f}, {0.5f, 0.8f, 0.9f}, {0.53f, 0.8f, 0.94f}, {1.0f, 1.0f, 1.0f},
+                       {0.703f, 0.105f, 0.703f}, 3.0f, 1.0f, 30.0f, 0.0025f};
+}
+
+void ocean_default_march(ocean_march* m)
+{
+  if (m)
+    *m = ocean_march{0.25f, 256, 10, 4, 1e-3f, 1.0f, 0.0f};
+}
+
+// The camera's own rules and its kernel argument
+static int camera_params(const ocean_camera* c, int width, int height, CameraParams& cam, const std::string& who)
+{
+  if (width < 1 || width > 16384 || height < 1 || height > 16384)
+    return fail(OCEAN_ERR_INVALID, who + ": width or height outside 1..16384");
+  const float* entries = c->position;  // 15 floats, then lod_scale
+  static_assert(sizeof(ocean_camera) == 16 * sizeof(float), "ocean_camera is 16 floats");
+  for (int k = 0; k < 15; k++)
+    if (!std::isfinite(entries[k]))
+      return fail(OCEAN_ERR_INVALID, who + ": non-finite camera entry");
+  if (!(c->tan_half_fov_y > 0.0f))
+    return fail(OCEAN_ERR_INVALID, who + ": tan_half_fov_y must be > 0");
+  if (c->near_plane < 0.0f || c->near_plane >= c->far_plane)
+    return fail(OCEAN_ERR_INVALID, who + ": near_plane must be >= 0 and below far_plane");
+  if (!(c->lod_scale >= 0.0f) || !std::isfinite(c->lod_scale))
+    return fail(OCEAN_ERR_INVALID, who + ": lod_scale must be finite and >= 0");
+  cam = CameraParams{};
+  for (int k = 0; k < 3; k++)
+  {
+    cam.pos[k] = c->position[k];
+    cam.right[k] = c->right[k];
+    cam.up[k] = c->up[k];
+    cam.fwd[k] = c->forward[k];
+  }
+  cam.tan_half = c->tan_half_fov_y;
+  cam.near_plane = c->near_plane;
+  cam.far_plane = c->far_plane;
+  cam.lod_scale = c->lod_scale;
+  cam.width = width;
+  cam.height = height;
+  return OCEAN_OK;
+}
+
+int ocean_camera_rays(const ocean_camera* camera, int width, int height, float* rays, void* hip_stream)
+{
+  const std::string who = "ocean_camera_rays";
+  if (!camera)
+    return fail(OCEAN_ERR_INVALID, who + ": null camera");
+  CameraParams cam;
+  TRY(camera_params(camera, width, height, cam, who));
+  if (!rays)
+    return fail(OCEAN_ERR_INVALID, who + ": null rays");
+  HIP_TRY(launch_camera_rays(cam, reinterpret_cast<float4*>(rays), static_cast<hipStream_t>(hip_stream)), who.c_str());
+  return OCEAN_OK;
+}
+
+int ocean_camera_render(ocean_generator* const* gens, const int* cascades, int count, const ocean_camera* camera,
+                        const ocean_shading* shading, const ocean_march* march, int width, int height, float* image,
+                        float* aux, uint8_t* image8)
+{
+  const std::string who = "ocean_camera_render";
+  // the rules that need no generator first
+  if (!gens || !cascades)
+    return fail(OCEAN_ERR_INVALID, who + ": null gens / cascades");
+  if (!camera)
+    return fail(OCEAN_ERR_INVALID, who + ": null camera");
+  if (!shading)
+    return fail(OCEAN_ERR_INVALID, who + ": null shading");
+  if (!march)
+    return fail(OCEAN_ERR_INVALID, who + ": null march");
+  CameraParams cam;
+  TRY(camera_params(camera, width, height, cam, who));
+  static_assert(sizeof(ocean_shading) == 19 * sizeof(float), "ocean_shading is 19 floats");
+  const float* entries = shading->wave_color;
+  for (int k = 0; k < 19; k++)
+    if (!std::isfinite(entries[k]))
+      return fail(OCEAN_ERR_INVALID, who + ": non-finite shading entry");
+  const double lx = shading->light_direction[0], ly = shading->light_direction[1], lz = shading->light_direction[2];
+  const double ll = std::sqrt(lx * lx + ly * ly + lz * lz);
+  if (!(ll > 0.0))
+    return fail(OCEAN_ERR_INVALID, who + ": light_direction is zero");
+  if (shading->sun_view_angle < 0.0f)
+    return fail(OCEAN_ERR_INVALID, who + ": sun_view_angle must be >= 0");
+  if (shading->sun_falloff_angle < 0.0f)
+    return fail(OCEAN_ERR_INVALID, who + ": sun_falloff_angle must be >= 0");
+  if (shading->fog_density < 0.0f)
+    return fail(OCEAN_ERR_INVALID, who + ": fog_density must be >= 0");
+  TRY(check_march(march->step, march->max_steps, march->refine, march->iterations, march->tolerance, march->slope,
+                  march->pad, who));
+  if (!image && !aux && !image8)
+    return fail(OCEAN_ERR_INVALID, who + ": all three outputs are null");
+  SurfaceParams p;
+  ocean_fft* fft;
+  if (cam.lod_scale > 0.0f)
+    TRY(surface_params_lod(gens, cascades, count, p, fft, who.c_str()));
+  else
+    TRY(surface_params(gens, cascades, count, p, fft, who.c_str()));
+  RaycastParams r{};
+  TRY(surface_bounds_rows(gens, cascades, count, r, who.c_str()));
+  r.step = march->step;
+  r.max_steps = march->max_steps;
+  r.refine = march->refine;
+  r.iterations = march->iterations;
+  r.tolerance = march->tolerance;
+  r.slope = march->slope;
+  r.pad = march->pad;
+  ShadingParams sh{};
+  for (int k = 0; k < 3; k++)
+  {
+    sh.wave[k] = shading->wave_color[k];
+    sh.scatter[k] = shading->scatter_color[k];
+    sh.sky[k] = shading->sky_color[k];
+    sh.light[k] = shading->light_color[k];
+    sh.L[k] = (float)((double)shading->light_direction[k] / ll);
+  }
+  // waveShader.glsl:48-49 (DEGREE_TO_RADIANS 0.0174533), in double, rounded once
+  sh.cthr = (float)std::cos((double)shading->sun_view_angle * 0.0174533);
+  sh.cfade = (float)std::cos(((double)shading->sun_view_angle + std::max((double)shading->sun_falloff_angle, 0.01)) *
+                             0.0174533);
+  sh.fog_begin = shading->fog_begin;
+  sh.fog_density = shading->fog_density;
+  HIP_TRY(launch_camera_render(p, r, cam, sh, reinterpret_cast<float4*>(image), reinterpret_cast<float4*>(aux),
+                               reinterpret_cast<uint32_t*>(image8), fft->stream, fft->cus),
+          who.c_str());
   return OCEAN_OK;
 }
 

@@ -337,6 +337,26 @@ struct RaycastParams
 };
 hipError_t launch_surface_raycast(const SurfaceParams& p, const RaycastParams& rc, const float4* rays, int64_t n_rays,
                                   float4* out, hipStream_t stream, int cus);
+// ocean_camera_render / ocean_camera_rays (include/oceanfft.h, device/k_camera.h): the camera as the call
+// passes it, and the shading with the host's constants (L normalised, the two cosines of the sun disc,
+// each evaluated in double and rounded once).
+struct CameraParams
+{
+  float pos[3], right[3], up[3], fwd[3];
+  float tan_half, near_plane, far_plane, lod_scale;
+  int width, height;
+};
+struct ShadingParams
+{
+  float wave[3], scatter[3], sky[3], light[3], L[3];
+  float cthr, cfade, fog_begin, fog_density;
+};
+hipError_t launch_camera_rays(const CameraParams& cam, float4* rays, hipStream_t stream);
+// One launch, a 16 x 16 pixel tile per work item; any of image / aux (float4 per pixel) / image8 (4 bytes per
+// pixel) may be null. p.c[i].*_mip set when cam.lod_scale > 0.
+hipError_t launch_camera_render(const SurfaceParams& p, const RaycastParams& rc, const CameraParams& cam,
+                                const ShadingParams& sh, float4* image, float4* aux, uint32_t* image8,
+                                hipStream_t stream, int cus);
 // Persistent foam (ocean_generator_advance_foam, include/oceanfft.h, device/k_foam.h). FoamParams above is
 // the displacement the row pass computes the Jacobian with; these are the step's values, per cascade.
 struct FoamCascade

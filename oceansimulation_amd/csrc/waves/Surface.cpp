@@ -1,6 +1,6 @@
 // Waves::SurfaceSampler over ocean_surface_sample_plane / ocean_surface_query /
 // ocean_surface_sample_plane_lod / ocean_surface_velocity / ocean_surface_sample_plane_foam /
-// ocean_water_kinematics, and Waves::HullSet over ocean_hulls
+// ocean_water_kinematics / ocean_camera_render, and Waves::HullSet over ocean_hulls
 // (include/oceanfft.h).
 #include "waves/Surface.h"
 
@@ -26,6 +26,9 @@ SurfaceSampler::~SurfaceSampler()
     renderDevice->DestroyTexture2D(verticesFoam);
   if (waterPoints)
     renderDevice->DestroyTexture2D(waterPoints);
+  for (Vision::ID id : {renderImage, renderAux, renderBytes})
+    if (id)
+      renderDevice->DestroyTexture2D(id);
 }
 
 Vision::ID SurfaceSampler::Sample(const std::vector<Generator*>& generators, const float camera[5], int res)
@@ -234,6 +237,46 @@ Vision::ID SurfaceSampler::Kinematics(const std::vector<Generator*>& generators,
   if (rc != OCEAN_OK)
     throw std::runtime_error(std::string("SurfaceSampler::Kinematics: ") + ocean_last_error());
   return waterPoints;
+}
+
+Vision::ID SurfaceSampler::Render(const std::vector<Generator*>& generators, const ocean_camera& camera,
+                                  const ocean_shading& shading, const ocean_march& march, int width, int height)
+{
+  if (width < 1 || height < 1)
+    throw std::runtime_error("SurfaceSampler::Render: need at least one pixel");
+  if (!renderImage || renderWidth != width || renderHeight != height)
+  {
+    for (Vision::ID* id : {&renderImage, &renderAux, &renderBytes})
+    {
+      if (*id)
+        renderDevice->DestroyTexture2D(*id);
+      *id = 0;
+    }
+    Vision::Texture2DDesc desc;
+    desc.Width = (std::size_t)width;
+    desc.Height = (std::size_t)height;
+    desc.PixelType = Vision::PixelType::RGBA32Float;
+    renderImage = renderDevice->CreateTexture2D(desc);
+    renderAux = renderDevice->CreateTexture2D(desc);
+    desc.PixelType = Vision::PixelType::RGBA8;
+    renderBytes = renderDevice->CreateTexture2D(desc);
+    renderWidth = width;
+    renderHeight = height;
+  }
+  std::vector<ocean_generator*> gens;
+  std::vector<int> cascades;
+  for (auto* g : generators)
+  {
+    gens.push_back(g->GetHandle());
+    cascades.push_back(0);
+  }
+  const int rc = ocean_camera_render(gens.data(), cascades.data(), (int)gens.size(), &camera, &shading, &march, width,
+                                     height, static_cast<float*>(renderDevice->GetTexturePointer(renderImage)),
+                                     static_cast<float*>(renderDevice->GetTexturePointer(renderAux)),
+                                     static_cast<uint8_t*>(renderDevice->GetTexturePointer(renderBytes)));
+  if (rc != OCEAN_OK)
+    throw std::runtime_error(std::string("SurfaceSampler::Render: ") + ocean_last_error());
+  return renderImage;
 }
 
 HullSet::HullSet(Vision::RenderDevice* device, FFTCalculator* fft, const float* points, int64_t nPoints,

@@ -7,11 +7,13 @@ ocean_water_kinematics, and the loads on floating bodies built on both, ocean_hu
 from __future__ import annotations
 
 import ctypes
+import math
 
 import numpy as np
 
 from . import hip
-from .capi import OCEAN_ERR_INVALID, OceanError, OceanSpraySettings, check, lib
+from .capi import (OCEAN_ERR_INVALID, OceanCamera, OceanError, OceanMarch, OceanShading, OceanSpraySettings, check,
+                   lib)
 from .hip import DeviceBuffer
 
 FLOATS_PER_VERTEX = 8  # x, y, z, jacobian, nx, ny, nz, 0 (query: base x, height, base z, ..., residual)
@@ -19,6 +21,62 @@ FLOATS_PER_RAY = 8     # ox, oy, oz, tmin, dx, dy, dz, tmax
 FLOATS_PER_HIT = 16    # ocean_surface_raycast's four rows
 FLOATS_PER_WATER_POINT = 12  # ocean_water_kinematics' three rows
 RAY_HIT, RAY_OUTSIDE, RAY_EXIT, RAY_STEP_LIMIT = 0, 1, 2, 3
+
+
+def default_camera() -> OceanCamera:
+    c = OceanCamera()
+    lib().ocean_default_camera(ctypes.byref(c))
+    return c
+
+
+def default_shading(**overrides) -> OceanShading:
+    s = OceanShading()
+    lib().ocean_default_shading(ctypes.byref(s))
+    _set_fields(s, overrides)
+    return s
+
+
+def default_march(**overrides) -> OceanMarch:
+    m = OceanMarch()
+    lib().ocean_default_march(ctypes.byref(m))
+    _set_fields(m, overrides)
+    return m
+
+
+def _set_fields(struct, values) -> None:
+    names = {f[0] for f in struct._fields_}
+    for k, v in values.items():
+        if k not in names:
+            raise AttributeError(f"{type(struct).__name__} has no field {k!r}")
+        if isinstance(getattr(struct, k), ctypes.Array):
+            v = type(getattr(struct, k))(*[float(x) for x in v])
+        setattr(struct, k, v)
+
+
+def camera_pose(position, pitch_deg: float, yaw_deg: float, fov_y_deg: float, near: float, far: float,
+                lod_scale: float = 0.0) -> OceanCamera:
+    """An ocean_camera from the reference's camera angles (src/Renderer.cpp:15-16), with ocean_default_camera's
+    convention evaluated in double and rounded once: forward = (cos p sin y, sin p, -cos p cos y),
+    right = (cos y, 0, sin y), up = right x forward."""
+    p, y = math.radians(pitch_deg), math.radians(yaw_deg)
+    f = (math.cos(p) * math.sin(y), math.sin(p), -math.cos(p) * math.cos(y))
+    r = (math.cos(y), 0.0, math.sin(y))
+    u = (r[1] * f[2] - r[2] * f[1], r[2] * f[0] - r[0] * f[2], r[0] * f[1] - r[1] * f[0])
+    c = OceanCamera()
+    _set_fields(c, dict(position=position, right=r, up=u, forward=f,
+                        tan_half_fov_y=math.tan(math.radians(fov_y_deg) / 2.0), near_plane=near, far_plane=far,
+                        lod_scale=lod_scale))
+    return c
+
+
+def camera_rays_host(camera: OceanCamera, width: int, height: int) -> np.ndarray:
+    """ocean_camera_rays on the default stream -> (height * width, 8) float32, row 0 the top row."""
+    n = int(width) * int(height)
+    out = DeviceBuffer(max(n, 1) * FLOATS_PER_RAY * 4)
+    check(lib().ocean_camera_rays(ctypes.byref(camera), int(width), int(height), ctypes.c_void_p(out.ptr), None),
+          "ocean_camera_rays")
+    hip.synchronize()
+    return out.to_host((n, FLOATS_PER_RAY))
 
 
 class SurfaceSampler:
@@ -178,6 +236,28 @@ class SurfaceSampler:
         self.fft.synchronize()
         return out.to_host((n, FLOATS_PER_HIT)) if n else np.zeros((0, FLOATS_PER_HIT), np.float32)
 
+    # ---- camera images (Generator.BuildBounds first; with camera.lod_scale > 0 also Generator.build_mips) ----
+    def render(self, camera: OceanCamera, shading: OceanShading, march: OceanMarch, width: int, height: int,
+               image_ptr: int = 0, aux_ptr: int = 0, image8_ptr: int = 0) -> None:
+        """Enqueue ocean_camera_render: device image (h, w, 4) float32, aux (h, w, 4) float32 (t, depth, jacobian,
+        status) and image8 (h, w, 4) uint8, any of them 0 (not all)."""
+        check(lib().ocean_camera_render(self._gens, self._cas, len(self.pairs), ctypes.byref(camera),
+                                        ctypes.byref(shading), ctypes.byref(march), int(width), int(height),
+                                        ctypes.c_void_p(image_ptr), ctypes.c_void_p(aux_ptr),
+                                        ctypes.c_void_p(image8_ptr)), "ocean_camera_render")
+
+    def render_host(self, camera: OceanCamera, width: int, height: int, shading: OceanShading = None,
+                    march: OceanMarch = None):
+        """(image (h, w, 4) float32, aux (h, w, 4) float32, image8 (h, w, 4) uint8) of one camera."""
+        shading = default_shading() if shading is None else shading
+        march = default_march() if march is None else march
+        n = int(width) * int(height)
+        image, aux, image8 = DeviceBuffer(max(n, 1) * 16), DeviceBuffer(max(n, 1) * 16), DeviceBuffer(max(n, 1) * 4)
+        self.render(camera, shading, march, width, height, image.ptr, aux.ptr, image8.ptr)
+        self.fft.synchronize()
+        return (image.to_host((height, width, 4)), aux.to_host((height, width, 4)),
+                image8.to_host((height, width, 4), np.uint8))
+
     def plane_host(self, camera, res: int) -> np.ndarray:
         pts = (res + 1) * (res + 1)
         out = DeviceBuffer(pts * FLOATS_PER_VERTEX * 4)
@@ -335,4 +415,5 @@ def host_cascades(pairs):
     return out
 
 
-__all__ = ["SurfaceSampler", "HullSet", "SprayEmitter", "host_cascades", "FLOATS_PER_VERTEX", "hip"]
+__all__ = ["SurfaceSampler", "HullSet", "SprayEmitter", "host_cascades", "FLOATS_PER_VERTEX", "hip", "camera_pose",
+           "default_camera", "default_shading", "default_march", "camera_rays_host"]
