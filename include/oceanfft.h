@@ -973,6 +973,109 @@ int ocean_spray_counts(ocean_spray* spray, int64_t out[18]);
  * a null emitter and before the first ocean_spray_emit. */
 const int64_t* ocean_spray_counts_device(ocean_spray* spray);
 
+/* ---- Spray particles: a persistent pool, stepped, landed on the water, compacted in order --------
+ * ocean_spray_emit says where spray is born and with what velocity; a pool carries it further. One call per
+ * frame, ocean_particles_step, moves every live particle under gravity and linear drag toward a wind, finds
+ * the water under it with ocean_surface_query's fixed point, compacts the survivors in their order into the
+ * next list and the particles that hit the water, in their order, into an impact list, and appends the
+ * records of an ocean_spray_emit call, whose count it reads on the device.
+ *
+ * Settings, one struct per call. The defaults (9.8, 0.5, no wind, 4, 1, 10, 4, 1e-3) are starting points,
+ * not measurements.
+ *     gravity     (m/s^2) downward
+ *     drag        (1/s) linear, toward the wind
+ *     wind        (m/s)
+ *     lifetime    (s) a particle whose age reaches it expires; +inf: never
+ *     gain        launch velocity = gain * the emitter record's velocity
+ *     lift        (m/s) upward, per unit of the emitter record's d = threshold - J (slot 3)
+ *     iterations  of the surface query under a particle, 0..64
+ *     tolerance   (m) of that query */
+typedef struct ocean_particle_settings {
+  float gravity;
+  float drag;
+  float wind[3];
+  float lifetime;
+  float gain;
+  float lift;
+  int32_t iterations;
+  float tolerance;
+} ocean_particle_settings;
+void ocean_default_particle_settings(ocean_particle_settings* out);
+/* A pool is its own object, like an emitter. It is created with everything it ever needs: two lists of
+ * capacity x 8 floats (the current and the next one), the scratch of the compaction (88 B per 256
+ * particles) and the count table; OCEAN_ERR_OOM when an allocation fails. A fresh pool is empty and its
+ * counts are all zero. Calls run on the stream of `fft`. OCEAN_ERR_INVALID for a null out or fft and for a
+ * capacity outside 1..2^28. */
+typedef struct ocean_particles ocean_particles;
+int ocean_particles_create(ocean_particles** out, ocean_fft* fft, int64_t capacity);
+/* Waits for the plan's stream, then frees the pool. A null pool is accepted. */
+int ocean_particles_destroy(ocean_particles* pool);
+/* emit_records: device, the `out` of an ocean_spray_emit call, or null; emit_counts_device: that emitter's
+ * ocean_spray_counts_device. landed_out: device, landed_capacity x 8 floats.
+ *
+ * Contract, in unfused fp32. A particle is 8 floats (px, py, pz, age, ux, uy, uz, id). With s = *settings,
+ * `alive` the length of the list, and each particle r < alive in list order:
+ *     ax = s.drag * (s.wind[0] - ux)
+ *     ay = s.drag * (s.wind[1] - uy) - s.gravity
+ *     az = s.drag * (s.wind[2] - uz)
+ *     ux' = ux + ax * dt   (uy', uz' likewise)                         one product, one sum each
+ *     px' = px + ux' * dt  (py', pz' likewise)                         semi-implicit Euler
+ *     age' = age + dt
+ *     w = slot 1 of ocean_surface_query over the call's pairs at q = (px', pz') with s.iterations and
+ *         s.tolerance: a cold start at q, the height at the last V(p), converged or not
+ *     landed   = !(py' > w)                                            a NaN lands
+ *     expired  = !landed && !(age' < s.lifetime)
+ *     survives = neither
+ * Survivors keep their order: survivor k becomes record k of the next list,
+ *     (px', py', pz', age', ux', uy', uz', id).
+ * Landed particles keep theirs: landed k < min(landed, landed_capacity) is written to landed_out[k] as
+ *     (px', w, pz', age', ux', uy', uz', id),
+ * the point and velocity of impact; records of landed_out from there on are not touched.
+ * landed_capacity == 0 with landed_out == null only counts.
+ * Append: with emit_records non-null and E = emit_counts_device[0] (the emitter's `written`, read on the
+ * device), appended = min(E, capacity - survivors), and emitter record e < appended,
+ * (px, py, pz, d, ux, uy, uz, id), becomes particle survivors + e:
+ *     (px, py, pz, +0, s.gain * ux, s.gain * uy + s.lift * d, s.gain * uz, id)    two products, one sum
+ * with the id's bits unchanged. Appended particles are not moved in this call. A null emit_records appends
+ * nothing, and emit_counts_device is then not read.
+ * Counts: int64[8] in device memory: [0] alive after the call (survivors + appended), [1] alive before it,
+ * [2] survivors, [3] landed found, [4] landed written, [5] expired, [6] appended, [7] dropped
+ * (E - appended). Always [1] == [2] + [3] + [5]. dt == 0 still classifies and compacts.
+ * Positions that are not finite give an unspecified w (their taps stay inside the maps).
+ *
+ * (generator, cascade) rules and stream as ocean_spray_emit: whole-grid generators, all of the plan's N,
+ * 1..16 pairs, gens[0] on the pool's plan, every generator with a frame calculated. Three kernel launches
+ * (move and classify per 256-particle item; scan of the items with the count table; scatter with the
+ * append), the kernel boundaries being the only ordering: no host synchronisation, no atomics, no
+ * allocation. The same call on the same list and maps gives the same bytes on every run and under every CU
+ * budget. A particle costs 32 B read and 32 B written in the first launch beside the query's taps, and, if
+ * it survives or lands, 32 B read and 32 B written in the third.
+ * OCEAN_ERR_INVALID, before any device call, naming the index in `gens` where one applies: a null pool; null
+ * gens / cascades or count outside 1..16; null settings; dt negative or non-finite; a non-finite gravity,
+ * wind, gain or lift; a drag that is negative or non-finite; a lifetime that is not > 0 (+inf accepted);
+ * iterations outside 0..64; a tolerance that is negative or non-finite; a negative landed_capacity; a null
+ * landed_out with landed_capacity > 0; a non-null emit_records with a null emit_counts_device; the
+ * (generator, cascade) rules; a generator that has calculated no frame yet.
+ * No reference counterpart. */
+int ocean_particles_step(ocean_particles* pool, ocean_generator* const* gens, const int* cascades, int count,
+                         const ocean_particle_settings* settings, float dt, const float* emit_records,
+                         const int64_t* emit_counts_device, int64_t landed_capacity, float* landed_out);
+/* Replaces the list with `count` caller records (device, count x 8 floats), in stream order: restoring a
+ * saved state. The counts become (count, 0, 0, ..). OCEAN_ERR_INVALID for a null pool, a count outside
+ * 0..capacity, or null records with count > 0. */
+int ocean_particles_load(ocean_particles* pool, const float* device_records, int64_t count);
+/* Empties the list: ocean_particles_load with count 0. */
+int ocean_particles_clear(ocean_particles* pool);
+/* The current list in device memory, counts[0] records: valid until the next ocean_particles_step,
+ * ocean_particles_load or ocean_particles_destroy on the pool (a step makes the other list current). Null,
+ * with ocean_last_error set, for a null pool. */
+const float* ocean_particles_records(ocean_particles* pool);
+/* Host copy of the counts; synchronises the plan's stream. OCEAN_ERR_INVALID for a null pool or output. */
+int ocean_particles_counts(ocean_particles* pool, int64_t out[8]);
+/* The counts in device memory, valid until the pool is destroyed. Null, with ocean_last_error set, for a
+ * null pool. */
+const int64_t* ocean_particles_counts_device(ocean_particles* pool);
+
 #ifdef __cplusplus
 }
 #endif

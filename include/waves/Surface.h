@@ -194,4 +194,42 @@ private:
   int64_t recordCapacity = 0;
 };
 
+// A persistent pool of spray particles (ocean_particles, oceanfft.h): per Step every particle moves under
+// gravity and drag toward a wind, the ones that reach the water or their lifetime leave, the survivors are
+// compacted in their order and a SprayEmitter call's records are appended. The counts stay on the device, and
+// a step is replayable bit for bit.
+class SprayParticles
+{
+public:
+  SprayParticles(Vision::RenderDevice* device, FFTCalculator* fft, int64_t capacity);
+  ~SprayParticles();
+  SprayParticles(const SprayParticles&) = delete;
+  SprayParticles& operator=(const SprayParticles&) = delete;
+
+  ocean_particles* GetHandle() const { return particles; }
+
+  // One step on the device's stream. emitter with emitRecords (the texture its last Emit returned): the
+  // records to append, or null / 0 for none. landedCapacity > 0: the impacts, (x, water height, z, age),
+  // (velocity, id), go to a buffer texture of 2*landedCapacity x 1 RGBA32F texels owned by the pool and
+  // reused while landedCapacity stays the same, which is returned; else 0 and the impacts are only counted.
+  Vision::ID Step(const std::vector<Generator*>& generators, const ocean_particle_settings& settings, float dt,
+                  const SprayEmitter* emitter, Vision::ID emitRecords, int64_t landedCapacity);
+  // Replaces the list with `count` device records of 8 floats; Clear empties it
+  void Load(const float* recordsDevice, int64_t count);
+  void Clear();
+  // The current list, GetCounts()[0] records of 8 floats: valid until the next Step or Load
+  const float* GetRecords() const;
+  // (alive, alive before, survivors, landed found, landed written, expired, appended, dropped); waits for the
+  // device's stream
+  void GetCounts(int64_t out[8]) const;
+  // The same table in device memory
+  const int64_t* GetCountsDevice() const;
+
+private:
+  Vision::RenderDevice* renderDevice = nullptr;
+  ocean_particles* particles = nullptr;
+  Vision::ID landed = 0;
+  int64_t landedCapacity = 0;
+};
+
 }  // namespace Waves

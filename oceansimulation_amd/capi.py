@@ -74,6 +74,24 @@ class OceanSpraySettings(ctypes.Structure):
 assert ctypes.sizeof(OceanSpraySettings) == 12
 
 
+class OceanParticleSettings(ctypes.Structure):
+    """ocean_particle_settings: one ocean_particles_step call's parameters, 40 bytes."""
+
+    _fields_ = [
+        ("gravity", ctypes.c_float),
+        ("drag", ctypes.c_float),
+        ("wind", ctypes.c_float * 3),
+        ("lifetime", ctypes.c_float),
+        ("gain", ctypes.c_float),
+        ("lift", ctypes.c_float),
+        ("iterations", ctypes.c_int32),
+        ("tolerance", ctypes.c_float),
+    ]
+
+
+assert ctypes.sizeof(OceanParticleSettings) == 40
+
+
 class OceanCamera(ctypes.Structure):
     """ocean_camera: position, world-space basis (viewInverse columns 0, 1 and -column 2), lens, 64 bytes."""
 
@@ -215,6 +233,16 @@ SIGNATURES = {
                               ctypes.c_int64, _vp]),
     "ocean_spray_counts": (_i, [_vp, ctypes.POINTER(ctypes.c_int64)]),
     "ocean_spray_counts_device": (_vp, [_vp]),
+    "ocean_default_particle_settings": (None, [ctypes.POINTER(OceanParticleSettings)]),
+    "ocean_particles_create": (_i, [ctypes.POINTER(_vp), _vp, ctypes.c_int64]),
+    "ocean_particles_destroy": (_i, [_vp]),
+    "ocean_particles_step": (_i, [_vp, _vp, _vp, _i, ctypes.POINTER(OceanParticleSettings), _f, _vp, _vp,
+                                  ctypes.c_int64, _vp]),
+    "ocean_particles_load": (_i, [_vp, _vp, ctypes.c_int64]),
+    "ocean_particles_clear": (_i, [_vp]),
+    "ocean_particles_records": (_vp, [_vp]),
+    "ocean_particles_counts": (_i, [_vp, ctypes.POINTER(ctypes.c_int64)]),
+    "ocean_particles_counts_device": (_vp, [_vp]),
     "ocean_generator_set_half_spectrum": (_i, [_vp, _i]),
     "ocean_generator_set_four_step": (_i, [_vp, _i]),
     "ocean_generator_set_h0_memo": (_i, [_vp, _i]),

@@ -1,0 +1,59 @@
+// launch_particles.hip — spray particles (device/k_particles.h): three launches per step, the move with the
+// fates of every item, the scan over the items with the count table, and the scatter with the append; the
+// kernel boundaries are the ordering between them.
+#include "device/k_particles.h"
+#include "ocean_internal.h"
+
+namespace oceanfft
+{
+
+int64_t particle_items(int64_t capacity) { return (capacity + kParticleItem - 1) / kParticleItem; }
+
+// table (padded to 256 B) | offset int64[items][2] | ballots uint64[items][4][2] | partial uint32[items][2]
+size_t particle_scratch_bytes(int64_t capacity)
+{
+  return 256 + (size_t)particle_items(capacity) *
+                   (2 * sizeof(int64_t) + 2 * kParticleWaves * sizeof(unsigned long long) + 2 * sizeof(uint32_t));
+}
+
+void particle_scratch(void* scratch, int64_t capacity, ParticleCall& c)
+{
+  unsigned char* b = static_cast<unsigned char*>(scratch);
+  const size_t items = (size_t)particle_items(capacity);
+  c.table = reinterpret_cast<int64_t*>(b);
+  c.offset = reinterpret_cast<int64_t*>(b + 256);
+  c.ballots = reinterpret_cast<unsigned long long*>(c.offset + 2 * items);
+  c.partial = reinterpret_cast<uint32_t*>(c.ballots + 2 * kParticleWaves * items);
+}
+
+hipError_t launch_particles_step(const ParticleCall& c, const SurfaceParams& p, hipStream_t stream, int cus)
+{
+  if (c.capacity < 1 || c.capacity > ((int64_t)1 << 28) || !c.table || !c.cur || !c.next || c.landed_capacity < 0 ||
+      (c.landed_capacity > 0 && !c.landed_out) || (c.emit && !c.emit_counts) || p.count < 1 ||
+      p.count > kMaxSurfaceCascades)
+    return hipErrorInvalidValue;
+  // an item per workgroup on at most cus * 8 workgroups (launch_surface.hip's launch_points), sized from the
+  // capacity: the count stays on the device
+  long blocks = (long)particle_items(c.capacity);
+  if (blocks > (long)cus * 8)
+    blocks = (long)cus * 8;
+  if (blocks < 1)
+    blocks = 1;
+  hipError_t e = hipSuccess;
+  hipLaunchKernelGGL(k_particles_move, dim3((unsigned)blocks), dim3(kParticleThreads), 0, stream, c, p);
+  if ((e = hipGetLastError()) != hipSuccess)
+    return e;
+  hipLaunchKernelGGL(k_particles_scan, dim3(1), dim3(kParticleScanThreads), 0, stream, c);
+  if ((e = hipGetLastError()) != hipSuccess)
+    return e;
+  hipLaunchKernelGGL(k_particles_scatter, dim3((unsigned)blocks), dim3(kParticleThreads), 0, stream, c);
+  return hipGetLastError();
+}
+
+hipError_t launch_particles_reset(int64_t* table, int64_t alive, hipStream_t stream)
+{
+  hipLaunchKernelGGL(k_particles_reset, dim3(1), dim3(64), 0, stream, table, alive);
+  return hipGetLastError();
+}
+
+}  // namespace oceanfft

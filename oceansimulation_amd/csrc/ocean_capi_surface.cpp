@@ -1,7 +1,8 @@
 // ocean_capi_surface.cpp — the part of the C ABI (include/oceanfft.h) that consumes a generator's maps:
 // the map getters, ocean_surface_sample / _query / _sample_plane, the mip pyramids and the *_lod requests,
 // the rate maps and ocean_surface_velocity, the depth layers and ocean_water_kinematics, the bounds and ocean_surface_raycast, the persistent foam with
-// ocean_surface_sample_foam, the camera images (ocean_camera_render), the hull sets and the spray emitters.
+// ocean_surface_sample_foam, the camera images (ocean_camera_render), the hull sets, the spray emitters and the
+// spray particles.
 // The plans and generators themselves are in ocean_capi.cpp, their exchanges in ocean_capi_exchange.cpp;
 // ocean_capi_internal.h has what the three share.
 //
@@ -1263,6 +1264,188 @@ int ocean_spray_counts(ocean_spray* s, int64_t out[18])
   HIP_TRY(hipMemcpyAsync(out, s->scratch, 18 * sizeof(int64_t), hipMemcpyDeviceToHost, s->fft->stream),
           "ocean_spray_counts");
   HIP_TRY(hipStreamSynchronize(s->fft->stream), "ocean_spray_counts");
+  return OCEAN_OK;
+}
+
+// ---- spray particles: a persistent pool, stepped, landed on the water, compacted in order ----
+void ocean_default_particle_settings(ocean_particle_settings* s)
+{
+  if (s)
+    *s = ocean_particle_settings{9.8f, 0.5f, {0.0f, 0.0f, 0.0f}, 4.0f, 1.0f, 10.0f, 4, 1e-3f};
+}
+
+struct ocean_particles
+{
+  ocean_fft* fft = nullptr;
+  int64_t capacity = 0;
+  float* list[2] = {nullptr, nullptr};  // capacity x 8 floats each; list[current] is the pool's list
+  int current = 0;
+  void* scratch = nullptr;  // particle_scratch_bytes(capacity): the count table first
+};
+
+int ocean_particles_destroy(ocean_particles* p)
+{
+  if (!p)
+    return OCEAN_OK;
+  if (p->scratch)  // a pool that launched anything has all three buffers
+    (void)hipStreamSynchronize(p->fft->stream);
+  (void)hipFree(p->list[0]);
+  (void)hipFree(p->list[1]);
+  (void)hipFree(p->scratch);
+  delete p;
+  return OCEAN_OK;
+}
+
+int ocean_particles_create(ocean_particles** out, ocean_fft* fft, int64_t capacity)
+{
+  const std::string who = "ocean_particles_create";
+  if (!out || !fft)
+    return fail(OCEAN_ERR_INVALID, who + ": null argument");
+  if (capacity < 1 || capacity > ((int64_t)1 << 28))
+    return fail(OCEAN_ERR_INVALID, who + ": capacity outside 1..2^28");
+  auto* p = new ocean_particles();
+  p->fft = fft;
+  p->capacity = capacity;
+  const size_t bytes = (size_t)capacity * 8 * sizeof(float);
+  hipError_t e = alloc_if_null(p->list[0], bytes);
+  e = alloc_if_null(p->list[1], bytes, e);
+  e = alloc_if_null(p->scratch, particle_scratch_bytes(capacity), e);
+  if (e == hipSuccess)
+    e = launch_particles_reset(static_cast<int64_t*>(p->scratch), 0, fft->stream);
+  if (e != hipSuccess)
+  {
+    ocean_particles_destroy(p);
+    return alloc_fail(e, who);
+  }
+  *out = p;
+  return OCEAN_OK;
+}
+
+int ocean_particles_step(ocean_particles* pool, ocean_generator* const* gens, const int* cascades, int count,
+                         const ocean_particle_settings* settings, float dt, const float* emit_records,
+                         const int64_t* emit_counts_device, int64_t landed_capacity, float* landed_out)
+{
+  const std::string who = "ocean_particles_step";
+  // the rules that need neither the pool's fields nor a generator first
+  if (!pool)
+    return fail(OCEAN_ERR_INVALID, who + ": null pool");
+  if (!gens || !cascades || count < 1 || count > kMaxSurfaceCascades)
+    return fail(OCEAN_ERR_INVALID, who + ": need 1..16 (generator, cascade) pairs");
+  if (!settings)
+    return fail(OCEAN_ERR_INVALID, who + ": null settings");
+  if (!(dt >= 0.0f) || !std::isfinite(dt))
+    return fail(OCEAN_ERR_INVALID, who + ": dt must be finite and >= 0");
+  const ocean_particle_settings& s = *settings;
+  if (!std::isfinite(s.gravity))
+    return fail(OCEAN_ERR_INVALID, who + ": non-finite gravity");
+  if (!(s.drag >= 0.0f) || !std::isfinite(s.drag))
+    return fail(OCEAN_ERR_INVALID, who + ": drag must be finite and >= 0");
+  if (!std::isfinite(s.wind[0]) || !std::isfinite(s.wind[1]) || !std::isfinite(s.wind[2]))
+    return fail(OCEAN_ERR_INVALID, who + ": non-finite wind");
+  if (!(s.lifetime > 0.0f))
+    return fail(OCEAN_ERR_INVALID, who + ": lifetime must be > 0 (+inf: never expires)");
+  if (!std::isfinite(s.gain))
+    return fail(OCEAN_ERR_INVALID, who + ": non-finite gain");
+  if (!std::isfinite(s.lift))
+    return fail(OCEAN_ERR_INVALID, who + ": non-finite lift");
+  TRY(check_fixed_point(s.iterations, s.tolerance, who));
+  if (landed_capacity < 0 || (landed_capacity > 0 && !landed_out))
+    return fail(OCEAN_ERR_INVALID, who + ": negative landed_capacity, or null landed_out with landed_capacity > 0");
+  if (emit_records && !emit_counts_device)
+    return fail(OCEAN_ERR_INVALID, who + ": emit_records without emit_counts_device");
+  SurfaceParams p;
+  ocean_fft* fft;
+  TRY(surface_params(gens, cascades, count, p, fft, who.c_str()));
+  if (gens[0]->fft != pool->fft)
+    return fail(OCEAN_ERR_INVALID, who + ": the first generator is on another plan than the pool");
+  for (int i = 0; i < count; i++)
+  {
+    if (gens[i]->slab)
+      return fail(OCEAN_ERR_INVALID,
+                  who + ": generator " + std::to_string(i) + " is a slab generator: row slabs, not whole maps");
+    if (gens[i]->frame.cascades != gens[i]->cascades)
+      return fail(OCEAN_ERR_INVALID, who + ": generator " + std::to_string(i) +
+                                         " has no frame calculated yet (ocean_generator_calculate)");
+  }
+  ParticleCall c{};
+  particle_scratch(pool->scratch, pool->capacity, c);
+  c.cur = pool->list[pool->current];
+  c.next = pool->list[pool->current ^ 1];
+  c.emit = emit_records;
+  c.emit_counts = emit_records ? emit_counts_device : nullptr;
+  c.landed_out = landed_out;
+  c.landed_capacity = landed_capacity;
+  c.capacity = pool->capacity;
+  c.dt = dt;
+  c.gravity = s.gravity;
+  c.drag = s.drag;
+  c.wind[0] = s.wind[0];
+  c.wind[1] = s.wind[1];
+  c.wind[2] = s.wind[2];
+  c.lifetime = s.lifetime;
+  c.gain = s.gain;
+  c.lift = s.lift;
+  c.iterations = s.iterations;
+  c.tolerance = s.tolerance;
+  HIP_TRY(launch_particles_step(c, p, fft->stream, fft->cus), who.c_str());
+  pool->current ^= 1;
+  return OCEAN_OK;
+}
+
+int ocean_particles_load(ocean_particles* pool, const float* device_records, int64_t count)
+{
+  const std::string who = "ocean_particles_load";
+  if (!pool)
+    return fail(OCEAN_ERR_INVALID, who + ": null pool");
+  if (count < 0 || (count > 0 && !device_records))
+    return fail(OCEAN_ERR_INVALID, who + ": negative count, or null records with count > 0");
+  if (count > pool->capacity)
+    return fail(OCEAN_ERR_INVALID, who + ": count above the pool's capacity");
+  if (count > 0)
+    HIP_TRY(hipMemcpyAsync(pool->list[pool->current], device_records, (size_t)count * 8 * sizeof(float),
+                           hipMemcpyDeviceToDevice, pool->fft->stream),
+            who.c_str());
+  HIP_TRY(launch_particles_reset(static_cast<int64_t*>(pool->scratch), count, pool->fft->stream), who.c_str());
+  return OCEAN_OK;
+}
+
+int ocean_particles_clear(ocean_particles* pool)
+{
+  if (!pool)
+    return fail(OCEAN_ERR_INVALID, "ocean_particles_clear: null pool");
+  HIP_TRY(launch_particles_reset(static_cast<int64_t*>(pool->scratch), 0, pool->fft->stream), "ocean_particles_clear");
+  return OCEAN_OK;
+}
+
+const float* ocean_particles_records(ocean_particles* pool)
+{
+  if (!pool)
+  {
+    fail(OCEAN_ERR_INVALID, "ocean_particles_records: null pool");
+    return nullptr;
+  }
+  return pool->list[pool->current];
+}
+
+const int64_t* ocean_particles_counts_device(ocean_particles* pool)
+{
+  if (!pool)
+  {
+    fail(OCEAN_ERR_INVALID, "ocean_particles_counts_device: null pool");
+    return nullptr;
+  }
+  return static_cast<const int64_t*>(pool->scratch);
+}
+
+int ocean_particles_counts(ocean_particles* pool, int64_t out[8])
+{
+  if (!pool)
+    return fail(OCEAN_ERR_INVALID, "ocean_particles_counts: null pool");
+  if (!out)
+    return fail(OCEAN_ERR_INVALID, "ocean_particles_counts: null output");
+  HIP_TRY(hipMemcpyAsync(out, pool->scratch, 8 * sizeof(int64_t), hipMemcpyDeviceToHost, pool->fft->stream),
+          "ocean_particles_counts");
+  HIP_TRY(hipStreamSynchronize(pool->fft->stream), "ocean_particles_counts");
   return OCEAN_OK;
 }
 

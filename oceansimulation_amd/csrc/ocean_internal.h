@@ -470,6 +470,36 @@ void spray_scratch(void* scratch, int n, SprayCall& s);
 // request; r is read with velocity only).
 hipError_t launch_spray_emit(const SprayCall& s, const SurfaceParams& p, const SurfaceRates& r, const SprayTiles& tiles,
                              bool velocity, hipStream_t stream, int cus);
+// Spray particles (ocean_particles_step, include/oceanfft.h, device/k_particles.h): one step of a pool. The
+// scratch behind an ocean_particles: table int64[8], then per item of kParticleItem particles the exclusive
+// prefixes (survivors, landed), the counts (survivors, landed) and the waves' ballots (survivors, landed).
+constexpr int kParticleItem = 256;  // particles per item: one per thread
+constexpr int kParticleCounts = 8;  // alive, alive before, survivors, landed, landed written, expired, appended, dropped
+struct ParticleCall
+{
+  int64_t* table;
+  int64_t* offset;              // [items][2]
+  uint32_t* partial;            // [items][2]
+  unsigned long long* ballots;  // [items][kParticleItem / 64][2]
+  float* cur;                   // [capacity][8]: the list, moved in place by stage 1
+  float* next;                  // [capacity][8]: the survivors, then the appended
+  const float* emit;            // an ocean_spray_emit call's records, or null
+  const int64_t* emit_counts;   // that call's count table (read with emit only)
+  float* landed_out;            // [landed_capacity][8] or null
+  int64_t landed_capacity;
+  int64_t capacity;
+  float dt, gravity, drag, wind[3], lifetime, gain, lift;
+  int iterations;
+  float tolerance;
+};
+int64_t particle_items(int64_t capacity);
+size_t particle_scratch_bytes(int64_t capacity);
+// The pointers of a scratch buffer of particle_scratch_bytes(capacity) bytes into c
+void particle_scratch(void* scratch, int64_t capacity, ParticleCall& c);
+// Three launches: move and classify, scan with the count table, scatter with the append
+hipError_t launch_particles_step(const ParticleCall& c, const SurfaceParams& p, hipStream_t stream, int cus);
+// One launch: the table of a list of `alive` records that no step has made (all other counts 0)
+hipError_t launch_particles_reset(int64_t* table, int64_t alive, hipStream_t stream);
 void launch_surface_atlas(const SurfaceParams& p, hipStream_t stream, int cus);
 size_t surface_atlas_texels(const SurfaceParams& p);
 bool surface_use_atlas(const SurfaceParams& p, int64_t points);

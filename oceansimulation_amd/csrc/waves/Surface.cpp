@@ -387,4 +387,89 @@ const int64_t* SprayEmitter::GetCountsDevice() const
   return table;
 }
 
+SprayParticles::SprayParticles(Vision::RenderDevice* device, FFTCalculator* fft, int64_t capacity) : renderDevice(device)
+{
+  if (ocean_particles_create(&particles, fft ? fft->GetPlan() : nullptr, capacity) != OCEAN_OK)
+    throw std::runtime_error(std::string("SprayParticles: ") + ocean_last_error());
+}
+
+SprayParticles::~SprayParticles()
+{
+  ocean_particles_destroy(particles);
+  if (landed)
+    renderDevice->DestroyTexture2D(landed);
+}
+
+Vision::ID SprayParticles::Step(const std::vector<Generator*>& generators, const ocean_particle_settings& settings,
+                                float dt, const SprayEmitter* emitter, Vision::ID emitRecords, int64_t capacity)
+{
+  if (capacity < 0)
+    throw std::runtime_error("SprayParticles::Step: negative landed capacity");
+  if (capacity != landedCapacity)
+  {
+    if (landed)
+      renderDevice->DestroyTexture2D(landed);
+    landed = 0;
+    if (capacity > 0)
+    {
+      Vision::Texture2DDesc desc;
+      desc.Width = 2 * (std::size_t)capacity;
+      desc.Height = 1;
+      desc.PixelType = Vision::PixelType::RGBA32Float;
+      landed = renderDevice->CreateTexture2D(desc);
+    }
+    landedCapacity = capacity;
+  }
+  std::vector<ocean_generator*> gens;
+  std::vector<int> cascades;
+  for (auto* g : generators)
+  {
+    gens.push_back(g->GetHandle());
+    cascades.push_back(0);
+  }
+  const bool append = emitter && emitRecords;
+  const int rc = ocean_particles_step(
+      particles, gens.data(), cascades.data(), (int)gens.size(), &settings, dt,
+      append ? static_cast<const float*>(renderDevice->GetTexturePointer(emitRecords)) : nullptr,
+      append ? emitter->GetCountsDevice() : nullptr, capacity,
+      landed ? static_cast<float*>(renderDevice->GetTexturePointer(landed)) : nullptr);
+  if (rc != OCEAN_OK)
+    throw std::runtime_error(std::string("SprayParticles::Step: ") + ocean_last_error());
+  return landed;
+}
+
+void SprayParticles::Load(const float* recordsDevice, int64_t count)
+{
+  if (ocean_particles_load(particles, recordsDevice, count) != OCEAN_OK)
+    throw std::runtime_error(std::string("SprayParticles::Load: ") + ocean_last_error());
+}
+
+void SprayParticles::Clear()
+{
+  if (ocean_particles_clear(particles) != OCEAN_OK)
+    throw std::runtime_error(std::string("SprayParticles::Clear: ") + ocean_last_error());
+}
+
+const float* SprayParticles::GetRecords() const
+{
+  const float* records = ocean_particles_records(particles);
+  if (!records)
+    throw std::runtime_error(std::string("SprayParticles::GetRecords: ") + ocean_last_error());
+  return records;
+}
+
+void SprayParticles::GetCounts(int64_t out[8]) const
+{
+  if (ocean_particles_counts(particles, out) != OCEAN_OK)
+    throw std::runtime_error(std::string("SprayParticles::GetCounts: ") + ocean_last_error());
+}
+
+const int64_t* SprayParticles::GetCountsDevice() const
+{
+  const int64_t* table = ocean_particles_counts_device(particles);
+  if (!table)
+    throw std::runtime_error(std::string("SprayParticles::GetCountsDevice: ") + ocean_last_error());
+  return table;
+}
+
 }  // namespace Waves

@@ -405,6 +405,94 @@ class SprayEmitter:
             pass
 
 
+PARTICLE_COUNTS = 8  # alive, alive before, survivors, landed found, landed written, expired, appended, dropped
+PARTICLE_ITEM = 256  # particles per work item of the step's kernels (kParticleItem)
+
+
+class SprayParticles:
+    """A persistent pool of spray particles (ocean_particles, include/oceanfft.h): 8-float records
+    (x, y, z, age, velocity x, y, z in m/s, id as the emitter's uint32 bits). One step moves them under gravity
+    and drag toward a wind, lands them on the water of a sampler's pairs, compacts survivors and impacts in
+    order and appends a SprayEmitter call's records."""
+
+    def __init__(self, fft, capacity: int):
+        self.fft = fft
+        self.capacity = int(capacity)
+        h = ctypes.c_void_p()
+        check(lib().ocean_particles_create(ctypes.byref(h), fft.handle, ctypes.c_int64(self.capacity)),
+              "ocean_particles_create")
+        self._h = h
+
+    @property
+    def handle(self):
+        return self._h
+
+    def step(self, sampler: SurfaceSampler, settings, dt: float, emitter: "SprayEmitter" = None,
+             emit_records: int = None, landed: int = None, landed_capacity: int = 0) -> None:
+        """Enqueue one step on the plan's stream. settings: an OceanParticleSettings; emitter with emit_records
+        (the device pointer its last emit wrote): the records to append, counted by the emitter's device table;
+        landed: device rows (landed_capacity, 8) for the impacts, or None to count them only."""
+        table = emitter.counts_device() if (emitter is not None and emit_records) else 0
+        check(lib().ocean_particles_step(self._h, sampler._gens, sampler._cas, len(sampler.pairs),
+                                         ctypes.byref(settings), ctypes.c_float(dt),
+                                         ctypes.c_void_p(emit_records or 0), ctypes.c_void_p(table),
+                                         ctypes.c_int64(landed_capacity), ctypes.c_void_p(landed or 0)),
+              "ocean_particles_step")
+
+    def load(self, records_ptr: int, count: int) -> None:
+        """Replace the list with `count` device records (count, 8)."""
+        check(lib().ocean_particles_load(self._h, ctypes.c_void_p(records_ptr or 0), ctypes.c_int64(count)),
+              "ocean_particles_load")
+
+    def load_host(self, records: np.ndarray) -> None:
+        records = np.ascontiguousarray(records).reshape(-1, FLOATS_PER_VERTEX)
+        assert records.dtype.itemsize == 4
+        src = DeviceBuffer.from_array(records) if records.shape[0] else None
+        self.load(src.ptr if src else 0, records.shape[0])
+        self.fft.synchronize()  # src is freed on return
+
+    def clear(self) -> None:
+        check(lib().ocean_particles_clear(self._h), "ocean_particles_clear")
+
+    @property
+    def records_ptr(self) -> int:
+        """The current list in device memory: valid until the next step, load or close."""
+        ptr = lib().ocean_particles_records(self._h)
+        if not ptr:
+            raise OceanError(OCEAN_ERR_INVALID, "ocean_particles_records")
+        return int(ptr)
+
+    def records_host(self, dtype=np.float32) -> np.ndarray:
+        """The live particles (alive, 8) on the host; synchronises the plan's stream."""
+        alive = int(self.counts()[0])
+        if not alive:
+            return np.zeros((0, FLOATS_PER_VERTEX), dtype)
+        return hip.to_host(self.records_ptr, (alive, FLOATS_PER_VERTEX), dtype)
+
+    def counts(self) -> np.ndarray:
+        """The int64[8] counts on the host; synchronises the plan's stream."""
+        out = (ctypes.c_int64 * PARTICLE_COUNTS)()
+        check(lib().ocean_particles_counts(self._h, out), "ocean_particles_counts")
+        return np.array(out[:], np.int64)
+
+    def counts_device(self) -> int:
+        ptr = lib().ocean_particles_counts_device(self._h)
+        if not ptr:
+            raise OceanError(OCEAN_ERR_INVALID, "ocean_particles_counts_device")
+        return int(ptr)
+
+    def close(self) -> None:
+        if self._h:
+            lib().ocean_particles_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def host_cascades(pairs):
     """[(height, disp, jac, planeSize, displacement)] host copies, for the CPU oracle."""
     out = []
@@ -415,5 +503,5 @@ def host_cascades(pairs):
     return out
 
 
-__all__ = ["SurfaceSampler", "HullSet", "SprayEmitter", "host_cascades", "FLOATS_PER_VERTEX", "hip", "camera_pose",
+__all__ = ["SurfaceSampler", "HullSet", "SprayEmitter", "SprayParticles", "PARTICLE_ITEM", "host_cascades", "FLOATS_PER_VERTEX", "hip", "camera_pose",
            "default_camera", "default_shading", "default_march", "camera_rays_host"]

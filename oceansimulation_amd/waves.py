@@ -11,7 +11,7 @@ import ctypes
 import numpy as np
 
 from . import capi, hip
-from .capi import OceanFoamSettings, OceanSettings, OceanSpraySettings, check, lib
+from .capi import OceanFoamSettings, OceanParticleSettings, OceanSettings, OceanSpraySettings, check, lib
 
 
 def default_settings(**overrides) -> OceanSettings:
@@ -58,6 +58,26 @@ def apply_spray_settings(s: OceanSpraySettings, **overrides) -> OceanSpraySettin
         if k not in ("threshold", "rate", "seed"):
             raise AttributeError(f"ocean_spray_settings has no field {k!r}")
         setattr(s, k, v)
+    return s
+
+
+def default_particle_settings(**overrides) -> OceanParticleSettings:
+    """ocean_particle_settings defaults (gravity 9.8, drag 0.5, no wind, lifetime 4, gain 1, lift 10, 4
+    iterations, tolerance 1e-3) with keyword overrides."""
+    s = OceanParticleSettings()
+    lib().ocean_default_particle_settings(ctypes.byref(s))
+    return apply_particle_settings(s, **overrides)
+
+
+def apply_particle_settings(s: OceanParticleSettings, **overrides) -> OceanParticleSettings:
+    names = [f[0] for f in OceanParticleSettings._fields_]
+    for k, v in overrides.items():
+        if k not in names:
+            raise AttributeError(f"ocean_particle_settings has no field {k!r}")
+        if k == "wind":
+            s.wind[0], s.wind[1], s.wind[2] = float(v[0]), float(v[1]), float(v[2])
+        else:
+            setattr(s, k, v)
     return s
 
 

@@ -1,0 +1,670 @@
+"""Spray particles: ocean_particles_step and its counts against the contract restated in numpy float32
+(tests/particles_ref.py, on surface_query_ref for the water height under a particle).
+
+Scene: test_spray.py's, WaveApp's three cascades (planes 5 / 17 / 101 m), default settings, eight frames of
+CalculateOcean(0.25, first frame only: update), rates calculated. The CPU tests pin the restatement on the oracle's
+maps (N = 64); the GPU tests compare the kernels with the restatement evaluated on the GPU's own maps, bit for bit:
+the contract fixes every rounding and the order of the lists, so there is no tolerance. Every output buffer is
+filled with 0xFF bytes before a call.
+
+Populations (test_reference_populations prints them): the emitters' d = threshold - J is a few hundredths, so with
+the default lift of 10 m/s per unit of d a particle lands in its first step. lift = 100, lifetime = 0.6 s and
+dt = 0.25 s keep about two thirds aloft per step and expire the ones that reach their third; a pool of 4500 at
+N = 64 (about 2400 emitters per step) fills in the third step and drops from then on. One parameter set covers
+every arm.
+"""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import particles_ref as PR
+import rates_ref
+import spray_ref as SR
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PLANES = (5.0, 17.0, 101.0)
+DT = 0.25
+FRAMES = 8
+SEED, STEP = 12345, 7
+FLY = dict(lift=100.0, lifetime=0.6)  # the module docstring's populations
+SPRAY = [(1.0, 64.0, SEED)] * len(PLANES)  # the issue's emission: threshold 1.0, rate 64
+NEW_CALLS = ("ocean_default_particle_settings", "ocean_particles_create", "ocean_particles_destroy",
+             "ocean_particles_step", "ocean_particles_load", "ocean_particles_clear", "ocean_particles_records",
+             "ocean_particles_counts", "ocean_particles_counts_device")
+SENTINEL = 0xFFFFFFFF
+
+
+def _struct(s):
+    """An OceanParticleSettings from particles_ref's dict."""
+    import oceansimulation_amd as ocean
+
+    return ocean.default_particle_settings(**s)
+
+
+# ---- without a GPU ----------------------------------------------------------------------------
+def test_exports_and_signatures():
+    from oceansimulation_amd import capi
+    import oceansimulation_amd as ocean
+    from oceansimulation_amd import surface
+
+    L = capi.lib()
+    for name in NEW_CALLS:
+        assert hasattr(L, name) and name in capi.SIGNATURES, name
+    for name in ("step", "load", "clear", "records_ptr", "records_host", "counts", "counts_device", "close"):
+        assert hasattr(ocean.SprayParticles, name), name
+    assert ocean.SprayParticles is surface.SprayParticles and "SprayParticles" in surface.__all__
+    for name in ("SprayParticles", "OceanParticleSettings", "default_particle_settings", "apply_particle_settings"):
+        assert hasattr(ocean, name) and name in ocean.__all__, name
+    assert surface.PARTICLE_ITEM >= 64 and surface.PARTICLE_ITEM % 64 == 0 and surface.PARTICLE_COUNTS == PR.COUNTS
+    kernels = open(os.path.join(ROOT, "oceansimulation_amd", "csrc", "ocean_internal.h")).read()
+    assert f"constexpr int kParticleItem = {surface.PARTICLE_ITEM};" in kernels
+
+
+def test_default_particle_settings_and_size():
+    from oceansimulation_amd import capi
+    import oceansimulation_amd as ocean
+
+    assert ctypes.sizeof(capi.OceanParticleSettings) == 40
+    s = capi.OceanParticleSettings(-1.0, -1.0, (7.0, 7.0, 7.0), -1.0, -1.0, -1.0, 99, -1.0)
+    capi.lib().ocean_default_particle_settings(ctypes.byref(s))
+    got = (s.gravity, s.drag, tuple(s.wind), s.lifetime, s.gain, s.lift, s.iterations, s.tolerance)
+    assert got == (np.float32(9.8), 0.5, (0.0, 0.0, 0.0), 4.0, 1.0, 10.0, 4, np.float32(1e-3))
+    d = PR.DEFAULTS
+    assert got == (np.float32(d["gravity"]), d["drag"], d["wind"], d["lifetime"], d["gain"], d["lift"], d["iterations"],
+                   np.float32(d["tolerance"]))
+    capi.lib().ocean_default_particle_settings(None)  # a null output is ignored
+    s = ocean.default_particle_settings(lift=100.0, wind=(1.0, 0.0, -2.0), iterations=8)
+    assert (s.lift, tuple(s.wind), s.iterations, s.drag) == (100.0, (1.0, 0.0, -2.0), 8, 0.5)
+    with pytest.raises(AttributeError):
+        ocean.apply_particle_settings(s, threshold=1.0)
+    header = open(os.path.join(ROOT, "include", "oceanfft.h")).read()
+    body = header[header.index("typedef struct ocean_particle_settings"):header.index("} ocean_particle_settings;")]
+    names = [f[0] for f in capi.OceanParticleSettings._fields_]
+    assert sorted(names, key=lambda f: body.index(f" {f}")) == names
+    for decl in ("float gravity;", "float drag;", "float wind[3];", "float lifetime;", "float gain;", "float lift;",
+                 "int32_t iterations;", "float tolerance;"):
+        assert decl in body, decl
+    assert "(9.8, 0.5, no wind, 4, 1, 10, 4, 1e-3) are starting points" in header
+
+
+def test_rejected_arguments_name_the_call():
+    """Everything that can be refused without a device: OCEAN_ERR_INVALID (or a null pointer) with the entry
+    point's name in ocean_last_error. A pool owns its lists from creation on, so none exists without a GPU: the
+    step's rules are checked through a pool pointer that is never dereferenced, since every rule listed here is
+    checked before the pool's fields or a generator are read (the last case, a null generator, is where a call
+    with good arguments stops)."""
+    from oceansimulation_amd import capi
+
+    L = capi.lib()
+    inv = capi.OCEAN_ERR_INVALID
+    one = ctypes.c_void_p(16)  # a non-null pointer that is never dereferenced
+    h = ctypes.c_void_p()
+    for args in ((None, one, 16), (ctypes.byref(h), None, 16), (ctypes.byref(h), one, 0), (ctypes.byref(h), one, -1),
+                 (ctypes.byref(h), one, (1 << 28) + 1)):
+        assert L.ocean_particles_create(args[0], args[1], ctypes.c_int64(args[2])) == inv
+        assert b"ocean_particles_create" in L.ocean_last_error() and not h
+    counts = (ctypes.c_int64 * 8)()
+    assert L.ocean_particles_counts(None, counts) == inv and b"ocean_particles_counts: null pool" in L.ocean_last_error()
+    assert L.ocean_particles_counts(one, None) == inv and b"ocean_particles_counts: null output" in L.ocean_last_error()
+    assert not L.ocean_particles_counts_device(None) and b"ocean_particles_counts_device" in L.ocean_last_error()
+    assert not L.ocean_particles_records(None) and b"ocean_particles_records" in L.ocean_last_error()
+    assert L.ocean_particles_clear(None) == inv and b"ocean_particles_clear" in L.ocean_last_error()
+    assert L.ocean_particles_load(None, one, ctypes.c_int64(1)) == inv and b"ocean_particles_load: null pool" in L.ocean_last_error()
+    assert L.ocean_particles_load(one, one, ctypes.c_int64(-1)) == inv and b"ocean_particles_load" in L.ocean_last_error()
+    assert L.ocean_particles_load(one, None, ctypes.c_int64(1)) == inv and b"null records" in L.ocean_last_error()
+    assert L.ocean_particles_destroy(None) == capi.OCEAN_OK
+
+    g1, c1 = (ctypes.c_void_p * 1)(None), (ctypes.c_int * 1)(0)
+    g17, c17 = (ctypes.c_void_p * 17)(*([16] * 17)), (ctypes.c_int * 17)()
+    nan, inf = float("nan"), float("inf")
+
+    def step(pool=one, gens=g1, cas=c1, count=1, settings=True, dt=DT, emit=None, emit_counts=None, landed_capacity=4,
+             landed=one, **fields):
+        s = capi.OceanParticleSettings()
+        L.ocean_default_particle_settings(ctypes.byref(s))
+        for k, v in fields.items():
+            if k == "wind":
+                s.wind[:] = v
+            else:
+                setattr(s, k, v)
+        return L.ocean_particles_step(pool, gens, cas, count, ctypes.byref(s) if settings else None, ctypes.c_float(dt),
+                                      emit, emit_counts, ctypes.c_int64(landed_capacity), landed)
+
+    cases = [(dict(pool=None), b"null pool"), (dict(gens=None), b"pairs"), (dict(cas=None), b"pairs"),
+             (dict(count=0), b"pairs"), (dict(gens=g17, cas=c17, count=17), b"pairs"),
+             (dict(settings=False), b"null settings"),
+             (dict(dt=-0.1), b"dt"), (dict(dt=nan), b"dt"), (dict(dt=inf), b"dt"),
+             (dict(gravity=nan), b"gravity"), (dict(gravity=inf), b"gravity"),
+             (dict(wind=(0.0, nan, 0.0)), b"wind"), (dict(wind=(0.0, 0.0, -inf)), b"wind"), (dict(wind=(inf, 0.0, 0.0)), b"wind"),
+             (dict(gain=nan), b"gain"), (dict(gain=-inf), b"gain"), (dict(lift=nan), b"lift"), (dict(lift=inf), b"lift"),
+             (dict(drag=-0.5), b"drag"), (dict(drag=nan), b"drag"), (dict(drag=inf), b"drag"),
+             (dict(lifetime=0.0), b"lifetime"), (dict(lifetime=-1.0), b"lifetime"), (dict(lifetime=nan), b"lifetime"),
+             (dict(iterations=-1), b"iterations"), (dict(iterations=65), b"iterations"),
+             (dict(tolerance=-1e-3), b"tolerance"), (dict(tolerance=nan), b"tolerance"), (dict(tolerance=inf), b"tolerance"),
+             (dict(landed_capacity=-1), b"landed_capacity"), (dict(landed=None), b"landed_out"),
+             (dict(emit=one, emit_counts=None), b"emit_counts_device"),
+             # accepted values, refused only for the generator: +inf lifetime, a counting-only call, an emission
+             (dict(lifetime=inf), b"null generator"), (dict(landed_capacity=0, landed=None), b"null generator"),
+             (dict(emit=one, emit_counts=one), b"null generator"), (dict(iterations=0, tolerance=0.0, dt=0.0), b"null generator"),
+             (dict(), b"null generator")]
+    for kwargs, word in cases:
+        assert step(**kwargs) == inv, (kwargs, word)
+        assert b"ocean_particles_step:" in L.ocean_last_error() and word in L.ocean_last_error(), (kwargs, L.ocean_last_error())
+
+
+def test_cpp_headers_compile_standalone(tmp_path):
+    """A consumer of the pool compiles against the drop-in headers alone."""
+    src = tmp_path / "consumer.cpp"
+    src.write_text(
+        '#include "waves/Surface.h"\n'
+        "#include <vector>\n"
+        "const float* frame(Waves::SprayEmitter& e, Waves::SprayParticles& p, std::vector<Waves::Generator*>& gens,\n"
+        "                   float dt, uint32_t step, int64_t* counts, Vision::ID* impacts) {\n"
+        "  std::vector<ocean_spray_settings> s(gens.size());\n"
+        "  for (auto& v : s) { ocean_default_spray_settings(&v); v.rate = 64.0f; }\n"
+        "  ocean_particle_settings ps; ocean_default_particle_settings(&ps); ps.wind[0] = 3.0f;\n"
+        "  static_assert(sizeof(ocean_particle_settings) == 40, \"layout\");\n"
+        "  for (auto* g : gens) { g->CalculateOcean(dt); g->CalculateRates(); }\n"
+        "  Vision::ID records = e.Emit(gens, s.data(), nullptr, dt, step, true, 65536);\n"
+        "  *impacts = p.Step(gens, ps, dt, &e, records, 4096);\n"
+        "  p.GetCounts(counts);\n"
+        "  const int64_t* table = p.GetCountsDevice(); (void)table;\n"
+        "  ocean_particles* h = p.GetHandle(); (void)h;\n"
+        "  if (counts[0] < 0) { p.Clear(); p.Load(p.GetRecords(), 0); }\n"
+        "  return p.GetRecords();\n"
+        "}\n")
+    r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", f"-I{ROOT}/include", "-I/opt/rocm/include",
+                        "-D__HIP_PLATFORM_AMD__", str(src)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    copy = tmp_path / "copy.cpp"
+    copy.write_text('#include "waves/Surface.h"\n'
+                    "Waves::SprayParticles* dup(const Waves::SprayParticles& p) { return new Waves::SprayParticles(p); }\n")
+    r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", f"-I{ROOT}/include", "-I/opt/rocm/include",
+                        "-D__HIP_PLATFORM_AMD__", str(copy)], capture_output=True, text=True)
+    assert r.returncode != 0 and "deleted" in r.stderr  # non-copyable
+    so = os.path.join(ROOT, "oceansimulation_amd", "libwaves.so")
+    syms = subprocess.run(["nm", "-DC", "--defined-only", so], capture_output=True, text=True).stdout
+    for sig in ("Waves::SprayParticles::SprayParticles(Vision::RenderDevice*, Waves::FFTCalculator*, long)",
+                "Waves::SprayParticles::~SprayParticles()", "Waves::SprayParticles::Step(",
+                "Waves::SprayParticles::Load(float const*, long)", "Waves::SprayParticles::Clear()",
+                "Waves::SprayParticles::GetRecords() const", "Waves::SprayParticles::GetCounts(long*) const",
+                "Waves::SprayParticles::GetCountsDevice() const"):
+        assert sig in syms, sig
+
+
+def test_reference_populations(oracle):
+    """The restatement on the oracle's maps of the eighth frame, N = 64: six steps with an emission each (threshold
+    1.0, rate 64, the emitter's step number advancing), lift 100, lifetime 0.6, dt 0.25, a pool of 4500."""
+    n, capacity = 64, 4500
+    gens = [oracle.OracleGenerator(n, oracle.default_settings(planeSize=L)) for L in PLANES]
+    for k in range(FRAMES):
+        for g in gens:
+            g.calculate_ocean(DT, k == 0)
+    cascades = [(g.height, g.disp, g.jac, g.settings.planeSize, g.settings.displacement) for g in gens]
+    rates = [rates_ref.rate_maps(g.settings, n, g.h0) for g in gens]
+    jacs = [np.array(g.jac, np.float32) for g in gens]
+    s = PR.settings(**FLY)
+    lst = np.zeros((0, 8), np.uint32)
+    full = []
+    for k in range(6):
+        ids, ds, base, _ = SR.emit(jacs, PLANES, SPRAY, DT, STEP + k)
+        emitted = SR.records(ids, ds, rates_ref.surface_velocity(cascades, rates, base))
+        nxt, hit, c = PR.step(oracle, cascades, lst, s, DT, emit=emitted, capacity=capacity)
+        print(f"step {k}: alive {c[0]} before {c[1]} survivors {c[2]} landed {c[3]} expired {c[5]} appended {c[6]} "
+              f"dropped {c[7]}")
+        assert c[1] == lst.shape[0] == c[2] + c[3] + c[5] and c[0] == c[2] + c[6] == nxt.shape[0] <= capacity
+        assert c[6] + c[7] == emitted.shape[0] and c[4] == c[3] == hit.shape[0]
+        # Survivors and landed are disjoint ordered subsequences of the previous list, the rest expired. A texel
+        # emits in several steps, so a particle is named by its id and its age, which names the emission.
+        place = {key: at for at, key in enumerate(_keys(lst, DT))}
+        assert len(place) == lst.shape[0]
+        kept = np.array([place[key] for key in _keys(nxt[:c[2]])], np.int64)
+        fell = np.array([place[key] for key in _keys(hit)], np.int64)
+        assert np.all(np.diff(kept) > 0) and np.all(np.diff(fell) > 0) and not set(kept) & set(fell)
+        # the appended are the emitter's first records, launched
+        new = nxt[c[2]:].view(np.float32)
+        assert np.array_equal(nxt[c[2]:, 7], ids[:c[6]]) and np.all(new[:, 3] == 0)
+        assert np.array_equal(new[:, 5], np.float32(1.0) * emitted[:c[6], 5] + np.float32(100.0) * emitted[:c[6], 3])
+        full.append(all(int(v) > 0 for v in (c[2], c[3], c[5], c[6], c[7])))
+        lst = nxt
+    assert any(full), "no step has survivors, landed, expired, appended and dropped all non-zero"
+
+
+def _keys(rows, dt=None):
+    """(id, age) of every record as one integer; with dt the age after a step of dt."""
+    age = np.ascontiguousarray(rows.view(np.float32)[:, 3])
+    if dt is not None:
+        age = age + np.float32(dt)
+    return ((rows[:, 7].astype(np.uint64) << np.uint64(32)) | age.view(np.uint32)).tolist()
+
+
+def test_reference_fates_by_construction(oracle):
+    """Still water (zero maps): w = 0 everywhere, so the fates follow from heights and ages alone."""
+    flat = [(np.zeros((16, 16, 4), np.float32), np.zeros((16, 16, 4), np.float32), np.ones((16, 16), np.float32), 10.0, 1.0)]
+    rec = np.zeros((5, 8), np.float32)
+    rec[:, 1] = (5.0, -1.0, np.nan, 5.0, 0.0)   # above, below, NaN, above but old, exactly on the water
+    rec[:, 3] = (0.0, 0.0, 0.0, 0.9, 0.0)
+    rec.view(np.uint32)[:, 7] = (1, 2, 0x7FC00003, 4, 5)
+    s = PR.settings(gravity=0.0, drag=0.0, lifetime=1.0)
+    nxt, hit, c = PR.step(oracle, flat, rec, s, 0.1)
+    assert c.tolist() == [1, 5, 1, 3, 3, 1, 0, 0]
+    assert nxt[:, 7].tolist() == [1] and hit[:, 7].tolist() == [2, 0x7FC00003, 5]
+    assert np.all(hit.view(np.float32)[:, 1] == 0) and nxt.view(np.float32)[0, 3] == np.float32(0.1)
+    # 0.9f + 0.1f rounds to 1.0f: not < 1, expired; with lifetime +inf it survives
+    _, _, c = PR.step(oracle, flat, rec, PR.settings(gravity=0.0, drag=0.0, lifetime=np.inf), 0.1)
+    assert c.tolist() == [2, 5, 2, 3, 3, 0, 0, 0]
+    # gravity and drag, one step by hand
+    one = np.zeros((1, 8), np.float32)
+    one[0, :7] = (1.0, 10.0, 2.0, 0.0, 4.0, 0.0, -2.0)
+    nxt, _, _ = PR.step(oracle, flat, one, PR.settings(wind=(2.0, 0.0, 0.0)), 0.5)
+    f = np.float32
+    ux = f(4.0) + f(0.5) * (f(2.0) - f(4.0)) * f(0.5)
+    uy = f(0.0) + (f(0.5) * (f(0.0) - f(0.0)) - f(9.8)) * f(0.5)
+    assert nxt.view(np.float32)[0, :7].tolist() == [f(1.0) + ux * f(0.5), f(10.0) + uy * f(0.5), f(2.0) + f(-1.5) * f(0.5),
+                                                   f(0.5), ux, uy, f(-1.5)]
+
+
+# ---- on the GPU -------------------------------------------------------------------------------
+gpu = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def ocean():
+    import oceansimulation_amd as o
+    from oceansimulation_amd import capi
+
+    assert capi.lib().ocean_device_count() > 0, "no GPU visible to liboceanfft.so"
+    return o
+
+
+class Scene:
+    """One three-cascade generator after the eight frames, with rates, its sampler and an emitter."""
+
+    def __init__(self, ocean, n):
+        from oceansimulation_amd.surface import SprayEmitter, SurfaceSampler
+
+        self.ocean = ocean
+        self.n = n
+        self.fft = ocean.FFTCalculator(n)
+        self.gen = ocean.Generator(self.fft, len(PLANES))
+        for c, L in enumerate(PLANES):
+            ocean.apply_settings(self.gen.GetOceanSettings(c), planeSize=L)
+        for k in range(FRAMES):
+            self.gen.CalculateOcean(DT, k == 0)
+        self.gen.calculate_rates()
+        self.sampler = SurfaceSampler([(self.gen, c) for c in range(len(PLANES))])
+        self.emitter = SprayEmitter(self.fft)
+        self._host = None
+
+    def next_frame(self):
+        self.gen.CalculateOcean(DT, False)
+        self.gen.calculate_rates()
+        self._host = None
+
+    @property
+    def host(self):
+        """The maps of the current frame as the oracle takes them, copied once per frame."""
+        from oceansimulation_amd.surface import host_cascades
+
+        if self._host is None:
+            self._host = host_cascades(self.sampler.pairs)
+        return self._host
+
+    def pool(self, capacity):
+        from oceansimulation_amd.surface import SprayParticles
+
+        return SprayParticles(self.fft, capacity)
+
+    def emit(self, step, capacity, settings=SPRAY):
+        """One ocean_spray_emit into a 0xFF-filled buffer: (the device buffer, its written records on the host)."""
+        from oceansimulation_amd.hip import DeviceBuffer
+
+        out = DeviceBuffer.from_array(np.full(capacity * 32, 0xFF, np.uint8))
+        self.emitter.emit(self.sampler, [dict(threshold=t, rate=r, seed=sd) for t, r, sd in settings], DT, step, out.ptr,
+                          capacity)
+        written = int(self.emitter.counts()[0])
+        return out, out.to_host((capacity, 8), np.uint32)[:written].copy()
+
+    def step(self, pool, s, dt, emit=None, landed_capacity=0, pad=3):
+        """One ocean_particles_step, the impacts into a 0xFF-filled buffer of landed_capacity + pad records (a null
+        one for landed_capacity 0): (the new list, the whole impact buffer, counts), the lists as uint32 rows."""
+        from oceansimulation_amd import hip
+        from oceansimulation_amd.hip import DeviceBuffer
+
+        rows = landed_capacity + pad
+        out = DeviceBuffer.from_array(np.full(rows * 32, 0xFF, np.uint8))
+        pool.step(self.sampler, _struct(s), dt, emitter=self.emitter if emit is not None else None,
+                  emit_records=emit.ptr if emit is not None else None, landed=out.ptr if landed_capacity else None,
+                  landed_capacity=landed_capacity)
+        counts = pool.counts()
+        assert np.array_equal(hip.to_host(pool.counts_device(), (8,), np.int64), counts)
+        return pool.records_host(np.uint32), out.to_host((rows, 8), np.uint32), counts
+
+
+@pytest.fixture(scope="module")
+def scenes(ocean):
+    built = {}
+
+    def get(n):
+        if n not in built:
+            built[n] = Scene(ocean, n)
+        return built[n]
+
+    return get
+
+
+def _check(got, want, landed_capacity):
+    """Counts, the list, the impacts that fit, and the sentinel after them."""
+    (lst, hit, counts), (want_lst, want_hit, want_counts) = got, want
+    expect = want_counts.copy()
+    expect[4] = min(int(want_counts[3]), landed_capacity)
+    assert np.array_equal(counts, expect), (counts, expect)
+    assert counts[1] == counts[2] + counts[3] + counts[5] and counts[0] == counts[2] + counts[6]
+    assert np.array_equal(lst, want_lst)
+    written = int(expect[4])
+    assert np.array_equal(hit[:written], want_hit[:written])
+    assert np.all(hit[written:] == SENTINEL)
+
+
+def _state(oracle, host, count, seed, s, dt):
+    """`count` particles over the 101 m plane spread over the three fates by construction: heights within
+    [-1, 2) m of the water under their moved position (above it more often than below), ages over twice the
+    lifetime, ids of any bit pattern. Returns uint32 rows."""
+    import surface_query_ref as Q
+
+    rng = np.random.default_rng(seed)
+    rec = np.zeros((count, 8), np.float32)
+    rec[:, 0] = rng.uniform(0.0, 101.0, count)
+    rec[:, 2] = rng.uniform(0.0, 101.0, count)
+    rec[:, 4:7] = rng.uniform(-2.0, 2.0, (count, 3))
+    rec[:, 3] = rng.uniform(0.0, 2.0 * min(s["lifetime"], 8.0), count)
+    bits = rec.view(np.uint32)
+    bits[:, 7] = rng.integers(0, 1 << 32, count, dtype=np.uint64).astype(np.uint32)
+    # the height that the move takes to [-1, 2) m above the water under the moved position
+    drag, g, fdt = np.float32(s["drag"]), np.float32(s["gravity"]), np.float32(dt)
+    uy = rec[:, 5] + (drag * (np.float32(s["wind"][1]) - rec[:, 5]) - g) * fdt
+    ux = rec[:, 4] + (drag * (np.float32(s["wind"][0]) - rec[:, 4])) * fdt
+    uz = rec[:, 6] + (drag * (np.float32(s["wind"][2]) - rec[:, 6])) * fdt
+    q = np.stack([rec[:, 0] + ux * fdt, rec[:, 2] + uz * fdt], -1)
+    w = Q.surface_query(oracle, host, q, s["iterations"], s["tolerance"])[:, 1]
+    rec[:, 1] = w - uy * fdt + rng.uniform(-1.0, 2.0, count).astype(np.float32)
+    return bits.copy()
+
+
+@gpu
+@pytest.mark.parametrize("n", [64, 256])
+def test_sequence_equals_restatement(ocean, oracle, n):
+    """Six steps of frame -> rates -> ocean_spray_emit (threshold 1.0, rate 64) -> ocean_particles_step on a scene
+    of its own. After every step the list, the impacts, the sentinel after them and the 8 counts against the
+    restatement on the GPU's maps of that frame (the emitter's records are the GPU's: test_spray.py compares
+    those), and the impacts' slot 1 against ocean_surface_query at their (px', pz'). The pool is sized so that it
+    fills: 4500 at N = 64 (the module docstring), 16 times that at 256."""
+    sc = Scene(ocean, n)
+    capacity = 4500 * (n // 64) ** 2
+    emit_capacity = 3 * n * n
+    s = PR.settings(**FLY)
+    pool = sc.pool(capacity)
+    assert not pool.counts().any() and pool.records_host().shape == (0, 8)  # a fresh pool has counts
+    want_lst = np.zeros((0, 8), np.uint32)
+    full = []
+    for k in range(6):
+        if k:
+            sc.next_frame()
+        buf, emitted = sc.emit(STEP + k, emit_capacity)
+        landed_capacity = capacity  # room for all
+        got = sc.step(pool, s, DT, emit=buf, landed_capacity=landed_capacity)
+        want = PR.step(oracle, sc.host, want_lst, s, DT, emit=emitted, capacity=capacity)
+        c = want[2]
+        print(f"N = {n} step {k}: alive {c[0]} before {c[1]} survivors {c[2]} landed {c[3]} expired {c[5]} "
+              f"appended {c[6]} dropped {c[7]}")
+        _check(got, want, landed_capacity)
+        hit = got[1][:int(c[3])]
+        if hit.shape[0]:
+            q = sc.sampler.query_host(hit.view(np.float32)[:, [0, 2]], s["iterations"], s["tolerance"])
+            assert np.array_equal(q.view(np.uint32)[:, 1], hit[:, 1])
+        full.append(all(int(v) > 0 for v in (c[2], c[3], c[5], c[6], c[7])))
+        want_lst = want[0]
+    assert any(full)
+    pool.clear()
+    assert pool.counts().tolist() == [0] * 8
+    pool.close()
+
+
+@gpu
+@pytest.mark.parametrize("count", ["1", "63", "64", "65", "T-1", "T", "T+1", "3*T+17"])
+def test_pool_sizes_through_load(scenes, oracle, count):
+    """Lists that end inside the first wave, at its end, inside an item, at its end, one past it, and in a
+    fourth item; the pool's capacity is the list's length. No emission; impacts with room for all."""
+    from oceansimulation_amd.surface import PARTICLE_ITEM as T
+
+    count = eval(count, {"T": T})
+    sc = scenes(64)
+    s = PR.settings(lifetime=1.0)
+    state = _state(oracle, sc.host, count, 100 + count, s, DT)
+    want = PR.step(oracle, sc.host, state, s, DT)
+    print(f"{count} particles: survivors {want[2][2]} landed {want[2][3]} expired {want[2][5]}")
+    if count >= 63:
+        assert want[2][2] > 0 and want[2][3] > 0 and want[2][5] > 0
+    pool = sc.pool(count)
+    pool.load_host(state)
+    assert pool.counts().tolist() == [count] + [0] * 7 and np.array_equal(pool.records_host(np.uint32), state)
+    _check(sc.step(pool, s, DT, landed_capacity=count), want, count)
+    pool.close()
+
+
+@gpu
+def test_scan_past_its_first_chunk(ocean):
+    """More than 1024 items (the scan's chunk) on N = 16 maps with one iteration, against the same particles
+    stepped in two pools of at most one chunk each, concatenated: particles are independent and the order is
+    kept, so the lists and the summed counts are equal, with no restatement at this size."""
+    from oceansimulation_amd.surface import PARTICLE_ITEM as T
+
+    sc = Scene(ocean, 16)
+    count = 1024 * T + 3 * T + 17
+    rng = np.random.default_rng(5)
+    rec = np.zeros((count, 8), np.float32)
+    rec[:, 0] = rng.uniform(0.0, 101.0, count)
+    rec[:, 2] = rng.uniform(0.0, 101.0, count)
+    rec[:, 1] = rng.uniform(-0.5, 1.5, count)
+    rec[:, 3] = rng.uniform(0.0, 2.0, count)
+    rec[:, 4:7] = rng.uniform(-2.0, 2.0, (count, 3))
+    state = rec.view(np.uint32)
+    state[:, 7] = np.arange(count, dtype=np.uint32)
+    s = PR.settings(lifetime=1.0, iterations=1)
+    whole = sc.pool(count)
+    whole.load_host(state)
+    got = sc.step(whole, s, DT, landed_capacity=count, pad=0)
+    whole.close()
+    parts = []
+    for lo, hi in ((0, 1024 * T), (1024 * T, count)):
+        part = sc.pool(hi - lo)
+        part.load_host(state[lo:hi])
+        parts.append(sc.step(part, s, DT, landed_capacity=hi - lo, pad=0))
+        part.close()
+    counts = parts[0][2] + parts[1][2]
+    print("counts", got[2].tolist())
+    assert np.array_equal(got[2], counts) and min(counts[2], counts[3], counts[5]) > count // 20
+    assert np.array_equal(got[0], np.concatenate([parts[0][0], parts[1][0]]))
+    landed = [p[1][:int(p[2][3])] for p in parts]
+    assert np.array_equal(got[1][:int(counts[3])], np.concatenate(landed))
+    assert np.all(got[1][int(counts[3]):] == SENTINEL)
+
+
+@gpu
+def test_landed_capacity(scenes, oracle):
+    """0 with a null output, 1, a cut inside the second item, exactly `landed`, and landed + 100."""
+    from oceansimulation_amd.surface import PARTICLE_ITEM as T
+
+    sc = scenes(64)
+    count = 3 * T + 17
+    s = PR.settings(lifetime=1.0)
+    state = _state(oracle, sc.host, count, 7, s, DT)
+    want = PR.step(oracle, sc.host, state, s, DT)
+    landed = int(want[2][3])
+    first_item = PR.step(oracle, sc.host, state[:T], s, DT)[2][3]
+    assert 0 < first_item < landed
+    pool = sc.pool(count)
+    for capacity in (0, 1, int(first_item) + 5, landed, landed + 100):
+        pool.load_host(state)
+        _check(sc.step(pool, s, DT, landed_capacity=capacity), want, capacity)
+    pool.close()
+
+
+@gpu
+def test_pool_capacity_cuts_the_append(scenes, oracle):
+    """Room for 0, 1, a cut inside the emission, exactly the emission and more than it. The list is `survivors`
+    particles far above the water with up to 100 that die (below it, or old) between them, so that it fits the
+    pool; appended and dropped are exact and the list is the restatement's."""
+    sc = scenes(64)
+    buf, emitted = sc.emit(STEP, 500)
+    assert emitted.shape[0] == 500
+    s = PR.settings(lifetime=1.0)
+    survivors = 300
+    for room in (0, 1, 200, 500, 800):
+        dying = min(room, 100)
+        rec = np.zeros((survivors + dying, 8), np.float32)
+        rec[:, 0] = np.linspace(0.0, 101.0, rec.shape[0])
+        rec[:, 2] = 3.0
+        rec[:, 1] = 50.0
+        die = np.linspace(0, rec.shape[0] - 1, dying).astype(np.int64) if dying else np.zeros(0, np.int64)
+        rec[die[0::2], 1] = -50.0
+        rec[die[1::2], 3] = 10.0
+        rec.view(np.uint32)[:, 7] = np.arange(rec.shape[0], dtype=np.uint32) + 0x10000
+        pool = sc.pool(survivors + room)
+        pool.load_host(rec)
+        want = PR.step(oracle, sc.host, rec, s, DT, emit=emitted, capacity=survivors + room)
+        assert want[2][2] == survivors and want[2][6] == min(room, 500) and want[2][7] == 500 - min(room, 500), want[2]
+        _check(sc.step(pool, s, DT, emit=buf, landed_capacity=128), want, 128)
+        pool.close()
+
+
+@gpu
+def test_edge_inputs(scenes, oracle):
+    from oceansimulation_amd.surface import PARTICLE_ITEM as T
+
+    sc = scenes(64)
+    count = T + 40
+    s = PR.settings(lifetime=1.0)
+    state = _state(oracle, sc.host, count, 11, s, DT)
+    pool = sc.pool(count + 64)
+    # a null emission
+    pool.load_host(state)
+    got = sc.step(pool, s, DT, landed_capacity=count)
+    _check(got, PR.step(oracle, sc.host, state, s, DT), count)
+    assert got[2][6] == 0 and got[2][7] == 0
+    # an emission whose `written` is 0: no pair emits
+    buf, emitted = sc.emit(STEP, 64, settings=[(1.0, 0.0, SEED)] * 3)
+    assert emitted.shape[0] == 0
+    pool.load_host(state)
+    got = sc.step(pool, s, DT, emit=buf, landed_capacity=count)
+    _check(got, PR.step(oracle, sc.host, state, s, DT, emit=emitted, capacity=count + 64), count)
+    assert got[2][6] == 0 and got[2][7] == 0
+    # dt = 0 still classifies and compacts
+    pool.load_host(state)
+    want = PR.step(oracle, sc.host, state, s, 0.0)
+    assert want[2][2] > 0 and want[2][3] > 0 and want[2][5] > 0
+    _check(sc.step(pool, s, 0.0, landed_capacity=count), want, count)
+    # a NaN height lands, on the water under it
+    nan = state.copy()
+    nan[5::7, 1] = 0x7FC00000
+    nan[6::7, 1] = 0xFFFFFFFF
+    want = PR.step(oracle, sc.host, nan, s, DT)
+    assert set(nan[5::7, 7]) <= set(want[1][:, 7]) and set(nan[6::7, 7]) <= set(want[1][:, 7])
+    assert np.isfinite(want[1].view(np.float32)[:, 1]).all()
+    pool.load_host(nan)
+    _check(sc.step(pool, s, DT, landed_capacity=count), want, count)
+    # lifetime = +inf never expires, whatever the age
+    old = state.copy()
+    old.view(np.float32)[::3, 3] = 1e30
+    forever = PR.settings(lifetime=np.inf)
+    want = PR.step(oracle, sc.host, old, forever, DT)
+    assert want[2][5] == 0 and want[2][2] > 0
+    pool.load_host(old)
+    _check(sc.step(pool, forever, DT, landed_capacity=count), want, count)
+    pool.close()
+
+
+@gpu
+def test_replay_and_cu_budget(scenes, oracle):
+    """The same state stepped twice gives the same bytes, and so does a step under a budget of one CU: at most 8
+    workgroups (launch_points' cap), so with 26 items and an append of more than 3 * 8 * 256 records every item
+    loop runs past its first item. The full device's result is the restatement's."""
+    from oceansimulation_amd.surface import PARTICLE_ITEM as T
+
+    sc = scenes(64)
+    count = 3 * 8 * T + T + 17
+    s = PR.settings(lifetime=1.0)
+    state = _state(oracle, sc.host, count, 3, s, DT)
+    buf, emitted = sc.emit(STEP, 3 * 64 * 64, settings=[(10.0, 1e30, SEED)] * 3)  # every texel emits
+    assert emitted.shape[0] == 3 * 64 * 64
+    capacity = count + 4000
+    want = PR.step(oracle, sc.host, state, s, DT, emit=emitted, capacity=capacity)
+    assert want[2][6] > 3 * 8 * T and want[2][7] > 0 and min(want[2][2], want[2][3], want[2][5]) > T, want[2]
+    pool = sc.pool(capacity)
+    results = []
+    try:
+        for budget in (0, 0, 1):
+            sc.fft.set_cu_budget(budget)
+            pool.load_host(state)
+            results.append(sc.step(pool, s, DT, emit=buf, landed_capacity=count))
+    finally:
+        sc.fft.set_cu_budget(0)
+    _check(results[0], want, count)
+    for other in results[1:]:
+        assert all(np.array_equal(a, b) for a, b in zip(other, results[0]))
+    pool.close()
+
+
+@gpu
+def test_emitter_is_only_read(scenes):
+    from oceansimulation_amd import hip
+
+    sc = scenes(64)
+    buf, _ = sc.emit(STEP, 1000)
+    before = buf.to_host((1000, 8), np.uint32), sc.emitter.counts()
+    pool = sc.pool(600)
+    got = sc.step(pool, PR.settings(**FLY), DT, emit=buf)
+    assert got[2][6] == 600 and got[2][7] == before[1][0] - 600
+    assert np.array_equal(buf.to_host((1000, 8), np.uint32), before[0])
+    assert np.array_equal(hip.to_host(sc.emitter.counts_device(), (18,), np.int64), before[1])
+    pool.close()
+
+
+@gpu
+def test_refusals(ocean, scenes):
+    from oceansimulation_amd import capi
+    from oceansimulation_amd.surface import SprayParticles, SurfaceSampler
+
+    sc = scenes(64)
+    pool = sc.pool(8)
+    state = np.zeros((9, 8), np.float32)
+    with pytest.raises(capi.OceanError, match="ocean_particles_load: count above the pool's capacity"):
+        pool.load_host(state)
+    pool.load_host(state[:8])
+    assert pool.counts()[0] == 8
+    s = _struct(PR.settings())
+    gens = [ocean.Generator(sc.fft, 1) for _ in range(2)]
+    gens[0].CalculateOcean(DT)
+    with pytest.raises(capi.OceanError, match="ocean_particles_step: generator 1 has no frame"):
+        pool.step(SurfaceSampler([(g, 0) for g in gens]), s, DT)
+    with pytest.raises(capi.OceanError, match="ocean_particles_step: null generator or cascade out of range"):
+        pool.step(SurfaceSampler([(gens[0], 1)]), s, DT)
+    other = ocean.FFTCalculator(64)
+    elsewhere = SprayParticles(other, 8)
+    with pytest.raises(capi.OceanError, match="ocean_particles_step: the first generator is on another plan"):
+        elsewhere.step(sc.sampler, s, DT)
+    small = ocean.FFTCalculator(32)
+    g32 = ocean.Generator(small, 1)
+    g32.CalculateOcean(DT)
+    with pytest.raises(capi.OceanError, match="ocean_particles_step: all cascades must share one map size"):
+        pool.step(SurfaceSampler([(gens[0], 0), (g32, 0)]), s, DT)
+    assert pool.counts()[0] == 8  # refused calls change nothing
+    elsewhere.close()
+    pool.close()
+    for g in gens + [g32]:
+        g.close()
+    other.close()
+    small.close()
