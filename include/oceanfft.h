@@ -748,6 +748,86 @@ int ocean_camera_render(ocean_generator* const* gens, const int* cascades, int c
                         const ocean_shading* shading, const ocean_march* march, int width, int height, float* image,
                         float* aux, uint8_t* image8);
 
+/* ---- Camera layers: whitecaps in the water pass, spray records splatted over it -----------------
+ * ocean_camera_render with what makes a sea look white: the persistent foam (ocean_generator_advance_foam)
+ * shaded under the fog, and spray records (an ocean_particles list, or an ocean_spray_emit call's out)
+ * drawn as small screen-space sprites with a per-pixel depth test against the water each pixel's ray found,
+ * a hit count and the nearest record's index. The same inputs give the same bytes on every run. No
+ * reference counterpart (the reference draws neither); the defaults of ocean_default_camera_layers are
+ * starting points, not measurements.
+ *
+ * Contract, in unfused fp32, with ocean_camera_render's names (T = tan_half_fov_y, aspect, dot, min, max,
+ * sky, col, diffuse, z, V, d, f):
+ *   water pass: ocean_camera_render's contract with one insertion at status 0 when foam_opacity > 0, after
+ *         col and before the fog:
+ *         foam = the persistent foam at V.xz: the sum over pairs of tap_c(F_c) / (float)count, accumulated
+ *                as the fragment stage accumulates the Jacobian there (ocean_surface_sample_foam's slot 7 for
+ *                a point displaced to V.xz); always on level 0, also with lod_scale > 0
+ *         w = min(max((foam - foam_lo) / (foam_hi - foam_lo), 0), 1);  w = (w*w) * (3 - 2*w)
+ *         w = w * foam_opacity
+ *         fc.c = (diffuse + 0.5) * foam_color.c
+ *         col'.c = col.c*(1 - w) + fc.c*w          then out.c = col'.c*(1 - f) + sky(d).c*f as before
+ *         Every generator then needs foam storage (ocean_surface_sample_foam's rule).
+ *   spray pass (records non-null and max_records > 0): n = min(*count_device, max_records) read on the
+ *         device (a null count_device: n = max_records; a negative count: 0). For each record r < n with
+ *         p = its slots 0..2:
+ *         e = p - position;  z = dot(e, forward);  x = dot(e, right);  y = dot(e, up)
+ *         culled unless z >= near_plane && z <= far_plane                           (NaN culls)
+ *         sx = ((x / (z * (aspect*T))) + 1) * (0.5f * (float)width);   ci = floorf(sx)
+ *         sy = (1 - (y / (z * T))) * (0.5f * (float)height);           cj = floorf(sy)
+ *         half = (int)min(floorf(spray_radius / (z * ((2*T) / (float)height))), (float)spray_max_half),
+ *                a NaN gives 0
+ *         culled unless (float)-half <= ci <= (float)(width-1+half) and (float)-half <= cj <=
+ *                (float)(height-1+half), compared in float                          (NaN culls)
+ *         for every pixel q = (ci+a, cj+b), |a|, |b| <= half, inside the image:
+ *             passes iff aux[q].status != 0 || z < aux[q].z          (the water pass's view depth)
+ *             key[q] = min(key[q], (uint64)bits(z) << 32 | r);   hits[q] += 1
+ *         key starts at all ones and hits at 0. A record that passes has z > 0 (z = 0 projects to infinity),
+ *         so the bits of z order as the floats do; equal depths resolve to the lower record index. min and +
+ *         are integer atomics: they commute, so the words do not depend on the order of arrival.
+ *   composite, per pixel with c = hits > 0, zs = the key's high word as a float, r = its low word, base = the
+ *         water pass's pixel:
+ *         a = min((float)c * spray_opacity, 1)
+ *         fs = max(1 - expf(-((zs - fog_begin) * fog_density)), 0)
+ *         s.c = spray_color.c * light_color.c;   sc.c = s.c*(1 - fs) + sky(d).c*fs
+ *         out.c = base.c*(1 - a) + sc.c*a
+ *         c == 0: out = base.
+ *   image = (out, 1);  image8 from out as ocean_camera_render's;  aux = the water pass's, unchanged
+ *   aux2 = (foam, zs, the bits of the uint32 c, the bits of the uint32 r): foam is 0 where status != 0 or
+ *         foam_opacity == 0; a pixel without spray has zs = 0, c = 0, r = 0xFFFFFFFF.
+ * image, aux, aux2: width*height x 4 floats; image8: width*height x 4 bytes; device memory, any of them null,
+ * not all. records: device memory, 8 floats per record, 4-byte aligned. scratch: caller-owned device memory
+ * of ocean_camera_layers_scratch_bytes(width, height) bytes (48 per pixel and at most 32 of padding; 0 for a
+ * width or height outside 1..16384), 16-byte aligned, needed only when the spray pass runs: the per-pixel
+ * key, hit count and foam, and the float image and aux where the caller passed null for them. Its contents
+ * are undefined after the call.
+ * With foam_opacity == 0 and no spray pass the picture is ocean_camera_render's own launch (the same kernel),
+ * and aux2, if asked for, a constant fill in a launch of its own. With foam and no spray: one launch. With
+ * spray: three (water, splat, composite). All on the plan's stream under its CU budget; no allocation, no
+ * host synchronisation.
+ * OCEAN_ERR_INVALID, before any device call: everything ocean_camera_render refuses (up to its outputs);
+ * null layers; a non-finite layers entry; foam_lo >= foam_hi; foam_opacity or spray_opacity outside 0..1;
+ * a negative spray_radius; spray_max_half outside 0..8; max_records outside 0..2^28; records non-null with
+ * max_records > 0 and a null scratch; all four outputs null. Then the generators' rules as
+ * ocean_camera_render, and with foam_opacity > 0 a generator without foam storage (named by its index). */
+typedef struct ocean_camera_layers
+{
+  float foam_color[3];    /* default (1, 1, 1) */
+  float foam_lo, foam_hi; /* foam value where whitecaps begin / are full; default 0.25, 0.75 */
+  float foam_opacity;     /* 0: no foam stage, no foam storage needed; default 1 */
+  float spray_color[3];   /* default (1, 1, 1) */
+  float spray_radius;     /* metres: world half-size of a particle's sprite; default 0.05 */
+  int32_t spray_max_half; /* sprite half-size cap in pixels, 0..8; default 2 */
+  float spray_opacity;    /* per particle covering a pixel; default 0.25 */
+} ocean_camera_layers;
+void ocean_default_camera_layers(ocean_camera_layers* layers);
+size_t ocean_camera_layers_scratch_bytes(int width, int height);
+int ocean_camera_render_layers(ocean_generator* const* gens, const int* cascades, int count,
+                               const ocean_camera* camera, const ocean_shading* shading, const ocean_march* march,
+                               const ocean_camera_layers* layers, int width, int height, const float* records,
+                               const int64_t* count_device, int64_t max_records, void* scratch, float* image,
+                               float* aux, float* aux2, uint8_t* image8);
+
 /* ---- Hull sets: net wave force and torque on batches of floating bodies -------------------------
  * The consumer of the three sections above: a floating body is a set of hull points, each carrying a
  * displaced volume and drag coefficients; per step the caller hands in the bodies' poses and gets one

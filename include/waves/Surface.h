@@ -85,6 +85,19 @@ public:
   Vision::ID GetRenderAux() const { return renderAux; }
   Vision::ID GetRenderBytes() const { return renderBytes; }
 
+  // Render with what makes the sea white (ocean_camera_render_layers, oceanfft.h): the persistent foam shaded
+  // under the fog (layers.foam_opacity > 0: every generator needs a Generator::AdvanceFoam() or ResetFoam()
+  // first) and spray records drawn over the water with a per-pixel depth test: recordsDevice is a
+  // SprayParticles pool's GetRecords() with its GetCountsDevice() and capacity, or a SprayEmitter call's records
+  // with a device count (null: all maxRecords); a null recordsDevice draws no spray. The same textures as
+  // Render, and GetRenderAux2(): (foam, spray depth, hit count, nearest record index, the last two as uint32
+  // bits) per pixel. A call replays bit for bit.
+  Vision::ID RenderLayers(const std::vector<Generator*>& generators, const ocean_camera& camera,
+                          const ocean_shading& shading, const ocean_march& march, const ocean_camera_layers& layers,
+                          int width, int height, const float* recordsDevice = nullptr,
+                          const int64_t* countDevice = nullptr, int64_t maxRecords = 0);
+  Vision::ID GetRenderAux2() const { return renderAux2; }
+
   // Sample with the persistent foam (ocean_surface_sample_plane_foam, oceanfft.h): the same mesh and the
   // same texture layout as Sample, with the generators' averaged foam in the last float of each vertex,
   // which Sample leaves 0. Every generator needs a Generator::AdvanceFoam() or ResetFoam() first. Its own
@@ -104,7 +117,8 @@ public:
                         int iterations, float tolerance);
 
 private:
-  Vision::ID renderImage = 0, renderAux = 0, renderBytes = 0;
+  void RenderTextures(int width, int height, const char* who);
+  Vision::ID renderImage = 0, renderAux = 0, renderBytes = 0, renderAux2 = 0, renderScratch = 0;
   int renderWidth = 0, renderHeight = 0;
   Vision::ID waterPoints = 0;
   int64_t waterPointCount = 0;

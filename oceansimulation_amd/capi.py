@@ -139,6 +139,24 @@ class OceanMarch(ctypes.Structure):
 
 assert ctypes.sizeof(OceanCamera) == 64 and ctypes.sizeof(OceanShading) == 76 and ctypes.sizeof(OceanMarch) == 28
 
+
+class OceanCameraLayers(ctypes.Structure):
+    """ocean_camera_layers: the foam stage and the spray sprites of ocean_camera_render_layers, 48 bytes."""
+
+    _fields_ = [
+        ("foam_color", ctypes.c_float * 3),
+        ("foam_lo", ctypes.c_float),
+        ("foam_hi", ctypes.c_float),
+        ("foam_opacity", ctypes.c_float),
+        ("spray_color", ctypes.c_float * 3),
+        ("spray_radius", ctypes.c_float),
+        ("spray_max_half", ctypes.c_int32),
+        ("spray_opacity", ctypes.c_float),
+    ]
+
+
+assert ctypes.sizeof(OceanCameraLayers) == 48
+
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _f = ctypes.c_float
@@ -211,6 +229,11 @@ SIGNATURES = {
     "ocean_camera_rays": (_i, [ctypes.POINTER(OceanCamera), _i, _i, _vp, _vp]),
     "ocean_camera_render": (_i, [_vp, _vp, _i, ctypes.POINTER(OceanCamera), ctypes.POINTER(OceanShading),
                                  ctypes.POINTER(OceanMarch), _i, _i, _vp, _vp, _vp]),
+    "ocean_default_camera_layers": (None, [ctypes.POINTER(OceanCameraLayers)]),
+    "ocean_camera_layers_scratch_bytes": (_sz, [_i, _i]),
+    "ocean_camera_render_layers": (_i, [_vp, _vp, _i, ctypes.POINTER(OceanCamera), ctypes.POINTER(OceanShading),
+                                        ctypes.POINTER(OceanMarch), ctypes.POINTER(OceanCameraLayers), _i, _i, _vp, _vp,
+                                        ctypes.c_int64, _vp, _vp, _vp, _vp, _vp]),
     "ocean_default_foam_settings": (None, [_fsp]),
     "ocean_generator_foam_settings": (_fsp, [_vp, _i]),
     "ocean_generator_advance_foam": (_i, [_vp, _f]),

@@ -4,6 +4,9 @@
 // pixel's footprint when lod_scale > 0) -> the reference's water colour (resources/waveShader.glsl:146-160)
 // -> its fog (:221-233) -> its sky (:41-63) -> image. No hit record goes through memory: per pixel 16 B
 // (image), 16 B (aux) and 4 B (image8) are written, whichever of them the caller asked for.
+// ocean_camera_render_layers' water pass is the same kernel with FOAM = true: the persistent foam shaded
+// between the water colour and the fog, and the per-pixel words its spray pass (device/k_camera_spray.h)
+// starts from.
 //
 // A work item is a 16 x 16 pixel tile; wave w of the workgroup owns an 8 x 8 sub-tile of it, so the 64 rays
 // of a wave leave through neighbouring pixels: their march lengths are similar (a wave runs until its last
@@ -16,8 +19,11 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "device/ray_march.h"
 #include "device/surface_lod.h"
+#include "device/surface_sample.h"
 #include "ocean_internal.h"
 
 namespace oceanfft
@@ -88,13 +94,27 @@ __global__ __launch_bounds__(kCameraThreads) void k_camera_rays(CameraParams cam
   }
 }
 
+// The two arguments only the FOAM variants have: nothing in their place otherwise, so the FOAM = false
+// instantiations read the arguments, and are the code, they were before the variants existed.
+struct CameraNoArg
+{
+};
+template <bool FOAM>
+using CameraFoamArg = std::conditional_t<FOAM, SurfaceFoam, CameraNoArg>;
+template <bool FOAM>
+using CameraWaterArg = std::conditional_t<FOAM, CameraWaterLayers, CameraNoArg>;
+
 // grid: items = ceil(width / 16) * ceil(height / 16) tiles, item loop. The camera and the shading constants
 // on top of the march's arguments ask for 106 SGPRs, one wave per SIMD less than the march alone runs at
 // (8 waves need <= 96 on gfx950): capped, the surplus spills to lanes of one VGPR (no scratch).
-template <bool LOD>
+// FOAM (ocean_camera_render_layers' water pass): the foam stage between the water colour and the fog (when
+// lw.foam_opacity > 0: the foam maps in an argument of their own, as k_surface_foam), the pixel's aux2 row
+// when no spray pass follows, and when one does the pixel's foam, key and hit words for it (lw.key non-null):
+// the kernel owns each pixel exactly once, so the spray pass needs no memset.
+template <bool LOD, bool FOAM>
 __global__ __launch_bounds__(kCameraThreads) __attribute__((amdgpu_num_sgpr(96))) void k_camera_render(
     SurfaceParams p, RaycastParams rc, CameraParams cam, ShadingParams sh, float4* __restrict__ image,
-    float4* __restrict__ aux, uint32_t* __restrict__ image8)
+    float4* __restrict__ aux, uint32_t* __restrict__ image8, CameraFoamArg<FOAM> fm, CameraWaterArg<FOAM> lw)
 {
 #pragma clang fp contract(off)
   float ylo, yhi;
@@ -115,6 +135,7 @@ __global__ __launch_bounds__(kCameraThreads) __attribute__((amdgpu_num_sgpr(96))
     float4 a = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
     float fog = 1.0f;  // the share of sky(d): all of it unless the ray hits
     float wr = 0.0f, wg = 0.0f, wb = 0.0f;
+    [[maybe_unused]] float foam = 0.0f;
     RayMarch m;
     if (ray_march(p, rc, ylo, yhi, cam.pos[0], cam.pos[1], cam.pos[2], cam.near_plane * ray.len, ray.dx, ray.dy, ray.dz,
                   cam.far_plane * ray.len, m))
@@ -147,6 +168,18 @@ __global__ __launch_bounds__(kCameraThreads) __attribute__((amdgpu_num_sgpr(96))
         wr = ((light * sh.wave[0]) * sr) + scatter * sh.scatter[0];
         wg = ((light * sh.wave[1]) * sg) + scatter * sh.scatter[1];
         wb = ((light * sh.wave[2]) * sb) + scatter * sh.scatter[2];
+        if constexpr (FOAM)
+          if (lw.foam_opacity > 0.0f)
+          {
+            foam = surface_foam_stage(p, fm, m.vx, m.vz);
+            float w = ray_min(ray_max((foam - lw.foam_lo) / (lw.foam_hi - lw.foam_lo), 0.0f), 1.0f);
+            w = (w * w) * (3.0f - 2.0f * w);
+            w = w * lw.foam_opacity;
+            const float lit = diffuse + 0.5f;
+            wr = wr * (1.0f - w) + (lit * lw.foam_color[0]) * w;
+            wg = wg * (1.0f - w) + (lit * lw.foam_color[1]) * w;
+            wb = wb * (1.0f - w) + (lit * lw.foam_color[2]) * w;
+          }
         fog = ray_max(1.0f - expf(-((z - sh.fog_begin) * sh.fog_density)), 0.0f);
       }
     }
@@ -163,6 +196,17 @@ __global__ __launch_bounds__(kCameraThreads) __attribute__((amdgpu_num_sgpr(96))
       aux[idx] = a;
     if (image8)
       image8[idx] = camera_byte(cr) | (camera_byte(cg) << 8) | (camera_byte(cb) << 16) | 0xFF000000u;
+    if constexpr (FOAM)
+    {
+      if (lw.aux2)
+        lw.aux2[idx] = make_float4(foam, 0.0f, __uint_as_float(0u), __uint_as_float(0xFFFFFFFFu));
+      if (lw.key)
+      {
+        lw.key[idx] = ~0ull;
+        lw.hits[idx] = 0u;
+        lw.foam[idx] = foam;
+      }
+    }
   }
 }
 

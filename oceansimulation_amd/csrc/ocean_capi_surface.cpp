@@ -1,7 +1,7 @@
 // ocean_capi_surface.cpp — the part of the C ABI (include/oceanfft.h) that consumes a generator's maps:
 // the map getters, ocean_surface_sample / _query / _sample_plane, the mip pyramids and the *_lod requests,
 // the rate maps and ocean_surface_velocity, the depth layers and ocean_water_kinematics, the bounds and ocean_surface_raycast, the persistent foam with
-// ocean_surface_sample_foam, the camera images (ocean_camera_render), the hull sets, the spray emitters and the
+// ocean_surface_sample_foam, the camera images (ocean_camera_render, ocean_camera_render_layers), the hull sets, the spray emitters and the
 // spray particles.
 // The plans and generators themselves are in ocean_capi.cpp, their exchanges in ocean_capi_exchange.cpp;
 // ocean_capi_internal.h has what the three share.
@@ -687,12 +687,12 @@ int ocean_camera_rays(const ocean_camera* camera, int width, int height, float* 
   return OCEAN_OK;
 }
 
-int ocean_camera_render(ocean_generator* const* gens, const int* cascades, int count, const ocean_camera* camera,
-                        const ocean_shading* shading, const ocean_march* march, int width, int height, float* image,
-                        float* aux, uint8_t* image8)
+// The rules of a render that need no generator, in the contract's order up to the outputs, and the camera's
+// and the shading's kernel arguments (ocean_camera_render, ocean_camera_render_layers)
+static int camera_scalars(ocean_generator* const* gens, const int* cascades, const ocean_camera* camera,
+                          const ocean_shading* shading, const ocean_march* march, int width, int height,
+                          CameraParams& cam, ShadingParams& sh, const std::string& who)
 {
-  const std::string who = "ocean_camera_render";
-  // the rules that need no generator first
   if (!gens || !cascades)
     return fail(OCEAN_ERR_INVALID, who + ": null gens / cascades");
   if (!camera)
@@ -701,7 +701,6 @@ int ocean_camera_render(ocean_generator* const* gens, const int* cascades, int c
     return fail(OCEAN_ERR_INVALID, who + ": null shading");
   if (!march)
     return fail(OCEAN_ERR_INVALID, who + ": null march");
-  CameraParams cam;
   TRY(camera_params(camera, width, height, cam, who));
   static_assert(sizeof(ocean_shading) == 19 * sizeof(float), "ocean_shading is 19 floats");
   const float* entries = shading->wave_color;
@@ -720,24 +719,7 @@ int ocean_camera_render(ocean_generator* const* gens, const int* cascades, int c
     return fail(OCEAN_ERR_INVALID, who + ": fog_density must be >= 0");
   TRY(check_march(march->step, march->max_steps, march->refine, march->iterations, march->tolerance, march->slope,
                   march->pad, who));
-  if (!image && !aux && !image8)
-    return fail(OCEAN_ERR_INVALID, who + ": all three outputs are null");
-  SurfaceParams p;
-  ocean_fft* fft;
-  if (cam.lod_scale > 0.0f)
-    TRY(surface_params_lod(gens, cascades, count, p, fft, who.c_str()));
-  else
-    TRY(surface_params(gens, cascades, count, p, fft, who.c_str()));
-  RaycastParams r{};
-  TRY(surface_bounds_rows(gens, cascades, count, r, who.c_str()));
-  r.step = march->step;
-  r.max_steps = march->max_steps;
-  r.refine = march->refine;
-  r.iterations = march->iterations;
-  r.tolerance = march->tolerance;
-  r.slope = march->slope;
-  r.pad = march->pad;
-  ShadingParams sh{};
+  sh = ShadingParams{};
   for (int k = 0; k < 3; k++)
   {
     sh.wave[k] = shading->wave_color[k];
@@ -752,6 +734,44 @@ int ocean_camera_render(ocean_generator* const* gens, const int* cascades, int c
                              0.0174533);
   sh.fog_begin = shading->fog_begin;
   sh.fog_density = shading->fog_density;
+  return OCEAN_OK;
+}
+
+// The generators' part of a render: the maps (the pyramids with lod_scale > 0), the bounds rows and the march
+static int camera_scene(ocean_generator* const* gens, const int* cascades, int count, const CameraParams& cam,
+                        const ocean_march* march, SurfaceParams& p, RaycastParams& r, ocean_fft*& fft,
+                        const std::string& who)
+{
+  if (cam.lod_scale > 0.0f)
+    TRY(surface_params_lod(gens, cascades, count, p, fft, who.c_str()));
+  else
+    TRY(surface_params(gens, cascades, count, p, fft, who.c_str()));
+  r = RaycastParams{};
+  TRY(surface_bounds_rows(gens, cascades, count, r, who.c_str()));
+  r.step = march->step;
+  r.max_steps = march->max_steps;
+  r.refine = march->refine;
+  r.iterations = march->iterations;
+  r.tolerance = march->tolerance;
+  r.slope = march->slope;
+  r.pad = march->pad;
+  return OCEAN_OK;
+}
+
+int ocean_camera_render(ocean_generator* const* gens, const int* cascades, int count, const ocean_camera* camera,
+                        const ocean_shading* shading, const ocean_march* march, int width, int height, float* image,
+                        float* aux, uint8_t* image8)
+{
+  const std::string who = "ocean_camera_render";
+  CameraParams cam;
+  ShadingParams sh;
+  TRY(camera_scalars(gens, cascades, camera, shading, march, width, height, cam, sh, who));
+  if (!image && !aux && !image8)
+    return fail(OCEAN_ERR_INVALID, who + ": all three outputs are null");
+  SurfaceParams p;
+  RaycastParams r;
+  ocean_fft* fft;
+  TRY(camera_scene(gens, cascades, count, cam, march, p, r, fft, who));
   HIP_TRY(launch_camera_render(p, r, cam, sh, reinterpret_cast<float4*>(image), reinterpret_cast<float4*>(aux),
                                reinterpret_cast<uint32_t*>(image8), fft->stream, fft->cus),
           who.c_str());
@@ -930,6 +950,116 @@ int ocean_surface_sample_plane_foam(ocean_generator* const* gens, const int* cas
   TRY(plane_request(camera, res, out, "ocean_surface_sample_plane_foam", plane, pts));
   HIP_TRY(launch_surface_foam(p, f, plane, nullptr, pts, reinterpret_cast<float4*>(out), fft->stream, fft->cus),
           "ocean_surface_sample_plane_foam");
+  return OCEAN_OK;
+}
+
+// ---- camera layers: the foam stage in the water pass, spray records splatted over it ----
+void ocean_default_camera_layers(ocean_camera_layers* l)
+{
+  if (l)  // starting points, not measurements
+    *l = ocean_camera_layers{{1.0f, 1.0f, 1.0f}, 0.25f, 0.75f, 1.0f, {1.0f, 1.0f, 1.0f}, 0.05f, 2, 0.25f};
+}
+
+size_t ocean_camera_layers_scratch_bytes(int width, int height)
+{
+  if (width < 1 || width > 16384 || height < 1 || height > 16384)
+    return 0;
+  return camera_layers_scratch_bytes(width, height);
+}
+
+int ocean_camera_render_layers(ocean_generator* const* gens, const int* cascades, int count,
+                               const ocean_camera* camera, const ocean_shading* shading, const ocean_march* march,
+                               const ocean_camera_layers* layers, int width, int height, const float* records,
+                               const int64_t* count_device, int64_t max_records, void* scratch, float* image,
+                               float* aux, float* aux2, uint8_t* image8)
+{
+  const std::string who = "ocean_camera_render_layers";
+  CameraParams cam;
+  ShadingParams sh;
+  TRY(camera_scalars(gens, cascades, camera, shading, march, width, height, cam, sh, who));
+  if (!layers)
+    return fail(OCEAN_ERR_INVALID, who + ": null layers");
+  const ocean_camera_layers& l = *layers;
+  const float entries[12] = {l.foam_color[0], l.foam_color[1], l.foam_color[2], l.foam_lo, l.foam_hi, l.foam_opacity,
+                             l.spray_color[0], l.spray_color[1], l.spray_color[2], l.spray_radius, l.spray_opacity,
+                             0.0f};
+  for (float v : entries)
+    if (!std::isfinite(v))
+      return fail(OCEAN_ERR_INVALID, who + ": non-finite layers entry");
+  if (l.foam_lo >= l.foam_hi)
+    return fail(OCEAN_ERR_INVALID, who + ": foam_lo must be below foam_hi");
+  if (l.foam_opacity < 0.0f || l.foam_opacity > 1.0f)
+    return fail(OCEAN_ERR_INVALID, who + ": foam_opacity outside 0..1");
+  if (l.spray_opacity < 0.0f || l.spray_opacity > 1.0f)
+    return fail(OCEAN_ERR_INVALID, who + ": spray_opacity outside 0..1");
+  if (l.spray_radius < 0.0f)
+    return fail(OCEAN_ERR_INVALID, who + ": spray_radius must be >= 0");
+  if (l.spray_max_half < 0 || l.spray_max_half > 8)
+    return fail(OCEAN_ERR_INVALID, who + ": spray_max_half outside 0..8");
+  if (max_records < 0 || max_records > ((int64_t)1 << 28))
+    return fail(OCEAN_ERR_INVALID, who + ": max_records outside 0..2^28");
+  const bool spray = records && max_records > 0;
+  if (spray && !scratch)
+    return fail(OCEAN_ERR_INVALID, who + ": records need scratch (ocean_camera_layers_scratch_bytes)");
+  if (!image && !aux && !aux2 && !image8)
+    return fail(OCEAN_ERR_INVALID, who + ": all four outputs are null");
+  SurfaceParams p;
+  RaycastParams r;
+  ocean_fft* fft;
+  TRY(camera_scene(gens, cascades, count, cam, march, p, r, fft, who));
+  SurfaceFoam fm{};
+  const bool foam = l.foam_opacity > 0.0f;
+  if (foam)
+    TRY(surface_foam(gens, cascades, count, fft, fm, who.c_str()));
+  float4* const image4 = reinterpret_cast<float4*>(image);
+  float4* const aux4 = reinterpret_cast<float4*>(aux);
+  float4* const aux24 = reinterpret_cast<float4*>(aux2);
+  uint32_t* const bytes = reinterpret_cast<uint32_t*>(image8);
+  if (!foam && !spray)
+  {
+    // ocean_camera_render itself: the same kernel instantiation; aux2 has nothing to say but "no spray"
+    if (image || aux || image8)
+      HIP_TRY(launch_camera_render(p, r, cam, sh, image4, aux4, bytes, fft->stream, fft->cus), who.c_str());
+    if (aux2)
+      HIP_TRY(launch_camera_aux2_none(cam, aux24, fft->stream, fft->cus), who.c_str());
+    return OCEAN_OK;
+  }
+  CameraWaterLayers lw{};
+  for (int k = 0; k < 3; k++)
+    lw.foam_color[k] = l.foam_color[k];
+  lw.foam_lo = l.foam_lo;
+  lw.foam_hi = l.foam_hi;
+  lw.foam_opacity = l.foam_opacity;
+  if (!spray)
+  {
+    lw.aux2 = aux24;
+    HIP_TRY(launch_camera_render_foam(p, r, cam, sh, fm, lw, image4, aux4, bytes, fft->stream, fft->cus), who.c_str());
+    return OCEAN_OK;
+  }
+  // the spray pass follows: the water pass leaves its float image and aux where the composite and the splat
+  // read them (the caller's, else the scratch's), and the pixel words; image8 and aux2 are the composite's
+  CameraSpray s{};
+  float4 *scratch_image, *scratch_aux;
+  float* foam_words;
+  camera_layers_scratch(scratch, width, height, s.key, s.hits, foam_words, scratch_image, scratch_aux);
+  s.foam = foam_words;
+  s.base = image4 ? image4 : scratch_image;
+  float4* const water_aux = aux4 ? aux4 : scratch_aux;
+  s.aux = water_aux;
+  s.records = records;
+  s.count_device = count_device;
+  s.max_records = max_records;
+  for (int k = 0; k < 3; k++)
+    s.color[k] = l.spray_color[k];
+  s.radius = l.spray_radius;
+  s.opacity = l.spray_opacity;
+  s.max_half = l.spray_max_half;
+  lw.key = s.key;
+  lw.hits = s.hits;
+  lw.foam = foam_words;
+  HIP_TRY(launch_camera_render_foam(p, r, cam, sh, fm, lw, s.base, water_aux, nullptr, fft->stream, fft->cus),
+          who.c_str());
+  HIP_TRY(launch_camera_spray(cam, sh, s, image4, bytes, aux24, fft->stream, fft->cus), who.c_str());
   return OCEAN_OK;
 }
 

@@ -388,6 +388,49 @@ struct SurfaceFoam
 };
 hipError_t launch_surface_foam(const SurfaceParams& p, const SurfaceFoam& f, const SurfacePlane& plane, const float2* xz,
                                int64_t count, float4* out, hipStream_t stream, int cus);
+// ocean_camera_render_layers (include/oceanfft.h, device/k_camera.h, device/k_camera_spray.h). The water
+// pass's own values: the foam stage (foam_opacity 0: none, SurfaceFoam unread), aux2 when no spray pass
+// follows (or null), and when one does the per-pixel words it starts from (key null: none).
+struct CameraWaterLayers
+{
+  float foam_color[3];
+  float foam_lo, foam_hi, foam_opacity;
+  float4* aux2;
+  unsigned long long* key;  // [pixels]: ~0
+  uint32_t* hits;           // [pixels]: 0
+  float* foam;              // [pixels]: the pixel's foam, for the composite's aux2
+};
+// The spray pass: the records, the per-pixel words behind the scratch pointer and the water pass's picture
+// (the caller's image / aux, or the scratch's where the caller passed null).
+struct CameraSpray
+{
+  const float* records;         // [max_records][8]
+  const int64_t* count_device;  // or null: max_records
+  int64_t max_records;          // 1 .. 2^28
+  unsigned long long* key;
+  uint32_t* hits;
+  const float* foam;
+  float4* base;       // the water pass's image, read by the composite
+  const float4* aux;  // the water pass's aux, read by the splat
+  float color[3];
+  float radius, opacity;
+  int max_half;
+};
+size_t camera_layers_scratch_bytes(int width, int height);
+// The pointers of a scratch buffer of camera_layers_scratch_bytes bytes: key, hits, foam, then the float
+// image and aux (each used only where the caller has none)
+void camera_layers_scratch(void* scratch, int width, int height, unsigned long long*& key, uint32_t*& hits,
+                           float*& foam, float4*& image, float4*& aux);
+// The water pass of the layered render: k_camera_render<LOD, true>, one launch
+hipError_t launch_camera_render_foam(const SurfaceParams& p, const RaycastParams& rc, const CameraParams& cam,
+                                     const ShadingParams& sh, const SurfaceFoam& fm, const CameraWaterLayers& lw,
+                                     float4* image, float4* aux, uint32_t* image8, hipStream_t stream, int cus);
+// aux2 of a call with both layers off (the picture is launch_camera_render's): (0, 0, 0, index 0xFFFFFFFF)
+hipError_t launch_camera_aux2_none(const CameraParams& cam, float4* aux2, hipStream_t stream, int cus);
+// The spray pass after it: the splat (a lane per record) and the composite (a lane per pixel), two launches;
+// image / image8 / aux2: the call's outputs, any of them null.
+hipError_t launch_camera_spray(const CameraParams& cam, const ShadingParams& sh, const CameraSpray& s, float4* image,
+                               uint32_t* image8, float4* aux2, hipStream_t stream, int cus);
 // ocean_hulls (include/oceanfft.h, device/k_hulls.h): the tables ocean_hulls_create builds and one call
 constexpr int kHullTilePoints = 64;  // points per work item: the lanes of one wave
 // One tile of one body: points [first, first + count) of the hull set's points, point_out rows from

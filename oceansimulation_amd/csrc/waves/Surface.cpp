@@ -1,6 +1,6 @@
 // Waves::SurfaceSampler over ocean_surface_sample_plane / ocean_surface_query /
 // ocean_surface_sample_plane_lod / ocean_surface_velocity / ocean_surface_sample_plane_foam /
-// ocean_water_kinematics / ocean_camera_render, and Waves::HullSet over ocean_hulls
+// ocean_water_kinematics / ocean_camera_render / ocean_camera_render_layers, and Waves::HullSet over ocean_hulls
 // (include/oceanfft.h).
 #include "waves/Surface.h"
 
@@ -26,7 +26,7 @@ SurfaceSampler::~SurfaceSampler()
     renderDevice->DestroyTexture2D(verticesFoam);
   if (waterPoints)
     renderDevice->DestroyTexture2D(waterPoints);
-  for (Vision::ID id : {renderImage, renderAux, renderBytes})
+  for (Vision::ID id : {renderImage, renderAux, renderBytes, renderAux2, renderScratch})
     if (id)
       renderDevice->DestroyTexture2D(id);
 }
@@ -239,30 +239,34 @@ Vision::ID SurfaceSampler::Kinematics(const std::vector<Generator*>& generators,
   return waterPoints;
 }
 
+void SurfaceSampler::RenderTextures(int width, int height, const char* who)
+{
+  if (width < 1 || height < 1)
+    throw std::runtime_error(std::string(who) + ": need at least one pixel");
+  if (renderImage && renderWidth == width && renderHeight == height)
+    return;
+  for (Vision::ID* id : {&renderImage, &renderAux, &renderBytes, &renderAux2, &renderScratch})
+  {
+    if (*id)
+      renderDevice->DestroyTexture2D(*id);
+    *id = 0;
+  }
+  Vision::Texture2DDesc desc;
+  desc.Width = (std::size_t)width;
+  desc.Height = (std::size_t)height;
+  desc.PixelType = Vision::PixelType::RGBA32Float;
+  renderImage = renderDevice->CreateTexture2D(desc);
+  renderAux = renderDevice->CreateTexture2D(desc);
+  desc.PixelType = Vision::PixelType::RGBA8;
+  renderBytes = renderDevice->CreateTexture2D(desc);
+  renderWidth = width;
+  renderHeight = height;
+}
+
 Vision::ID SurfaceSampler::Render(const std::vector<Generator*>& generators, const ocean_camera& camera,
                                   const ocean_shading& shading, const ocean_march& march, int width, int height)
 {
-  if (width < 1 || height < 1)
-    throw std::runtime_error("SurfaceSampler::Render: need at least one pixel");
-  if (!renderImage || renderWidth != width || renderHeight != height)
-  {
-    for (Vision::ID* id : {&renderImage, &renderAux, &renderBytes})
-    {
-      if (*id)
-        renderDevice->DestroyTexture2D(*id);
-      *id = 0;
-    }
-    Vision::Texture2DDesc desc;
-    desc.Width = (std::size_t)width;
-    desc.Height = (std::size_t)height;
-    desc.PixelType = Vision::PixelType::RGBA32Float;
-    renderImage = renderDevice->CreateTexture2D(desc);
-    renderAux = renderDevice->CreateTexture2D(desc);
-    desc.PixelType = Vision::PixelType::RGBA8;
-    renderBytes = renderDevice->CreateTexture2D(desc);
-    renderWidth = width;
-    renderHeight = height;
-  }
+  RenderTextures(width, height, "SurfaceSampler::Render");
   std::vector<ocean_generator*> gens;
   std::vector<int> cascades;
   for (auto* g : generators)
@@ -276,6 +280,46 @@ Vision::ID SurfaceSampler::Render(const std::vector<Generator*>& generators, con
                                      static_cast<uint8_t*>(renderDevice->GetTexturePointer(renderBytes)));
   if (rc != OCEAN_OK)
     throw std::runtime_error(std::string("SurfaceSampler::Render: ") + ocean_last_error());
+  return renderImage;
+}
+
+Vision::ID SurfaceSampler::RenderLayers(const std::vector<Generator*>& generators, const ocean_camera& camera,
+                                        const ocean_shading& shading, const ocean_march& march,
+                                        const ocean_camera_layers& layers, int width, int height,
+                                        const float* recordsDevice, const int64_t* countDevice, int64_t maxRecords)
+{
+  RenderTextures(width, height, "SurfaceSampler::RenderLayers");
+  Vision::Texture2DDesc desc;
+  desc.PixelType = Vision::PixelType::RGBA32Float;
+  if (!renderAux2)
+  {
+    desc.Width = (std::size_t)width;
+    desc.Height = (std::size_t)height;
+    renderAux2 = renderDevice->CreateTexture2D(desc);
+  }
+  const bool spray = recordsDevice && maxRecords > 0;
+  if (spray && !renderScratch)
+  {
+    desc.Width = (ocean_camera_layers_scratch_bytes(width, height) + 15) / 16;  // texels of 16 bytes
+    desc.Height = 1;
+    renderScratch = renderDevice->CreateTexture2D(desc);
+  }
+  std::vector<ocean_generator*> gens;
+  std::vector<int> cascades;
+  for (auto* g : generators)
+  {
+    gens.push_back(g->GetHandle());
+    cascades.push_back(0);
+  }
+  const int rc = ocean_camera_render_layers(
+      gens.data(), cascades.data(), (int)gens.size(), &camera, &shading, &march, &layers, width, height, recordsDevice,
+      countDevice, maxRecords, spray ? renderDevice->GetTexturePointer(renderScratch) : nullptr,
+      static_cast<float*>(renderDevice->GetTexturePointer(renderImage)),
+      static_cast<float*>(renderDevice->GetTexturePointer(renderAux)),
+      static_cast<float*>(renderDevice->GetTexturePointer(renderAux2)),
+      static_cast<uint8_t*>(renderDevice->GetTexturePointer(renderBytes)));
+  if (rc != OCEAN_OK)
+    throw std::runtime_error(std::string("SurfaceSampler::RenderLayers: ") + ocean_last_error());
   return renderImage;
 }
 

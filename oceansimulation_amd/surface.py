@@ -12,8 +12,8 @@ import math
 import numpy as np
 
 from . import hip
-from .capi import (OCEAN_ERR_INVALID, OceanCamera, OceanError, OceanMarch, OceanShading, OceanSpraySettings, check,
-                   lib)
+from .capi import (OCEAN_ERR_INVALID, OceanCamera, OceanCameraLayers, OceanError, OceanMarch, OceanShading,
+                   OceanSpraySettings, check, lib)
 from .hip import DeviceBuffer
 
 FLOATS_PER_VERTEX = 8  # x, y, z, jacobian, nx, ny, nz, 0 (query: base x, height, base z, ..., residual)
@@ -43,6 +43,13 @@ def default_march(**overrides) -> OceanMarch:
     return m
 
 
+def default_camera_layers(**overrides) -> OceanCameraLayers:
+    l = OceanCameraLayers()
+    lib().ocean_default_camera_layers(ctypes.byref(l))
+    _set_fields(l, overrides)
+    return l
+
+
 def _set_fields(struct, values) -> None:
     names = {f[0] for f in struct._fields_}
     for k, v in values.items():
@@ -67,6 +74,11 @@ def camera_pose(position, pitch_deg: float, yaw_deg: float, fov_y_deg: float, ne
                         tan_half_fov_y=math.tan(math.radians(fov_y_deg) / 2.0), near_plane=near, far_plane=far,
                         lod_scale=lod_scale))
     return c
+
+
+def camera_layers_scratch_bytes(width: int, height: int) -> int:
+    """Bytes of ocean_camera_render_layers' scratch for a width x height image."""
+    return int(lib().ocean_camera_layers_scratch_bytes(int(width), int(height)))
 
 
 def camera_rays_host(camera: OceanCamera, width: int, height: int) -> np.ndarray:
@@ -256,6 +268,54 @@ class SurfaceSampler:
         self.render(camera, shading, march, width, height, image.ptr, aux.ptr, image8.ptr)
         self.fft.synchronize()
         return (image.to_host((height, width, 4)), aux.to_host((height, width, 4)),
+                image8.to_host((height, width, 4), np.uint8))
+
+    # ---- camera images with foam and spray (with layers.foam_opacity > 0: Generator.AdvanceFoam or ResetFoam) ----
+    def render_layers(self, camera: OceanCamera, shading: OceanShading, march: OceanMarch, layers: OceanCameraLayers,
+                      width: int, height: int, image_ptr: int = 0, aux_ptr: int = 0, aux2_ptr: int = 0,
+                      image8_ptr: int = 0, particles: "SprayParticles" = None, records_ptr: int = 0,
+                      count_ptr: int = 0, max_records: int = 0, scratch_ptr: int = 0) -> None:
+        """Enqueue ocean_camera_render_layers: render's outputs and aux2 (h, w, 4) float32 (foam, spray depth,
+        hit count and nearest record index as uint32 bits), any of them 0 (not all). The spray is a
+        SprayParticles pool (its list, counted by its device table), or device records (max_records, 8) with a
+        device int64 count (0: all of them); either needs scratch_ptr, camera_layers_scratch_bytes(w, h) bytes."""
+        if particles is not None:
+            records_ptr, count_ptr, max_records = particles.records_ptr, particles.counts_device(), particles.capacity
+        check(lib().ocean_camera_render_layers(self._gens, self._cas, len(self.pairs), ctypes.byref(camera),
+                                               ctypes.byref(shading), ctypes.byref(march), ctypes.byref(layers),
+                                               int(width), int(height), ctypes.c_void_p(records_ptr),
+                                               ctypes.c_void_p(count_ptr), ctypes.c_int64(max_records),
+                                               ctypes.c_void_p(scratch_ptr), ctypes.c_void_p(image_ptr),
+                                               ctypes.c_void_p(aux_ptr), ctypes.c_void_p(aux2_ptr),
+                                               ctypes.c_void_p(image8_ptr)), "ocean_camera_render_layers")
+
+    def render_layers_host(self, camera: OceanCamera, width: int, height: int, layers: OceanCameraLayers = None,
+                           shading: OceanShading = None, march: OceanMarch = None,
+                           particles: "SprayParticles" = None, records: np.ndarray = None, count: int = None):
+        """(image, aux, aux2 (h, w, 4) float32, image8 (h, w, 4) uint8) of one camera. The spray: a SprayParticles
+        pool, or host records (n, 8) of which the first `count` are used (a device count; None: all n)."""
+        layers = default_camera_layers() if layers is None else layers
+        shading = default_shading() if shading is None else shading
+        march = default_march() if march is None else march
+        n = int(width) * int(height)
+        image, aux, aux2 = (DeviceBuffer(max(n, 1) * 16) for _ in range(3))
+        image8 = DeviceBuffer(max(n, 1) * 4)
+        rec = cnt = scratch = None
+        max_records = 0
+        if records is not None:
+            records = np.ascontiguousarray(records).reshape(-1, FLOATS_PER_VERTEX)
+            assert records.dtype.itemsize == 4
+            max_records = records.shape[0]
+            rec = DeviceBuffer.from_array(records) if max_records else None
+            if count is not None:
+                cnt = DeviceBuffer.from_array(np.array([count], np.int64))
+        if particles is not None or max_records:
+            scratch = DeviceBuffer(camera_layers_scratch_bytes(width, height))
+        self.render_layers(camera, shading, march, layers, width, height, image.ptr, aux.ptr, aux2.ptr, image8.ptr,
+                           particles=particles, records_ptr=rec.ptr if rec else 0, count_ptr=cnt.ptr if cnt else 0,
+                           max_records=max_records, scratch_ptr=scratch.ptr if scratch else 0)
+        self.fft.synchronize()
+        return (image.to_host((height, width, 4)), aux.to_host((height, width, 4)), aux2.to_host((height, width, 4)),
                 image8.to_host((height, width, 4), np.uint8))
 
     def plane_host(self, camera, res: int) -> np.ndarray:
@@ -504,4 +564,5 @@ def host_cascades(pairs):
 
 
 __all__ = ["SurfaceSampler", "HullSet", "SprayEmitter", "SprayParticles", "PARTICLE_ITEM", "host_cascades", "FLOATS_PER_VERTEX", "hip", "camera_pose",
-           "default_camera", "default_shading", "default_march", "camera_rays_host"]
+           "default_camera", "default_shading", "default_march", "camera_rays_host", "default_camera_layers",
+           "camera_layers_scratch_bytes", "OceanCameraLayers"]
