@@ -105,6 +105,57 @@ __device__ __forceinline__ float2 evolve(float4 a, float k, const CascadeFrame& 
   return make_float2(ampx + oppx, ampy + oppy);
 }
 
+// H as evolve() and its time derivative Hd = i w (a e^{iwt} - b e^{-iwt}) of one texel from one dispersion
+// and one sincos_phase (k_kinematics_pack, device/k_kinematics.h): D = a.xy (c + i s) - a.zw (c - i s),
+// Hd = i w D. The frame's own w and phase bits, so H has evolve()'s bits.
+__device__ __forceinline__ void evolve_with_rate(float4 a, float k, const CascadeFrame& f, float2& H, float2& Hd)
+{
+#pragma clang fp contract(off)
+  const float w = dispersion_evolve(k, f.g, f.h);
+  float ws, wc;
+  sincos_phase(w * f.time, &ws, &wc);
+  const float ampx = a.x * wc - a.y * ws;
+  const float ampy = a.x * ws + a.y * wc;
+  const float oppx = a.z * wc + a.w * ws;
+  const float oppy = a.w * wc - a.z * ws;
+  H = make_float2(ampx + oppx, ampy + oppy);
+  const float dx = ampx - oppx, dy = ampy - oppy;
+  Hd = make_float2(-(w * dy), w * dx);
+}
+
+// dH/dt alone (k_rates_pack, device/k_rates.h): the same operations, H dropped
+__device__ __forceinline__ float2 evolve_rate(float4 a, float k, const CascadeFrame& f)
+{
+  float2 H, Hd;
+  evolve_with_rate(a, k, f, H, Hd);
+  return Hd;
+}
+
+// Texel j of this thread in work item `local` of one cascade's strip-blocked h0 image (k_rates_pack and
+// k_kinematics_pack; the two shapes, J = 4 texels per thread or 1: device/k_rates.h): its column x and row y,
+// and its index in the blocked image, < 2^28. n = 2^logn, lcw = log2 CW (BLOCK only).
+template <bool BLOCK>
+__device__ __forceinline__ unsigned pack_item_texel(unsigned local, int j, int n, int logn, int logb, int lcw, int& x,
+                                                    int& y)
+{
+  if constexpr (BLOCK)
+  {
+    // consecutive items go down a block column: lrows = log2 of the block rows per image
+    const int lrows = logn - (10 - lcw);
+    const unsigned br = local & ((1u << lrows) - 1), bc = local >> lrows, e = 256u * j + threadIdx.x;
+    x = (int)((bc << lcw) + (e & ((1u << lcw) - 1)));
+    y = (int)((br << (10 - lcw)) + (e >> lcw));
+    return (((unsigned)x >> logb) << (logn + logb)) + ((unsigned)y << logb) + ((unsigned)x & ((1u << logb) - 1));
+  }
+  else
+  {
+    const unsigned t = (local << 8) + threadIdx.x;
+    x = (int)(((t >> (logb + logn)) << logb) + (t & ((1u << logb) - 1)));
+    y = (int)((t >> logb) & (unsigned)(n - 1));
+    return t;
+  }
+}
+
 // heightMap texel = (H + i*dH/dx, dH/dz + i*Dx)   (spectrum.compute:236)
 __device__ __forceinline__ CPair pack_height(float2 H, const KVec& q)
 {

@@ -9,7 +9,8 @@
 // which thread sees which texel does not matter to a minimum). A range that ends past the map (N = 16, 32:
 // 256 and 1024 texels) clamps its indices to the last texel, which is read again: no predicate, same result.
 // Each thread keeps 18 running values; a wave folds them in registers (permlane32 / permlane16 swaps,
-// bank-masked DPP row shifts, quad_perm: device/lane_xchg.h, the exchanges of k_hulls.h's fold64); the
+// bank-masked DPP row shifts, quad_perm: xor_lane_pair of device/lane_xchg.h, which k_hulls.h's fold64
+// combines with an add and this file with min / max); the
 // waves' 18 values cross through LDS and the item's row goes to partial[item].
 // Stage 2 (k_bounds_fold): an item is one cascade; 1024 threads fold the cascade's partial rows the same way
 // into the table.
@@ -43,28 +44,9 @@ struct BoundsBuild
 template <int STRIDE, bool MAX>
 __device__ __forceinline__ float bounds_fold_step(float v)
 {
-  float other;
-  if constexpr (STRIDE == 32 || STRIDE == 16)
-  {
-    // lo = hi = v: the swap leaves a lane's own value in one of the two and its partner's in the other
-    float lo = v, hi = v;
-    swap_lane_bit_perm<STRIDE == 32 ? 5 : 4>(lo, hi);
-    v = lo;
-    other = hi;
-  }
-  else if constexpr (STRIDE == 8 || STRIDE == 4)
-  {
-    constexpr int SET = STRIDE == 4 ? 0xA : 0xC, CLEAR = STRIDE == 4 ? 0x5 : 0x3;  // as swap_lane_bit_dpp
-    const float t = dpp_update<0x110 + STRIDE, SET>(v, v);  // lanes with the bit: lane - STRIDE
-    other = dpp_update<0x100 + STRIDE, CLEAR>(t, v);        // lanes without it: lane + STRIDE
-  }
-  else
-  {
-    static_assert(STRIDE == 2 || STRIDE == 1, "a power of two below 64");
-    constexpr int QUAD = STRIDE == 2 ? 0x4E : 0xB1;  // quad_perm:[2,3,0,1] / [1,0,3,2]
-    other = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), QUAD, 0xF, 0xF, false));
-  }
-  return MAX ? fmaxf(v, other) : fminf(v, other);
+  float a, b;
+  xor_lane_pair<STRIDE>(v, a, b);
+  return MAX ? fmaxf(a, b) : fminf(a, b);
 }
 
 template <bool MAX>

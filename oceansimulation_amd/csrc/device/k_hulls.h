@@ -8,9 +8,9 @@
 // butterfly with strides 32 -> 1, every lane adding its partner's value, so after the last step every lane
 // holds a[0] of `for h in 32 .. 1: a = a[:h] + a[h:]` (fp32 addition is commutative, so which of a pair
 // is "own" does not matter). Lanes past the tile's count carry +0.0f, the contract's padding. The
-// exchanges stay in registers: v_permlane32_swap / v_permlane16_swap for lane bits 5 and 4, bank-masked
-// DPP row shifts (device/lane_xchg.h's dpp_update) for bits 3 and 2, quad_perm for bits 1 and 0. They read
-// the registers of lanes whatever EXEC says, so they run outside every lane-dependent branch, with the
+// exchanges stay in registers (xor_lane_pair, device/lane_xchg.h, shared with the minima and maxima of
+// device/k_bounds.h): v_permlane32_swap / v_permlane16_swap for lane bits 5 and 4, bank-masked DPP row
+// shifts for bits 3 and 2, quad_perm for bits 1 and 0. They read the registers of lanes whatever EXEC says, so they run outside every lane-dependent branch, with the
 // whole wave active: the item loop and its bound are wave-uniform (one wave per workgroup, items dealt by
 // blockIdx).
 //
@@ -42,25 +42,9 @@ template <int STRIDE>
 __device__ __forceinline__ float fold_step(float v)
 {
 #pragma clang fp contract(off)
-  if constexpr (STRIDE == 32 || STRIDE == 16)
-  {
-    // lo = hi = v: the swap leaves a lane's own value in one of the two and its partner's in the other
-    float lo = v, hi = v;
-    swap_lane_bit_perm<STRIDE == 32 ? 5 : 4>(lo, hi);
-    return lo + hi;
-  }
-  else if constexpr (STRIDE == 8 || STRIDE == 4)
-  {
-    constexpr int SET = STRIDE == 4 ? 0xA : 0xC, CLEAR = STRIDE == 4 ? 0x5 : 0x3;  // as swap_lane_bit_dpp
-    const float t = dpp_update<0x110 + STRIDE, SET>(v, v);  // lanes with the bit: lane - STRIDE
-    return v + dpp_update<0x100 + STRIDE, CLEAR>(t, v);     // lanes without it: lane + STRIDE
-  }
-  else
-  {
-    static_assert(STRIDE == 2 || STRIDE == 1, "a power of two below 64");
-    constexpr int QUAD = STRIDE == 2 ? 0x4E : 0xB1;  // quad_perm:[2,3,0,1] / [1,0,3,2]
-    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), QUAD, 0xF, 0xF, false));
-  }
+  float a, b;
+  xor_lane_pair<STRIDE>(v, a, b);
+  return a + b;
 }
 
 // fold64 of the wave's 64 values, in every lane

@@ -20,7 +20,9 @@
 //
 // Memory: 16 B read (h0) and 32 * layers B written per point; k_rates_pack's two shapes (BLOCK: CW x
 // 1024 / CW texel blocks, four texels per thread, whole-line stores; linear: 256 consecutive texels of the
-// blocked image, N = 16, 32). H and Hd are evolved once per texel from one sincos_phase; the layers are
+// blocked image, N = 16, 32), by the same walk (pack_item_texel, device/evolve.h) and the same shape rule
+// (pack_shape, launch_common.h). H and Hd are evolved once per texel from one sincos_phase
+// (evolve_with_rate, device/evolve.h: evolve()'s and evolve_rate()'s bits); the layers are
 // the innermost loop and each layer's two texels are stored as soon as they are formed, so only the four
 // packed texels of a point stay live, not its layers (62 VGPRs, no scratch, 8 waves per SIMD).
 // Measured (tools/kinematics_bench.py, profiles/kinematics_bench.log; the whole call minus its EncodeIFFT
@@ -39,23 +41,6 @@ namespace oceanfft
 {
 
 constexpr int kKinematicsTile = 256;  // threads per workgroup; a BLOCK item is 1024 texels, a linear one 256
-
-// evolve() and evolve_rate() (device/evolve.h, device/k_rates.h) of one texel from one dispersion and one
-// sincos_phase: the same operations in the same order, so H and Hd have those functions' bits.
-__device__ __forceinline__ void evolve_with_rate(float4 a, float k, const CascadeFrame& f, float2& H, float2& Hd)
-{
-#pragma clang fp contract(off)
-  const float w = dispersion_evolve(k, f.g, f.h);
-  float ws, wc;
-  sincos_phase(w * f.time, &ws, &wc);
-  const float ampx = a.x * wc - a.y * ws;
-  const float ampy = a.x * ws + a.y * wc;
-  const float oppx = a.z * wc + a.w * ws;
-  const float oppy = a.w * wc - a.z * ws;
-  H = make_float2(ampx + oppx, ampy + oppy);
-  const float dx = ampx - oppx, dy = ampy - oppy;
-  Hd = make_float2(-(w * dy), w * dx);
-}
 
 // (A_h, A_v) of wavenumber k at rest depth d in water of depth h (the header of this file)
 __device__ __forceinline__ float2 depth_attenuation(float k, float d, float h)
@@ -91,25 +76,8 @@ __global__ __launch_bounds__(kKinematicsTile) void k_kinematics_pack(FrameParams
     int x[J], y[J];
     float4 a[J];
 #pragma unroll
-    for (int j = 0; j < J; j++)
-    {
-      unsigned t;  // texel of the blocked image, < 2^28
-      if constexpr (BLOCK)
-      {
-        const int lrows = logn - (10 - lcw);
-        const unsigned br = local & ((1u << lrows) - 1), bc = local >> lrows, e = 256u * j + threadIdx.x;
-        x[j] = (int)((bc << lcw) + (e & ((1u << lcw) - 1)));
-        y[j] = (int)((br << (10 - lcw)) + (e >> lcw));
-        t = (((unsigned)x[j] >> logb) << (logn + logb)) + ((unsigned)y[j] << logb) + ((unsigned)x[j] & ((1u << logb) - 1));
-      }
-      else
-      {
-        t = (local << 8) + threadIdx.x;
-        x[j] = (int)(((t >> (logb + logn)) << logb) + (t & ((1u << logb) - 1)));
-        y[j] = (int)((t >> logb) & (unsigned)(n - 1));
-      }
-      a[j] = hc[t];
-    }
+    for (int j = 0; j < J; j++)  // every load issued before the first use
+      a[j] = hc[pack_item_texel<BLOCK>(local, j, n, logn, logb, lcw, x[j], y[j])];
     const CascadeFrame f = fp.c[c];
     float4* oc = out + (size_t)c * kd.layers * 2 * nn;
 #pragma unroll

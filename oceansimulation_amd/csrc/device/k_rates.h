@@ -25,6 +25,8 @@
 // 8 TB/s at 48 B per point (a plain copy of the same bytes takes 1.28 ms); linear 1.95 ms (0.41), its
 // half-line (64-B) store pieces being the cost; four linear tiles of neighbouring strips per work item,
 // which complete the lines within one workgroup but still store them in halves, 1.81 ms.
+// The walk from a work item to its texels (pack_item_texel) and Hd (evolve_rate) are device/evolve.h's,
+// shared with k_kinematics_pack; the shape rule on the host is pack_shape (launch_common.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -35,21 +37,6 @@ namespace oceanfft
 {
 
 constexpr int kRatesTile = 256;  // texels per work item = threads per workgroup
-
-// dH/dt of one texel: D = a.xy (c + i s) - a.zw (c - i s), Hd = i w D
-__device__ __forceinline__ float2 evolve_rate(float4 a, float k, const CascadeFrame& f)
-{
-#pragma clang fp contract(off)  // the frame's own w and phase bits, as in evolve()
-  const float w = dispersion_evolve(k, f.g, f.h);
-  float ws, wc;
-  sincos_phase(w * f.time, &ws, &wc);
-  const float ampx = a.x * wc - a.y * ws;
-  const float ampy = a.x * ws + a.y * wc;
-  const float oppx = a.z * wc + a.w * ws;
-  const float oppy = a.w * wc - a.z * ws;
-  const float dx = ampx - oppx, dy = ampy - oppy;
-  return make_float2(-(w * dy), w * dx);
-}
 
 // rates: [cascade][height-rate image, displacement-rate image][n * n], row-major, still in k space
 // (the batched EncodeIFFT follows). items = cascades * n * n / (BLOCK ? 1024 : 256); lcw = log2 CW.
@@ -71,26 +58,8 @@ __global__ __launch_bounds__(kRatesTile) void k_rates_pack(FrameParams fp, int l
     int x[J], y[J];
     float4 a[J];
 #pragma unroll
-    for (int j = 0; j < J; j++)
-    {
-      unsigned t;  // texel of the blocked image, < 2^28
-      if constexpr (BLOCK)
-      {
-        // consecutive items go down a block column: lrows = log2 of the block rows per image
-        const int lrows = logn - (10 - lcw);
-        const unsigned br = local & ((1u << lrows) - 1), bc = local >> lrows, e = 256u * j + threadIdx.x;
-        x[j] = (int)((bc << lcw) + (e & ((1u << lcw) - 1)));
-        y[j] = (int)((br << (10 - lcw)) + (e >> lcw));
-        t = (((unsigned)x[j] >> logb) << (logn + logb)) + ((unsigned)y[j] << logb) + ((unsigned)x[j] & ((1u << logb) - 1));
-      }
-      else
-      {
-        t = (local << 8) + threadIdx.x;
-        x[j] = (int)(((t >> (logb + logn)) << logb) + (t & ((1u << logb) - 1)));
-        y[j] = (int)((t >> logb) & (unsigned)(n - 1));
-      }
-      a[j] = hc[t];
-    }
+    for (int j = 0; j < J; j++)  // every load issued before the first use
+      a[j] = hc[pack_item_texel<BLOCK>(local, j, n, logn, logb, lcw, x[j], y[j])];
     const CascadeFrame f = fp.c[c];
     float4* oc = rates + (size_t)c * 2 * nn;
 #pragma unroll

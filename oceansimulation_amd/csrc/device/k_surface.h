@@ -1,7 +1,7 @@
 // device/k_surface.h — the point kernels of the surface consumer: the atlas repack,
 // ocean_surface_sample[_plane] (k_surface), ocean_surface_query, ocean_surface_velocity and the
 // footprint-aware ocean_surface_sample[_plane]_lod (include/oceanfft.h). One thread per point, item loops
-// on the grid of launch_surface.hip's launch_points.
+// on the grid of launch_common.h's launch_points.
 //
 // resources/waveShader.glsl evaluated per mesh vertex on the generator's maps. Vertex stage (:101-110):
 // each cascade samples heightMap/displacementMap at pos.xz / planeSize, the position the earlier cascades

@@ -57,6 +57,37 @@ __device__ __forceinline__ void swap_lane_bit_perm(float& lo, float& hi)
   hi = __uint_as_float(b);
 }
 
+// The exchange of a wave fold (fold64 of device/k_hulls.h, the minima and maxima of device/k_bounds.h):
+// a and b become v and the value of lane (lane ^ STRIDE), for the caller to combine as a + b, min(a, b), ...
+// Strides 32 and 16 swap with lo = hi = v, which leaves a lane's own value in one of the two and its
+// partner's in the other, (a, b) = (lo, hi): which is which differs between the two halves of the pair.
+// Strides 8 to 1 give a = v and b = the partner's, by two bank-masked row shifts or one quad_perm. The
+// exchanges read the registers of lanes whatever EXEC says: callers keep the whole wave active.
+template <int STRIDE>
+__device__ __forceinline__ void xor_lane_pair(float v, float& a, float& b)
+{
+  if constexpr (STRIDE == 32 || STRIDE == 16)
+  {
+    a = v;
+    b = v;
+    swap_lane_bit_perm<STRIDE == 32 ? 5 : 4>(a, b);
+  }
+  else if constexpr (STRIDE == 8 || STRIDE == 4)
+  {
+    constexpr int SET = STRIDE == 4 ? 0xA : 0xC, CLEAR = STRIDE == 4 ? 0x5 : 0x3;  // as swap_lane_bit_dpp
+    const float t = dpp_update<0x110 + STRIDE, SET>(v, v);  // lanes with the bit: lane - STRIDE
+    a = v;
+    b = dpp_update<0x100 + STRIDE, CLEAR>(t, v);  // lanes without it: lane + STRIDE
+  }
+  else
+  {
+    static_assert(STRIDE == 2 || STRIDE == 1, "a power of two below 64");
+    constexpr int QUAD = STRIDE == 2 ? 0x4E : 0xB1;  // quad_perm:[2,3,0,1] / [1,0,3,2]
+    a = v;
+    b = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), QUAD, 0xF, 0xF, false));
+  }
+}
+
 template <int LB>
 __device__ __forceinline__ void swap_lane_bit_f(float& lo, float& hi)
 {

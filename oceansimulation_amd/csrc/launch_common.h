@@ -1,12 +1,16 @@
 // launch_common.h — host-side launch helpers shared by the kernel translation units: dispatch on
-// log2 N, and grid sizing (one-shot grids on the whole device, persistent grids under a CU budget).
+// log2 N, grid sizing (one-shot grids on the whole device, persistent grids under a CU budget), the grid
+// of the kernels with one thread per element, and the shape rule of the packed-image kernels.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <mutex>
 #include <type_traits>
 #include <vector>
+
+#include "ocean_internal.h"
 
 namespace oceanfft
 {
@@ -116,6 +120,48 @@ int persistent_grid(K kernel, int wg, int lds, int items, int cus)
     return items < 1 ? 1 : items;
   }
   return resident_grid(kernel, wg, lds, items, cus);
+}
+
+// A kernel with one thread per element over `count` elements (points, records, pixels; k_particles_move's
+// items of `threads` particles): ceil(count / threads) workgroups of `threads`, at most cus * 8, and the
+// kernel's stride loop takes the rest. Nothing to do is no error. Where the count stays on the device the
+// callers size the grid from the capacity.
+template <typename K, typename... Args>
+hipError_t launch_points(K kernel, int threads, int64_t count, hipStream_t stream, int cus, const Args&... args)
+{
+  if (count <= 0)
+    return hipSuccess;
+  long blocks = (long)((count + threads - 1) / threads);
+  const long cap = (long)cus * 8;
+  if (blocks > cap)
+    blocks = cap;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3((unsigned)threads), 0, stream, args...);
+  return hipGetLastError();
+}
+
+// The shape of k_rates_pack and k_kinematics_pack (device/k_rates.h) for an N = 2^logn image whose h0 is
+// blocked in strips of h0_blk columns: the block shape wherever its CW x 1024 / CW block fits the image,
+// every N >= 64, the linear one below.
+struct PackShape
+{
+  int logb;    // log2 of h0_blk
+  int lcw;     // log2 CW, CW = min(max(4 B, 8), 64)
+  bool block;  // the BLOCK instantiation
+  int items;   // cascades * N^2 / (block ? 1024 : 256) <= 64 * 2^20
+};
+
+inline hipError_t pack_shape(int logn, int h0_blk, int cascades, PackShape& s)
+{
+  s.logb = 0;
+  while ((1 << s.logb) < h0_blk)
+    s.logb++;
+  if (logn < 4 || logn > 14 || h0_blk < 1 || (1 << s.logb) != h0_blk || s.logb > logn || cascades < 1 ||
+      cascades > kMaxCascades)
+    return hipErrorInvalidValue;
+  s.lcw = s.logb + 2 < 3 ? 3 : (s.logb + 2 > 6 ? 6 : s.logb + 2);
+  s.block = s.lcw <= logn && 10 - s.lcw <= logn;
+  s.items = cascades << (2 * logn - (s.block ? 10 : 8));
+  return hipSuccess;
 }
 
 }  // namespace oceanfft

@@ -1,7 +1,9 @@
 // launch_particles.hip — spray particles (device/k_particles.h): three launches per step, the move with the
 // fates of every item, the scan over the items with the count table, and the scatter with the append; the
-// kernel boundaries are the ordering between them.
+// kernel boundaries are the ordering between them. The move and the scatter run on launch_points' grid
+// (launch_common.h).
 #include "device/k_particles.h"
+#include "launch_common.h"
 #include "ocean_internal.h"
 
 namespace oceanfft
@@ -32,22 +34,16 @@ hipError_t launch_particles_step(const ParticleCall& c, const SurfaceParams& p, 
       (c.landed_capacity > 0 && !c.landed_out) || (c.emit && !c.emit_counts) || p.count < 1 ||
       p.count > kMaxSurfaceCascades)
     return hipErrorInvalidValue;
-  // an item per workgroup on at most cus * 8 workgroups (launch_surface.hip's launch_points), sized from the
-  // capacity: the count stays on the device
-  long blocks = (long)particle_items(c.capacity);
-  if (blocks > (long)cus * 8)
-    blocks = (long)cus * 8;
-  if (blocks < 1)
-    blocks = 1;
-  hipError_t e = hipSuccess;
-  hipLaunchKernelGGL(k_particles_move, dim3((unsigned)blocks), dim3(kParticleThreads), 0, stream, c, p);
-  if ((e = hipGetLastError()) != hipSuccess)
+  // an item per workgroup (launch_points, launch_common.h), sized from the capacity: the count stays on the
+  // device
+  static_assert(kParticleItem == kParticleThreads, "one particle per thread of an item");
+  hipError_t e = launch_points(k_particles_move, kParticleThreads, c.capacity, stream, cus, c, p);
+  if (e != hipSuccess)
     return e;
   hipLaunchKernelGGL(k_particles_scan, dim3(1), dim3(kParticleScanThreads), 0, stream, c);
   if ((e = hipGetLastError()) != hipSuccess)
     return e;
-  hipLaunchKernelGGL(k_particles_scatter, dim3((unsigned)blocks), dim3(kParticleThreads), 0, stream, c);
-  return hipGetLastError();
+  return launch_points(k_particles_scatter, kParticleThreads, c.capacity, stream, cus, c);
 }
 
 hipError_t launch_particles_reset(int64_t* table, int64_t alive, hipStream_t stream)

@@ -1,6 +1,7 @@
 // launch_spray.hip — spray emitters (device/k_spray.h): at most four launches per call, the count of every
 // item, the scan over the items with the count table, and with a capacity the scatter of (d, id) and the
-// dense fill of the records; the kernel boundaries are the ordering between them.
+// dense fill of the records (on launch_points' grid, launch_common.h); the kernel boundaries are the ordering
+// between them.
 #include "device/k_spray.h"
 #include "launch_common.h"
 #include "ocean_internal.h"
@@ -47,18 +48,12 @@ hipError_t launch_spray_emit(const SprayCall& s, const SurfaceParams& p, const S
     if ((e = hipGetLastError()) != hipSuccess)
       return e;
   }
-  // a thread per record on at most cus * 8 workgroups (launch_surface.hip's launch_points), sized from the
-  // capacity: the count stays on the device
-  long blocks = (long)((s.capacity + kSprayThreads - 1) / kSprayThreads);
-  if (blocks > (long)cus * 8)
-    blocks = (long)cus * 8;
+  // a thread per record (launch_points, launch_common.h), sized from the capacity: the count stays on the device
   if (velocity)
-    hipLaunchKernelGGL(k_spray_fill<true>, dim3((unsigned)blocks), dim3(kSprayThreads), 0, stream, p, r, tiles,
+    return launch_points(k_spray_fill<true>, kSprayThreads, s.capacity, stream, cus, p, r, tiles,
+                         (const int64_t*)s.table, s.logn, s.out);
+  return launch_points(k_spray_fill<false>, kSprayThreads, s.capacity, stream, cus, p, r, tiles,
                        (const int64_t*)s.table, s.logn, s.out);
-  else
-    hipLaunchKernelGGL(k_spray_fill<false>, dim3((unsigned)blocks), dim3(kSprayThreads), 0, stream, p, r, tiles,
-                       (const int64_t*)s.table, s.logn, s.out);
-  return hipGetLastError();
 }
 
 }  // namespace oceanfft

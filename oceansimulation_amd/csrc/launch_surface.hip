@@ -1,9 +1,10 @@
 // launch_surface.hip — the point kernels of the surface consumer (device/k_surface.h): the atlas repack,
 // ocean_surface_sample[_plane], _sample[_plane]_foam, _query, _velocity and _sample[_plane]_lod, and the rules that decide when a
-// request samples the atlas.
+// request samples the atlas. The point kernels run on launch_points' grid (launch_common.h).
 #include <cstdint>
 
 #include "device/k_surface.h"
+#include "launch_common.h"
 #include "ocean_internal.h"
 
 namespace oceanfft
@@ -19,30 +20,15 @@ void launch_surface_atlas(const SurfaceParams& p, hipStream_t stream, int cus)
   hipLaunchKernelGGL(k_surface_atlas, dim3((unsigned)ab), dim3(256), 0, stream, p);
 }
 
-// A point kernel over `count` points: one thread per point on at most cus * 8 workgroups of 256, the item
-// loop takes the rest.
-template <typename K, typename... Args>
-static hipError_t launch_points(K kernel, int64_t count, hipStream_t stream, int cus, const Args&... args)
-{
-  if (count <= 0)
-    return hipSuccess;
-  long blocks = (long)((count + 255) / 256);
-  const long cap = (long)cus * 8;
-  if (blocks > cap)
-    blocks = cap;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, stream, args...);
-  return hipGetLastError();
-}
-
-// The same for a kernel with an atlas and a direct instantiation: p.atlas non-null runs the repack, then
-// the atlas one.
+// launch_points (launch_common.h, workgroups of 256) for a kernel with an atlas and a direct instantiation:
+// p.atlas non-null runs the repack, then the atlas one.
 template <typename K, typename... Args>
 static hipError_t launch_points_atlas(K atlas, K direct, const SurfaceParams& p, int64_t count, hipStream_t stream,
                                       int cus, const Args&... args)
 {
   if (p.atlas && count > 0)
     launch_surface_atlas(p, stream, cus);
-  return launch_points(p.atlas ? atlas : direct, count, stream, cus, p, args...);
+  return launch_points(p.atlas ? atlas : direct, 256, count, stream, cus, p, args...);
 }
 
 hipError_t launch_surface(const SurfaceParams& p, const SurfacePlane& plane, const float2* xz, int64_t count,
@@ -54,7 +40,7 @@ hipError_t launch_surface(const SurfaceParams& p, const SurfacePlane& plane, con
 hipError_t launch_surface_foam(const SurfaceParams& p, const SurfaceFoam& f, const SurfacePlane& plane, const float2* xz,
                                int64_t count, float4* out, hipStream_t stream, int cus)
 {
-  return launch_points(k_surface_foam, count, stream, cus, p, f, plane, xz, count, out);
+  return launch_points(k_surface_foam, 256, count, stream, cus, p, f, plane, xz, count, out);
 }
 
 hipError_t launch_surface_query(const SurfaceParams& p, const float2* xz, int64_t count, int iterations,
@@ -67,13 +53,13 @@ hipError_t launch_surface_query(const SurfaceParams& p, const float2* xz, int64_
 hipError_t launch_surface_velocity(const SurfaceParams& p, const SurfaceRates& r, const float2* xz, int64_t count,
                                    float4* out, hipStream_t stream, int cus)
 {
-  return launch_points(k_surface_velocity, count, stream, cus, p, r, xz, count, out);
+  return launch_points(k_surface_velocity, 256, count, stream, cus, p, r, xz, count, out);
 }
 
 hipError_t launch_surface_lod(const SurfaceParams& p, const SurfacePlane& plane, const float* xzf, int64_t count,
                               float4* out, hipStream_t stream, int cus)
 {
-  return launch_points(k_surface_lod, count, stream, cus, p, plane, xzf, count, out);
+  return launch_points(k_surface_lod, 256, count, stream, cus, p, plane, xzf, count, out);
 }
 
 size_t surface_atlas_texels(const SurfaceParams& p) { return (size_t)2 * p.count * p.n * p.n; }

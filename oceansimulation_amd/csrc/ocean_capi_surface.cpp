@@ -93,6 +93,63 @@ int plane_request(const float camera[5], int res, const float* out, const std::s
   return OCEAN_OK;
 }
 
+int check_dt(float dt, const std::string& who)
+{
+  if (!(dt >= 0.0f) || !std::isfinite(dt))
+    return fail(OCEAN_ERR_INVALID, who + ": dt must be finite and >= 0");
+  return OCEAN_OK;
+}
+
+// A request's generators run on the plan of the object it uses (`what`: the hull set, the emitter, the pool)
+int same_plan(const ocean_generator* first, const ocean_fft* fft, const char* what, const std::string& who)
+{
+  if (first->fft != fft)
+    return fail(OCEAN_ERR_INVALID, who + ": the first generator is on another plan than the " + what);
+  return OCEAN_OK;
+}
+
+// Every pair of a request (its surface_params passed) holds whole maps with a frame calculated
+int frames_calculated(ocean_generator* const* gens, int count, const std::string& who)
+{
+  for (int i = 0; i < count; i++)
+  {
+    if (gens[i]->slab)
+      return fail(OCEAN_ERR_INVALID,
+                  who + ": generator " + std::to_string(i) + " is a slab generator: row slabs, not whole maps");
+    if (gens[i]->frame.cascades != gens[i]->cascades)
+      return fail(OCEAN_ERR_INVALID, who + ": generator " + std::to_string(i) +
+                                         " has no frame calculated yet (ocean_generator_calculate)");
+  }
+  return OCEAN_OK;
+}
+
+// A few words of device memory to the host, complete on return
+int read_back(void* out, const void* device, size_t bytes, const ocean_fft* fft, const char* who)
+{
+  HIP_TRY(hipMemcpyAsync(out, device, bytes, hipMemcpyDeviceToHost, fft->stream), who);
+  HIP_TRY(hipStreamSynchronize(fft->stream), who);
+  return OCEAN_OK;
+}
+
+// The march of a ray cast or a render (its rules: check_march)
+void set_march(RaycastParams& r, const ocean_march& m)
+{
+  r.step = m.step;
+  r.max_steps = m.max_steps;
+  r.refine = m.refine;
+  r.iterations = m.iterations;
+  r.tolerance = m.tolerance;
+  r.slope = m.slope;
+  r.pad = m.pad;
+}
+
+// The refusal of an entry point that returns a pointer: the message is set, the result is null
+std::nullptr_t fail_null(const std::string& msg)
+{
+  fail(OCEAN_ERR_INVALID, msg);
+  return nullptr;
+}
+
 // Generator i of a request lacks the data `builder` makes (none / stale: the two wordings up to its name)
 int not_fresh(const std::string& who, int i, bool have, const char* none, const char* stale, const char* builder)
 {
@@ -240,23 +297,14 @@ int ocean_generator_build_mips(ocean_generator* g)
 static float* generator_mip(ocean_generator* g, int c, int level, int map, const char* who)
 {
   if (!g || c < 0 || c >= g->cascades)
-  {
-    fail(OCEAN_ERR_INVALID, std::string(who) + ": null generator or cascade out of range");
-    return nullptr;
-  }
+    return fail_null(std::string(who) + ": null generator or cascade out of range");
   if (level < 0 || level > g->fft->logn)
-  {
-    fail(OCEAN_ERR_INVALID, std::string(who) + ": level outside 0..log2(N)");
-    return nullptr;
-  }
+    return fail_null(std::string(who) + ": level outside 0..log2(N)");
   if (level == 0)
     return map == 0 ? ocean_generator_height_map(g, c)
                     : (map == 1 ? ocean_generator_displacement_map(g, c) : ocean_generator_jacobian_map(g, c));
   if (!g->mips)
-  {
-    fail(OCEAN_ERR_INVALID, std::string(who) + ": the pyramid was never built (ocean_generator_build_mips)");
-    return nullptr;
-  }
+    return fail_null(std::string(who) + ": the pyramid was never built (ocean_generator_build_mips)");
   const int n = g->fft->n;
   const size_t chain = mip_chain_texels(n), off = mip_level_offset(n, level);
   float* base = g->mips + (size_t)c * mip_cascade_floats(n);
@@ -346,15 +394,9 @@ int ocean_generator_calculate_rates(ocean_generator* g)
 static float* generator_rate_map(ocean_generator* g, int c, int image, const char* who)
 {
   if (!g || c < 0 || c >= g->cascades)
-  {
-    fail(OCEAN_ERR_INVALID, std::string(who) + ": null generator or cascade out of range");
-    return nullptr;
-  }
+    return fail_null(std::string(who) + ": null generator or cascade out of range");
   if (!g->rates)
-  {
-    fail(OCEAN_ERR_INVALID, std::string(who) + ": the rates were never calculated (ocean_generator_calculate_rates)");
-    return nullptr;
-  }
+    return fail_null(std::string(who) + ": the rates were never calculated (ocean_generator_calculate_rates)");
   return reinterpret_cast<float*>(g->rates + (size_t)g->fft->n * g->fft->n * (2 * c + image));
 }
 
@@ -459,21 +501,12 @@ float* ocean_generator_kinematics_map(ocean_generator* g, int c, int layer, int 
 {
   const char* who = "ocean_generator_kinematics_map";
   if (!g || c < 0 || c >= g->cascades)
-  {
-    fail(OCEAN_ERR_INVALID, std::string(who) + ": null generator or cascade out of range");
-    return nullptr;
-  }
+    return fail_null(std::string(who) + ": null generator or cascade out of range");
   if (!g->kin)
-  {
-    fail(OCEAN_ERR_INVALID,
-         std::string(who) + ": the depth layers were never calculated (ocean_generator_calculate_kinematics)");
-    return nullptr;
-  }
+    return fail_null(std::string(who) +
+                     ": the depth layers were never calculated (ocean_generator_calculate_kinematics)");
   if (layer < 0 || layer >= g->depths.layers || image < 0 || image > 1)
-  {
-    fail(OCEAN_ERR_INVALID, std::string(who) + ": layer or image out of range");
-    return nullptr;
-  }
+    return fail_null(std::string(who) + ": layer or image out of range");
   const size_t nn = (size_t)g->fft->n * g->fft->n;
   return reinterpret_cast<float*>(g->kin + nn * (((size_t)c * g->depths.layers + layer) * 2 + image));
 }
@@ -529,17 +562,11 @@ int ocean_generator_build_bounds(ocean_generator* g)
 static const float* generator_bounds(ocean_generator* g, const char* who)
 {
   if (!g)
-  {
-    fail(OCEAN_ERR_INVALID, std::string(who) + ": null generator");
-    return nullptr;
-  }
+    return fail_null(std::string(who) + ": null generator");
   if (!g->bounds || !g->bounds_fresh)
-  {
-    fail(OCEAN_ERR_INVALID, std::string(who) + (g->bounds ? ": the bounds are stale (the maps were rewritten since"
-                                                           : ": the bounds were never built (call") +
-                                " ocean_generator_build_bounds)");
-    return nullptr;
-  }
+    return fail_null(std::string(who) + (g->bounds ? ": the bounds are stale (the maps were rewritten since"
+                                                   : ": the bounds were never built (call") +
+                     " ocean_generator_build_bounds)");
   return g->bounds;
 }
 
@@ -555,10 +582,7 @@ int ocean_generator_bounds(ocean_generator* g, int cascade, float out[18])
     return OCEAN_ERR_INVALID;
   if (cascade < 0 || cascade >= g->cascades || !out)
     return fail(OCEAN_ERR_INVALID, "ocean_generator_bounds: cascade out of range or null output");
-  HIP_TRY(hipMemcpyAsync(out, table + (size_t)cascade * 18, 18 * sizeof(float), hipMemcpyDeviceToHost, g->fft->stream),
-          "ocean_generator_bounds");
-  HIP_TRY(hipStreamSynchronize(g->fft->stream), "ocean_generator_bounds");
-  return OCEAN_OK;
+  return read_back(out, table + (size_t)cascade * 18, 18 * sizeof(float), g->fft, "ocean_generator_bounds");
 }
 
 // The bounds rows of a request's cascades, which must be built and not older than the maps
@@ -591,13 +615,7 @@ int ocean_surface_raycast(ocean_generator* const* gens, const int* cascades, int
   TRY(surface_params(gens, cascades, count, p, fft, "ocean_surface_raycast"));
   RaycastParams r{};
   TRY(surface_bounds_rows(gens, cascades, count, r, "ocean_surface_raycast"));
-  r.step = step;
-  r.max_steps = max_steps;
-  r.refine = refine;
-  r.iterations = iterations;
-  r.tolerance = tolerance;
-  r.slope = slope;
-  r.pad = pad;
+  set_march(r, ocean_march{step, max_steps, refine, iterations, tolerance, slope, pad});
   HIP_TRY(launch_surface_raycast(p, r, reinterpret_cast<const float4*>(rays), n_rays, reinterpret_cast<float4*>(out),
                                  fft->stream, fft->cus),
           "ocean_surface_raycast");
@@ -748,13 +766,7 @@ static int camera_scene(ocean_generator* const* gens, const int* cascades, int c
     TRY(surface_params(gens, cascades, count, p, fft, who.c_str()));
   r = RaycastParams{};
   TRY(surface_bounds_rows(gens, cascades, count, r, who.c_str()));
-  r.step = march->step;
-  r.max_steps = march->max_steps;
-  r.refine = march->refine;
-  r.iterations = march->iterations;
-  r.tolerance = march->tolerance;
-  r.slope = march->slope;
-  r.pad = march->pad;
+  set_march(r, *march);
   return OCEAN_OK;
 }
 
@@ -788,10 +800,7 @@ void ocean_default_foam_settings(ocean_foam_settings* s)
 ocean_foam_settings* ocean_generator_foam_settings(ocean_generator* g, int c)
 {
   if (!g || c < 0 || c >= g->cascades)
-  {
-    fail(OCEAN_ERR_INVALID, "ocean_generator_foam_settings: null generator or cascade out of range");
-    return nullptr;
-  }
+    return fail_null("ocean_generator_foam_settings: null generator or cascade out of range");
   return &g->foam_settings[c];
 }
 
@@ -830,8 +839,7 @@ int ocean_generator_advance_foam(ocean_generator* g, float dt)
 {
   const std::string who = "ocean_generator_advance_foam";
   TRY(whole_maps(g, true, who));
-  if (!(dt >= 0.0f) || !std::isfinite(dt))
-    return fail(OCEAN_ERR_INVALID, who + ": dt must be finite and >= 0");
+  TRY(check_dt(dt, who));
   FoamCascade fc[kMaxCascades];
   for (int c = 0; c < g->cascades; c++)
   {
@@ -865,16 +873,10 @@ int ocean_generator_reset_foam(ocean_generator* g)
 static ocean_generator* generator_foam(ocean_generator* g, const char* who)
 {
   if (!g)
-  {
-    fail(OCEAN_ERR_INVALID, std::string(who) + ": null generator");
-    return nullptr;
-  }
+    return fail_null(std::string(who) + ": null generator");
   if (!g->foam)
-  {
-    fail(OCEAN_ERR_INVALID, std::string(who) + ": the generator has no foam yet (call ocean_generator_advance_foam or "
-                                               "ocean_generator_reset_foam)");
-    return nullptr;
-  }
+    return fail_null(std::string(who) + ": the generator has no foam yet (call ocean_generator_advance_foam or "
+                                        "ocean_generator_reset_foam)");
   return g;
 }
 
@@ -883,10 +885,7 @@ float* ocean_generator_foam_map(ocean_generator* g, int c)
   if (!generator_foam(g, "ocean_generator_foam_map"))
     return nullptr;
   if (c < 0 || c >= g->cascades)
-  {
-    fail(OCEAN_ERR_INVALID, "ocean_generator_foam_map: cascade out of range");
-    return nullptr;
-  }
+    return fail_null("ocean_generator_foam_map: cascade out of range");
   return g->foam + (size_t)g->fft->n * g->fft->n * c;
 }
 
@@ -901,11 +900,8 @@ int ocean_generator_foam_counts(ocean_generator* g, int cascade, int64_t out[3])
     return OCEAN_ERR_INVALID;
   if (cascade < 0 || cascade >= g->cascades || !out)
     return fail(OCEAN_ERR_INVALID, "ocean_generator_foam_counts: cascade out of range or null output");
-  HIP_TRY(hipMemcpyAsync(out, static_cast<const int64_t*>(g->foam_counts) + (size_t)cascade * 3, 3 * sizeof(int64_t),
-                         hipMemcpyDeviceToHost, g->fft->stream),
-          "ocean_generator_foam_counts");
-  HIP_TRY(hipStreamSynchronize(g->fft->stream), "ocean_generator_foam_counts");
-  return OCEAN_OK;
+  return read_back(out, static_cast<const int64_t*>(g->foam_counts) + (size_t)cascade * 3, 3 * sizeof(int64_t), g->fft,
+                   "ocean_generator_foam_counts");
 }
 
 // The foam maps of a request's cascades: every generator must have foam storage
@@ -1229,8 +1225,7 @@ int ocean_hulls_loads(ocean_hulls* h, ocean_generator* const* gens, const int* c
   SurfaceParams p;
   ocean_fft* fft;
   TRY(surface_params(gens, cascades, count, p, fft, "ocean_hulls_loads"));
-  if (gens[0]->fft != h->fft)
-    return fail(OCEAN_ERR_INVALID, "ocean_hulls_loads: the first generator is on another plan than the hull set");
+  TRY(same_plan(gens[0], h->fft, "hull set", "ocean_hulls_loads"));
   TRY(check_fixed_point(iterations, tolerance, "ocean_hulls_loads"));
   if (!(rho_g >= 0.0f) || !std::isfinite(rho_g))
     return fail(OCEAN_ERR_INVALID, "ocean_hulls_loads: rho_g must be finite and >= 0");
@@ -1312,8 +1307,7 @@ int ocean_spray_emit(ocean_spray* spray, ocean_generator* const* gens, const int
     return fail(OCEAN_ERR_INVALID, who + ": null settings");
   if (capacity < 0 || (capacity > 0 && !out))
     return fail(OCEAN_ERR_INVALID, who + ": negative capacity, or null output with capacity > 0");
-  if (!(dt >= 0.0f) || !std::isfinite(dt))
-    return fail(OCEAN_ERR_INVALID, who + ": dt must be finite and >= 0");
+  TRY(check_dt(dt, who));
   for (int i = 0; i < count; i++)
   {
     if (!std::isfinite(settings[i].threshold))
@@ -1324,17 +1318,8 @@ int ocean_spray_emit(ocean_spray* spray, ocean_generator* const* gens, const int
   SurfaceParams p;
   ocean_fft* fft;
   TRY(surface_params(gens, cascades, count, p, fft, who.c_str()));
-  if (gens[0]->fft != spray->fft)
-    return fail(OCEAN_ERR_INVALID, who + ": the first generator is on another plan than the emitter");
-  for (int i = 0; i < count; i++)
-  {
-    if (gens[i]->slab)
-      return fail(OCEAN_ERR_INVALID,
-                  who + ": generator " + std::to_string(i) + " is a slab generator: row slabs, not whole maps");
-    if (gens[i]->frame.cascades != gens[i]->cascades)
-      return fail(OCEAN_ERR_INVALID, who + ": generator " + std::to_string(i) +
-                                         " has no frame calculated yet (ocean_generator_calculate)");
-  }
+  TRY(same_plan(gens[0], spray->fft, "emitter", who));
+  TRY(frames_calculated(gens, count, who));
   SurfaceRates r{};
   if (velocity)
     TRY(surface_rates(gens, cascades, count, fft, r, who.c_str()));
@@ -1368,15 +1353,9 @@ int ocean_spray_emit(ocean_spray* spray, ocean_generator* const* gens, const int
 static ocean_spray* spray_emitted(ocean_spray* s, const char* who)
 {
   if (!s)
-  {
-    fail(OCEAN_ERR_INVALID, std::string(who) + ": null emitter");
-    return nullptr;
-  }
+    return fail_null(std::string(who) + ": null emitter");
   if (!s->scratch)
-  {
-    fail(OCEAN_ERR_INVALID, std::string(who) + ": the emitter has no counts yet (call ocean_spray_emit)");
-    return nullptr;
-  }
+    return fail_null(std::string(who) + ": the emitter has no counts yet (call ocean_spray_emit)");
   return s;
 }
 
@@ -1391,10 +1370,7 @@ int ocean_spray_counts(ocean_spray* s, int64_t out[18])
     return OCEAN_ERR_INVALID;
   if (!out)
     return fail(OCEAN_ERR_INVALID, "ocean_spray_counts: null output");
-  HIP_TRY(hipMemcpyAsync(out, s->scratch, 18 * sizeof(int64_t), hipMemcpyDeviceToHost, s->fft->stream),
-          "ocean_spray_counts");
-  HIP_TRY(hipStreamSynchronize(s->fft->stream), "ocean_spray_counts");
-  return OCEAN_OK;
+  return read_back(out, s->scratch, 18 * sizeof(int64_t), s->fft, "ocean_spray_counts");
 }
 
 // ---- spray particles: a persistent pool, stepped, landed on the water, compacted in order ----
@@ -1463,8 +1439,7 @@ int ocean_particles_step(ocean_particles* pool, ocean_generator* const* gens, co
     return fail(OCEAN_ERR_INVALID, who + ": need 1..16 (generator, cascade) pairs");
   if (!settings)
     return fail(OCEAN_ERR_INVALID, who + ": null settings");
-  if (!(dt >= 0.0f) || !std::isfinite(dt))
-    return fail(OCEAN_ERR_INVALID, who + ": dt must be finite and >= 0");
+  TRY(check_dt(dt, who));
   const ocean_particle_settings& s = *settings;
   if (!std::isfinite(s.gravity))
     return fail(OCEAN_ERR_INVALID, who + ": non-finite gravity");
@@ -1486,17 +1461,8 @@ int ocean_particles_step(ocean_particles* pool, ocean_generator* const* gens, co
   SurfaceParams p;
   ocean_fft* fft;
   TRY(surface_params(gens, cascades, count, p, fft, who.c_str()));
-  if (gens[0]->fft != pool->fft)
-    return fail(OCEAN_ERR_INVALID, who + ": the first generator is on another plan than the pool");
-  for (int i = 0; i < count; i++)
-  {
-    if (gens[i]->slab)
-      return fail(OCEAN_ERR_INVALID,
-                  who + ": generator " + std::to_string(i) + " is a slab generator: row slabs, not whole maps");
-    if (gens[i]->frame.cascades != gens[i]->cascades)
-      return fail(OCEAN_ERR_INVALID, who + ": generator " + std::to_string(i) +
-                                         " has no frame calculated yet (ocean_generator_calculate)");
-  }
+  TRY(same_plan(gens[0], pool->fft, "pool", who));
+  TRY(frames_calculated(gens, count, who));
   ParticleCall c{};
   particle_scratch(pool->scratch, pool->capacity, c);
   c.cur = pool->list[pool->current];
@@ -1550,20 +1516,14 @@ int ocean_particles_clear(ocean_particles* pool)
 const float* ocean_particles_records(ocean_particles* pool)
 {
   if (!pool)
-  {
-    fail(OCEAN_ERR_INVALID, "ocean_particles_records: null pool");
-    return nullptr;
-  }
+    return fail_null("ocean_particles_records: null pool");
   return pool->list[pool->current];
 }
 
 const int64_t* ocean_particles_counts_device(ocean_particles* pool)
 {
   if (!pool)
-  {
-    fail(OCEAN_ERR_INVALID, "ocean_particles_counts_device: null pool");
-    return nullptr;
-  }
+    return fail_null("ocean_particles_counts_device: null pool");
   return static_cast<const int64_t*>(pool->scratch);
 }
 
@@ -1573,10 +1533,7 @@ int ocean_particles_counts(ocean_particles* pool, int64_t out[8])
     return fail(OCEAN_ERR_INVALID, "ocean_particles_counts: null pool");
   if (!out)
     return fail(OCEAN_ERR_INVALID, "ocean_particles_counts: null output");
-  HIP_TRY(hipMemcpyAsync(out, pool->scratch, 8 * sizeof(int64_t), hipMemcpyDeviceToHost, pool->fft->stream),
-          "ocean_particles_counts");
-  HIP_TRY(hipStreamSynchronize(pool->fft->stream), "ocean_particles_counts");
-  return OCEAN_OK;
+  return read_back(out, pool->scratch, 8 * sizeof(int64_t), pool->fft, "ocean_particles_counts");
 }
 
 }  // extern "C"

@@ -353,7 +353,7 @@ def test_refusals(ocean):
     gen.CalculateOcean(DT)
     assert not L.ocean_generator_foam_map(gen.handle, 0)  # a frame is not foam storage
     for dt in (-0.1, float("nan"), float("inf")):
-        with pytest.raises(capi.OceanError, match="ocean_generator_advance_foam: dt"):
+        with pytest.raises(capi.OceanError, match="ocean_generator_advance_foam: dt must be finite and >= 0"):
             gen.AdvanceFoam(dt)
     for field, value in (("decay", -1.0), ("gain", -1.0), ("gain", float("inf")), ("bias", float("nan")),
                          ("level", float("inf"))):

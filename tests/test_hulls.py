@@ -390,7 +390,7 @@ def test_invalid_calls_fail_loudly(ocean):
         hulls.loads_host(SurfaceSampler([(gens[0], 0), (other, 0)]), poses)
     foreign = ocean.Generator(ocean.FFTCalculator(64), 1)  # the right size on another plan
     foreign.CalculateOcean(1.0)
-    with pytest.raises(OceanError, match="another plan"):
+    with pytest.raises(OceanError, match="ocean_hulls_loads: the first generator is on another plan than the hull set"):
         hulls.loads_host(SurfaceSampler([(foreign, 0)]), poses)
     with pytest.raises(OceanError, match="null poses"):
         hulls.loads(sampler, 0, 0)

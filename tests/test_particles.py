@@ -136,7 +136,8 @@ def test_rejected_arguments_name_the_call():
     cases = [(dict(pool=None), b"null pool"), (dict(gens=None), b"pairs"), (dict(cas=None), b"pairs"),
              (dict(count=0), b"pairs"), (dict(gens=g17, cas=c17, count=17), b"pairs"),
              (dict(settings=False), b"null settings"),
-             (dict(dt=-0.1), b"dt"), (dict(dt=nan), b"dt"), (dict(dt=inf), b"dt"),
+             (dict(dt=-0.1), b"dt must be finite and >= 0"), (dict(dt=nan), b"dt must be finite and >= 0"),
+             (dict(dt=inf), b"dt must be finite and >= 0"),
              (dict(gravity=nan), b"gravity"), (dict(gravity=inf), b"gravity"),
              (dict(wind=(0.0, nan, 0.0)), b"wind"), (dict(wind=(0.0, 0.0, -inf)), b"wind"), (dict(wind=(inf, 0.0, 0.0)), b"wind"),
              (dict(gain=nan), b"gain"), (dict(gain=-inf), b"gain"), (dict(lift=nan), b"lift"), (dict(lift=inf), b"lift"),
@@ -654,8 +655,13 @@ def test_refusals(ocean, scenes):
         pool.step(SurfaceSampler([(gens[0], 1)]), s, DT)
     other = ocean.FFTCalculator(64)
     elsewhere = SprayParticles(other, 8)
-    with pytest.raises(capi.OceanError, match="ocean_particles_step: the first generator is on another plan"):
+    with pytest.raises(capi.OceanError, match="ocean_particles_step: the first generator is on another plan than the pool"):
         elsewhere.step(sc.sampler, s, DT)
+    from oceansimulation_amd.slab import SlabGenerator
+    slab1 = SlabGenerator(sc.fft, 0, 1)  # one rank: whole-grid sized, yet its maps are a slab pipeline's
+    with pytest.raises(capi.OceanError,
+                       match="ocean_particles_step: generator 0 is a slab generator: row slabs, not whole maps"):
+        pool.step(SurfaceSampler([(slab1, 0)]), s, DT)
     small = ocean.FFTCalculator(32)
     g32 = ocean.Generator(small, 1)
     g32.CalculateOcean(DT)

@@ -106,7 +106,8 @@ def test_rejected_arguments_name_the_call():
     cases = [(dict(spray=None), b"null emitter"), (dict(gens=None), b"pairs"), (dict(cas=None), b"pairs"),
              (dict(count=0), b"pairs"), (dict(gens=g17, cas=c17, count=17), b"pairs"),
              (dict(settings=None), b"null settings"), (dict(capacity=-1), b"capacity"),
-             (dict(out=None), b"capacity"), (dict(dt=-0.1), b"dt"), (dict(dt=nan), b"dt"), (dict(dt=inf), b"dt"),
+             (dict(out=None), b"capacity"), (dict(dt=-0.1), b"dt must be finite and >= 0"),
+             (dict(dt=nan), b"dt must be finite and >= 0"), (dict(dt=inf), b"dt must be finite and >= 0"),
              (dict(settings=one_setting(nan, 8.0)), b"pair 0 has a non-finite threshold"),
              (dict(settings=one_setting(inf, 8.0)), b"pair 0 has a non-finite threshold"),
              (dict(settings=one_setting(1.0, -1.0)), b"pair 0 needs a rate"),
@@ -459,8 +460,13 @@ def test_refusals(ocean, scenes):
         fresh.emit(*args)
     other = ocean.FFTCalculator(64)
     elsewhere = SprayEmitter(other)
-    with pytest.raises(capi.OceanError, match="ocean_spray_emit: the first generator is on another plan"):
+    with pytest.raises(capi.OceanError, match="ocean_spray_emit: the first generator is on another plan than the emitter"):
         elsewhere.emit(*args, velocity=False)
+    from oceansimulation_amd.slab import SlabGenerator
+    slab1 = SlabGenerator(sc.fft, 0, 1)  # one rank: whole-grid sized, yet its maps are a slab pipeline's
+    with pytest.raises(capi.OceanError,
+                       match="ocean_spray_emit: generator 0 is a slab generator: row slabs, not whole maps"):
+        fresh.emit(SurfaceSampler([(slab1, 0)]), dict(rate=1.0), DT, STEP, velocity=False)
     small = ocean.FFTCalculator(32)
     g32 = ocean.Generator(small, 1)
     g32.CalculateOcean(DT)
