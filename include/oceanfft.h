@@ -974,6 +974,70 @@ int ocean_surface_sample_foam(ocean_generator* const* gens, const int* cascades,
 int ocean_surface_sample_plane_foam(ocean_generator* const* gens, const int* cascades, int count,
                                     const float camera[5], int res, float* out);
 
+/* ---- Foam deposit: spray impacts splatted into the persistent foam --------------------------------
+ * ocean_generator_advance_foam feeds the foam from the Jacobian alone. ocean_particles_step's impact list
+ * (landed_out: the point and velocity of every particle that hit the water, with its count on the device)
+ * says where spray comes down; ocean_foam_deposit adds foam there, without the host. The foam samplers and
+ * the camera's foam stage then see it with no change to any of them.
+ *
+ * Settings, per (generator, cascade) pair of a call. The defaults (0.05, 0.01) are starting points, not
+ * measurements.
+ *     amount     foam one impact adds, spread over the four texels around it
+ *     per_speed  (s/m) more foam per m/s of downward speed at the impact */
+typedef struct ocean_foam_deposit_settings {
+  float amount;
+  float per_speed;
+} ocean_foam_deposit_settings;
+void ocean_default_foam_deposit_settings(ocean_foam_deposit_settings* out);
+/* records: max_records x 8 floats in device memory, in the layout of landed_out; only slots 0, 2 and 5 are
+ * read (px, pz, uy). The number of records is n = min(*count_device, max_records), read on the device
+ * (a negative count is 0); a null count_device means n = max_records. For an impact list pass
+ * ocean_particles_counts_device(pool) + 4. settings: host, one per pair.
+ * Contract, in unfused fp32, per record r < n and per pair i in order, with L the pair's planeSize, F its
+ * foam map and s = settings[i]. The taps (o_k, w_k), k = 0..3, are the texels and weights with which the
+ * foam sampler reads F at the displaced position (px, pz): GL_LINEAR + GL_REPEAT at (px / L, pz / L). The
+ * deposit is the transpose of the sampler: it takes a world position, not a base point.
+ *     d   = s.amount + s.per_speed * max(-uy, 0.0f)        one product, one sum
+ *     m_k = min(d * w_k, 1.0f)
+ *     u_k = (uint64)(m_k * 16777216.0f)                    truncation; units of 2^-24, at most 2^24 per tap
+ *     A[i][o_k] += u_k                                     an integer sum over all records and taps
+ * and then for every texel t with A[i][t] > 0
+ *     F[t] = min(F[t] + (float)min(A[i][t], 2^24) * 0x1p-24f, 1.0f)
+ * Both conversions are exact and 2^28 records x 2^24 units cannot overflow 64 bits, so the result does not
+ * depend on the order of the records and a call replays bit for bit. A pair with amount == 0 and
+ * per_speed == 0 receives nothing and its map is not touched; texels without units keep their bits.
+ * Non-finite positions or velocities are unspecified; their taps still stay inside the maps.
+ * Counts: int64[50] in device memory owned by gens[0]:
+ *     [0] n   [1] offered (*count_device, or max_records when it is null)
+ *     [2 + 3i] taps with u_k > 0   [3 + 3i] texels touched   [4 + 3i] touched texels with F + add >= 1
+ * per pair i; the three values are 0 for i >= count.
+ * (generator, cascade) rules and stream as ocean_particles_step; every generator must have foam storage
+ * (ocean_surface_sample_foam's rule and message, naming the index in `gens`); two pairs may not name the same
+ * map. Three kernel launches: integer atomic adds into one uint64 accumulator per texel, an exchange that
+ * makes one lane the owner of each touched texel (so the work scales with the records, not with N * N), and
+ * the fold of the counts. No host synchronisation and no float atomics. The accumulators, 8 B per point and
+ * cascade of every generator with a depositing pair (1 GiB at 8 x 4096^2), and gens[0]'s counts are
+ * allocated and zeroed on the first call that needs them (OCEAN_ERR_OOM when that fails), are all zero
+ * between calls and are freed by ocean_generator_destroy; no allocation after that. It does not rewrite the
+ * generator's maps, so mips, rates and bounds stay fresh. max_records == 0 launches nothing and zeroes the
+ * counts.
+ * OCEAN_ERR_INVALID, before any device call: null gens / cascades / settings; count outside 1..16;
+ * max_records negative or above 2^28, or null records with max_records > 0; an amount or per_speed that is
+ * negative or non-finite. No reference counterpart. */
+int ocean_foam_deposit(ocean_generator* const* gens, const int* cascades, int count,
+                       const ocean_foam_deposit_settings* settings, const float* records,
+                       const int64_t* count_device, int64_t max_records);
+/* Host copy of the last call's counts with gen0 as gens[0]; synchronises the generator's stream.
+ * OCEAN_ERR_INVALID for a null generator or output and before the first such call. */
+int ocean_foam_deposit_counts(ocean_generator* gen0, int64_t out[50]);
+/* The table in device memory, valid until the generator is destroyed. Null, with ocean_last_error set, for a
+ * null generator and before the first call with gen0 as gens[0]. */
+const int64_t* ocean_foam_deposit_counts_device(ocean_generator* gen0);
+/* Measurement switch (default on): 0 issues one atomic per tap instead of folding runs of neighbouring
+ * records on one texel within the wave first (the same words either way; tools/foam_deposit_bench.py times
+ * both). Returns the previous value. */
+int ocean_debug_foam_deposit_merge(int enable);
+
 /* ---- Spray emitters: ordered compaction of breaking texels into records -------------------------
  * The Jacobian map says where the surface is folding now, the foam keeps its history, and
  * ocean_surface_velocity gives the position and velocity of the water particle under a base point. A

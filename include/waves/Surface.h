@@ -104,6 +104,17 @@ public:
   // texture, reused at the same res.
   Vision::ID SampleFoam(const std::vector<Generator*>& generators, const float camera[5], int res);
 
+  // Foam where spray lands (ocean_foam_deposit, oceanfft.h): every record of an impact list (a
+  // SprayParticles::Step's impacts with GetCountsDevice() + 4 and their capacity; a null countDevice: all
+  // maxRecords) adds to the generators' foam maps at the four texels SampleFoam would read at its position,
+  // settings[i] for generators[i]. Integer sums: the order of the records does not matter and a call replays bit
+  // for bit. Every generator needs a Generator::AdvanceFoam() or ResetFoam() first. Enqueued on the device's
+  // stream; GetDepositCounts is the call's int64[50] table (n, offered, then taps, texels touched and touched
+  // texels that saturated per generator) and synchronises.
+  void DepositFoam(const std::vector<Generator*>& generators, const ocean_foam_deposit_settings* settings,
+                   const float* recordsDevice, const int64_t* countDevice, int64_t maxRecords);
+  void GetDepositCounts(const std::vector<Generator*>& generators, int64_t out[50]) const;
+
   // What the water is doing at world positions, under the surface too (ocean_water_kinematics, oceanfft.h):
   // keels, mooring lines, ROVs, submerged sensors. xyzDevice: points x 3 floats (x, y, z; y up) in device
   // memory. Query's fixed point finds the water column above or below each point; the velocity and the

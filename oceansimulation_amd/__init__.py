@@ -5,18 +5,20 @@ Drop-in for the h0 -> h(k,t) -> 2D iFFT path of James51332/OceanSimulation
 include/oceanfft.h); this package is its ctypes binding plus a Python mirror of the reference
 classes used by the tests and bench.py.
 """
-from .capi import (OceanCamera, OceanCameraLayers, OceanError, OceanFoamSettings, OceanMarch, OceanParticleSettings,  # noqa: F401
-                   OceanSettings, OceanShading, OceanSpraySettings, lib)
+from .capi import (OceanCamera, OceanCameraLayers, OceanError, OceanFoamDepositSettings, OceanFoamSettings, OceanMarch,  # noqa: F401
+                   OceanParticleSettings, OceanSettings, OceanShading, OceanSpraySettings, lib)
 from .waves import (FFTCalculator, Generator, default_settings, apply_settings,  # noqa: F401
                     default_foam_settings, apply_foam_settings, default_spray_settings, apply_spray_settings,
-                    default_particle_settings, apply_particle_settings)
+                    default_particle_settings, apply_particle_settings, default_foam_deposit_settings,
+                    apply_foam_deposit_settings)
 from .surface import (SprayEmitter, SprayParticles, camera_pose, default_camera, default_march,  # noqa: F401
                       default_shading, default_camera_layers, camera_rays_host)
 
 __all__ = ["FFTCalculator", "Generator", "OceanSettings", "OceanFoamSettings", "OceanSpraySettings",
-           "OceanParticleSettings", "OceanError",
+           "OceanParticleSettings", "OceanFoamDepositSettings", "OceanError",
            "default_settings", "apply_settings", "default_foam_settings", "apply_foam_settings",
            "default_spray_settings", "apply_spray_settings", "default_particle_settings", "apply_particle_settings",
+           "default_foam_deposit_settings", "apply_foam_deposit_settings",
            "SprayEmitter", "SprayParticles", "OceanCamera", "OceanShading", "OceanMarch", "OceanCameraLayers",
            "camera_pose", "default_camera", "default_shading", "default_march", "default_camera_layers",
            "camera_rays_host", "lib"]

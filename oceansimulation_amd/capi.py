@@ -61,6 +61,18 @@ class OceanFoamSettings(ctypes.Structure):
 assert ctypes.sizeof(OceanFoamSettings) == 16
 
 
+class OceanFoamDepositSettings(ctypes.Structure):
+    """ocean_foam_deposit_settings: one (generator, cascade) pair's deposit parameters, 8 bytes."""
+
+    _fields_ = [
+        ("amount", ctypes.c_float),
+        ("per_speed", ctypes.c_float),
+    ]
+
+
+assert ctypes.sizeof(OceanFoamDepositSettings) == 8
+
+
 class OceanSpraySettings(ctypes.Structure):
     """ocean_spray_settings: one (generator, cascade) pair's emission parameters, 12 bytes."""
 
@@ -243,6 +255,11 @@ SIGNATURES = {
     "ocean_generator_foam_counts_device": (_vp, [_vp]),
     "ocean_surface_sample_foam": (_i, [_vp, _vp, _i, _vp, ctypes.c_int64, _vp]),
     "ocean_surface_sample_plane_foam": (_i, [_vp, _vp, _i, _vp, _i, _vp]),
+    "ocean_default_foam_deposit_settings": (None, [ctypes.POINTER(OceanFoamDepositSettings)]),
+    "ocean_foam_deposit": (_i, [_vp, _vp, _i, ctypes.POINTER(OceanFoamDepositSettings), _vp, _vp, ctypes.c_int64]),
+    "ocean_foam_deposit_counts": (_i, [_vp, ctypes.POINTER(ctypes.c_int64)]),
+    "ocean_foam_deposit_counts_device": (_vp, [_vp]),
+    "ocean_debug_foam_deposit_merge": (_i, [_i]),
     "ocean_hulls_create":(_i, [ctypes.POINTER(_vp), _vp, _vp, ctypes.c_int64, _vp, _i]),
     "ocean_hulls_destroy": (_i, [_vp]),
     "ocean_hulls_bodies": (_i, [_vp]),

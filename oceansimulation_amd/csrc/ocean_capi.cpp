@@ -950,7 +950,8 @@ int ocean_generator_destroy(ocean_generator* g)
                   (void*)g->xsend[1], (void*)g->xrecv[0], (void*)g->xrecv[1], (void*)f0.gab, (void*)f0.gde, (void*)f0.gc,
                   (void*)f0.spec, (void*)f1.gab, (void*)f1.gde, (void*)f1.gc, (void*)f1.spec, (void*)g->hs,
                   (void*)g->h0row, g->seedc, (void*)g->rm_ab, (void*)g->rm_de, (void*)g->rm_c, (void*)g->parts,
-                  (void*)g->xbuf, (void*)g->mips, (void*)g->rates, (void*)g->kin, (void*)g->bounds, (void*)g->foam, g->foam_counts})
+                  (void*)g->xbuf, (void*)g->mips, (void*)g->rates, (void*)g->kin, (void*)g->bounds, (void*)g->foam, g->foam_counts,
+                  (void*)g->deposit_acc, g->deposit_counts})
     if (p)
       (void)hipFree(p);
   delete g;

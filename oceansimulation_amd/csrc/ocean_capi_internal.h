@@ -179,6 +179,11 @@ struct ocean_generator
   std::vector<ocean_foam_settings> foam_settings;
   float* foam = nullptr;
   void* foam_counts = nullptr;
+  // ocean_foam_deposit: the accumulators [cascade][N * N] (uint64 units of 2^-24, all zero between calls) of a
+  // generator that has received a deposit, and the counts of the calls it was the first generator of (the int64
+  // table [50], then the workgroups' partial rows: foam_deposit_scratch_bytes); allocated and zeroed on first use
+  unsigned long long* deposit_acc = nullptr;
+  void* deposit_counts = nullptr;
   bool profiling = false;
   std::vector<EventPair> pending;
   std::vector<hipEvent_t> pool;

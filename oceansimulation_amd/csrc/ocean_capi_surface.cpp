@@ -1,7 +1,7 @@
 // ocean_capi_surface.cpp — the part of the C ABI (include/oceanfft.h) that consumes a generator's maps:
 // the map getters, ocean_surface_sample / _query / _sample_plane, the mip pyramids and the *_lod requests,
 // the rate maps and ocean_surface_velocity, the depth layers and ocean_water_kinematics, the bounds and ocean_surface_raycast, the persistent foam with
-// ocean_surface_sample_foam, the camera images (ocean_camera_render, ocean_camera_render_layers), the hull sets, the spray emitters and the
+// ocean_surface_sample_foam and ocean_foam_deposit, the camera images (ocean_camera_render, ocean_camera_render_layers), the hull sets, the spray emitters and the
 // spray particles.
 // The plans and generators themselves are in ocean_capi.cpp, their exchanges in ocean_capi_exchange.cpp;
 // ocean_capi_internal.h has what the three share.
@@ -31,6 +31,25 @@ int alloc_once(T*& ptr, size_t bytes, const std::string& who)
 {
   const hipError_t e = alloc_if_null(ptr, bytes);
   return e == hipSuccess ? OCEAN_OK : alloc_fail(e, who);
+}
+
+// A generator's buffer that is allocated on first use and zeroed on `stream` (ocean_foam_deposit's)
+template <typename T>
+int alloc_zeroed_once(T*& ptr, size_t bytes, hipStream_t stream, const std::string& who)
+{
+  if (ptr)
+    return OCEAN_OK;
+  T* fresh = nullptr;
+  hipError_t e = alloc_if_null(fresh, bytes);
+  if (e == hipSuccess && (e = hipMemsetAsync(fresh, 0, bytes, stream)) != hipSuccess)
+  {
+    (void)hipStreamSynchronize(stream);  // the memset of the buffer about to be freed may be in flight
+    (void)hipFree(fresh);
+  }
+  if (e != hipSuccess)
+    return alloc_fail(e, who);
+  ptr = fresh;
+  return OCEAN_OK;
 }
 
 // A generator that holds whole maps and, with `frame`, has calculated a frame
@@ -866,6 +885,9 @@ int ocean_generator_reset_foam(ocean_generator* g)
   ocean_fft* f = g->fft;
   HIP_TRY(hipMemsetAsync(g->foam, 0, (size_t)g->cascades * f->n * f->n * sizeof(float), f->stream), who.c_str());
   HIP_TRY(hipMemsetAsync(g->foam_counts, 0, foam_counts_bytes(f->n, g->cascades), f->stream), who.c_str());
+  if (g->deposit_acc)  // zero between calls already: a reset also clears what a failed deposit may have left
+    HIP_TRY(hipMemsetAsync(g->deposit_acc, 0, (size_t)g->cascades * f->n * f->n * sizeof(unsigned long long), f->stream),
+            who.c_str());
   return OCEAN_OK;
 }
 
@@ -947,6 +969,107 @@ int ocean_surface_sample_plane_foam(ocean_generator* const* gens, const int* cas
   HIP_TRY(launch_surface_foam(p, f, plane, nullptr, pts, reinterpret_cast<float4*>(out), fft->stream, fft->cus),
           "ocean_surface_sample_plane_foam");
   return OCEAN_OK;
+}
+
+// ---- foam deposit: spray impacts splatted into the persistent foam ----
+void ocean_default_foam_deposit_settings(ocean_foam_deposit_settings* s)
+{
+  if (s)
+    *s = ocean_foam_deposit_settings{0.05f, 0.01f};
+}
+
+static bool g_deposit_merge = true;
+
+int ocean_debug_foam_deposit_merge(int enable)
+{
+  const bool was = g_deposit_merge;
+  g_deposit_merge = enable != 0;
+  return was ? 1 : 0;
+}
+
+int ocean_foam_deposit(ocean_generator* const* gens, const int* cascades, int count,
+                       const ocean_foam_deposit_settings* settings, const float* records,
+                       const int64_t* count_device, int64_t max_records)
+{
+  const std::string who = "ocean_foam_deposit";
+  // the rules that need no generator first
+  if (!gens || !cascades || count < 1 || count > kMaxSurfaceCascades)
+    return fail(OCEAN_ERR_INVALID, who + ": need 1..16 (generator, cascade) pairs");
+  if (!settings)
+    return fail(OCEAN_ERR_INVALID, who + ": null settings");
+  if (max_records < 0 || max_records > ((int64_t)1 << 28) || (max_records > 0 && !records))
+    return fail(OCEAN_ERR_INVALID, who + ": max_records outside 0..2^28, or null records with max_records > 0");
+  for (int i = 0; i < count; i++)
+  {
+    const ocean_foam_deposit_settings& s = settings[i];
+    if (!(s.amount >= 0.0f) || !std::isfinite(s.amount) || !(s.per_speed >= 0.0f) || !std::isfinite(s.per_speed))
+      return fail(OCEAN_ERR_INVALID, who + ": pair " + std::to_string(i) + " needs amount and per_speed finite and >= 0");
+  }
+  SurfaceParams p;
+  ocean_fft* fft;
+  SurfaceFoam f;
+  TRY(surface_params(gens, cascades, count, p, fft, who.c_str()));
+  TRY(frames_calculated(gens, count, who));
+  TRY(surface_foam(gens, cascades, count, fft, f, who.c_str()));
+  for (int i = 1; i < count; i++)
+    for (int j = 0; j < i; j++)
+      if (gens[i] == gens[j] && cascades[i] == cascades[j])
+        return fail(OCEAN_ERR_INVALID, who + ": pairs " + std::to_string(j) + " and " + std::to_string(i) +
+                                           " are the same foam map: a texel has one owner per call");
+  // first use: the counts of gens[0] and the accumulators of every generator with an active pair
+  ocean_generator* g0 = gens[0];
+  TRY(alloc_zeroed_once(g0->deposit_counts, foam_deposit_scratch_bytes(), fft->stream, who));
+  const size_t nn = (size_t)fft->n * fft->n;
+  FoamDepositCall c{};
+  foam_deposit_scratch(g0->deposit_counts, c);
+  for (int i = 0; i < count; i++)
+  {
+    const ocean_foam_deposit_settings& s = settings[i];
+    const bool active = s.amount != 0.0f || s.per_speed != 0.0f;
+    if (active)
+      TRY(alloc_zeroed_once(gens[i]->deposit_acc, (size_t)gens[i]->cascades * nn * sizeof(unsigned long long), fft->stream,
+                         who));
+    c.c[i] = FoamDepositPair{const_cast<float*>(f.foam[i]), active ? gens[i]->deposit_acc + nn * cascades[i] : nullptr,
+                             p.c[i].plane, s.amount, s.per_speed, 0};
+  }
+  if (max_records == 0)
+  {
+    HIP_TRY(hipMemsetAsync(c.table, 0, kFoamDepositCounts * sizeof(int64_t), fft->stream), who.c_str());
+    return OCEAN_OK;
+  }
+  c.records = records;
+  c.count_device = count_device;
+  c.max_records = max_records;
+  c.n = fft->n;
+  c.pairs = count;
+  HIP_TRY(launch_foam_deposit(c, g_deposit_merge, fft->stream, fft->cus), who.c_str());
+  return OCEAN_OK;
+}
+
+// The first generator of an ocean_foam_deposit call, else null with a message
+static ocean_generator* generator_deposited(ocean_generator* g, const char* who)
+{
+  if (!g)
+    return fail_null(std::string(who) + ": null generator");
+  if (!g->deposit_counts)
+    return fail_null(std::string(who) + ": the generator was the first of no ocean_foam_deposit call yet");
+  return g;
+}
+
+const int64_t* ocean_foam_deposit_counts_device(ocean_generator* gen0)
+{
+  return generator_deposited(gen0, "ocean_foam_deposit_counts_device") ? static_cast<const int64_t*>(gen0->deposit_counts)
+                                                                       : nullptr;
+}
+
+int ocean_foam_deposit_counts(ocean_generator* gen0, int64_t out[50])
+{
+  if (!generator_deposited(gen0, "ocean_foam_deposit_counts"))
+    return OCEAN_ERR_INVALID;
+  if (!out)
+    return fail(OCEAN_ERR_INVALID, "ocean_foam_deposit_counts: null output");
+  return read_back(out, gen0->deposit_counts, kFoamDepositCounts * sizeof(int64_t), gen0->fft,
+                   "ocean_foam_deposit_counts");
 }
 
 // ---- camera layers: the foam stage in the water pass, spray records splatted over it ----

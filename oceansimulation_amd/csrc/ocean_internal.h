@@ -543,6 +543,40 @@ void particle_scratch(void* scratch, int64_t capacity, ParticleCall& c);
 hipError_t launch_particles_step(const ParticleCall& c, const SurfaceParams& p, hipStream_t stream, int cus);
 // One launch: the table of a list of `alive` records that no step has made (all other counts 0)
 hipError_t launch_particles_reset(int64_t* table, int64_t alive, hipStream_t stream);
+// Foam deposit (ocean_foam_deposit, include/oceanfft.h, device/k_foam_deposit.h): the impacts of a step
+// splatted into the pairs' persistent foam. One pair of the call: its foam map, its accumulators (one uint64
+// of 2^-24 units per texel; null: the pair deposits nothing) and its values.
+constexpr int kFoamDepositItem = 256;      // records per item: one per thread
+constexpr int kFoamDepositCounts = 50;     // n, offered, then per pair: taps, touched, saturated
+constexpr int kFoamDepositMaxGrid = 4096;  // workgroups of a launch at most: one partial row each
+struct FoamDepositPair
+{
+  float* foam;              // [nn]
+  unsigned long long* acc;  // [nn], all zero between calls; null: amount == 0 and per_speed == 0
+  float plane, amount, per_speed;
+  int pad;
+};
+// The scratch behind the counts: table int64[50] (padded to 512 B), then per workgroup of the accumulate
+// launch the taps per pair, then per workgroup of the apply launch (touched, saturated) per pair.
+struct FoamDepositCall
+{
+  const float* records;         // [max_records][8]: slots 0, 2 and 5 are read
+  const int64_t* count_device;  // or null: max_records
+  int64_t max_records;          // 1 .. 2^28
+  int64_t* table;
+  uint32_t* taps;   // [kFoamDepositMaxGrid][16]
+  uint32_t* owned;  // [kFoamDepositMaxGrid][16][2]
+  int n;            // map side (a power of two)
+  int pairs;        // 1 .. 16
+  int grid_add, grid_apply;  // the two launches' workgroups (the fold's row counts), set by the launcher
+  FoamDepositPair c[kMaxSurfaceCascades];
+};
+size_t foam_deposit_scratch_bytes();
+// The pointers of a scratch buffer of foam_deposit_scratch_bytes() bytes into c
+void foam_deposit_scratch(void* scratch, FoamDepositCall& c);
+// Three launches: accumulate, apply, fold the counts. merge: runs of neighbouring lanes on one texel are
+// folded within the wave before the atomics (the same words either way).
+hipError_t launch_foam_deposit(FoamDepositCall c, bool merge, hipStream_t stream, int cus);
 void launch_surface_atlas(const SurfaceParams& p, hipStream_t stream, int cus);
 size_t surface_atlas_texels(const SurfaceParams& p);
 bool surface_use_atlas(const SurfaceParams& p, int64_t points);

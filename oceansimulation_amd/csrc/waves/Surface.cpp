@@ -1,5 +1,5 @@
 // Waves::SurfaceSampler over ocean_surface_sample_plane / ocean_surface_query /
-// ocean_surface_sample_plane_lod / ocean_surface_velocity / ocean_surface_sample_plane_foam /
+// ocean_surface_sample_plane_lod / ocean_surface_velocity / ocean_surface_sample_plane_foam / ocean_foam_deposit /
 // ocean_water_kinematics / ocean_camera_render / ocean_camera_render_layers, and Waves::HullSet over ocean_hulls
 // (include/oceanfft.h).
 #include "waves/Surface.h"
@@ -206,6 +206,30 @@ Vision::ID SurfaceSampler::SampleFoam(const std::vector<Generator*>& generators,
   if (rc != OCEAN_OK)
     throw std::runtime_error(std::string("SurfaceSampler::SampleFoam: ") + ocean_last_error());
   return verticesFoam;
+}
+
+void SurfaceSampler::DepositFoam(const std::vector<Generator*>& generators, const ocean_foam_deposit_settings* settings,
+                                 const float* recordsDevice, const int64_t* countDevice, int64_t maxRecords)
+{
+  std::vector<ocean_generator*> gens;
+  std::vector<int> cascades;
+  for (auto* g : generators)
+  {
+    gens.push_back(g->GetHandle());
+    cascades.push_back(0);
+  }
+  const int rc = ocean_foam_deposit(gens.data(), cascades.data(), (int)gens.size(), settings, recordsDevice, countDevice,
+                                    maxRecords);
+  if (rc != OCEAN_OK)
+    throw std::runtime_error(std::string("SurfaceSampler::DepositFoam: ") + ocean_last_error());
+}
+
+void SurfaceSampler::GetDepositCounts(const std::vector<Generator*>& generators, int64_t out[50]) const
+{
+  if (generators.empty())
+    throw std::runtime_error("SurfaceSampler::GetDepositCounts: no generator");
+  if (ocean_foam_deposit_counts(generators[0]->GetHandle(), out) != OCEAN_OK)
+    throw std::runtime_error(std::string("SurfaceSampler::GetDepositCounts: ") + ocean_last_error());
 }
 
 Vision::ID SurfaceSampler::Kinematics(const std::vector<Generator*>& generators, const float* xyzDevice,

@@ -12,8 +12,8 @@ import math
 import numpy as np
 
 from . import hip
-from .capi import (OCEAN_ERR_INVALID, OceanCamera, OceanCameraLayers, OceanError, OceanMarch, OceanShading,
-                   OceanSpraySettings, check, lib)
+from .capi import (OCEAN_ERR_INVALID, OceanCamera, OceanCameraLayers, OceanError, OceanFoamDepositSettings, OceanMarch,
+                   OceanShading, OceanSpraySettings, check, lib)
 from .hip import DeviceBuffer
 
 FLOATS_PER_VERTEX = 8  # x, y, z, jacobian, nx, ny, nz, 0 (query: base x, height, base z, ..., residual)
@@ -21,6 +21,8 @@ FLOATS_PER_RAY = 8     # ox, oy, oz, tmin, dx, dy, dz, tmax
 FLOATS_PER_HIT = 16    # ocean_surface_raycast's four rows
 FLOATS_PER_WATER_POINT = 12  # ocean_water_kinematics' three rows
 RAY_HIT, RAY_OUTSIDE, RAY_EXIT, RAY_STEP_LIMIT = 0, 1, 2, 3
+DEPOSIT_COUNTS = 50  # ocean_foam_deposit: n, offered, then (taps, touched, saturated) per pair
+DEPOSIT_ITEM = 256   # records per work item of the deposit's kernels (kFoamDepositItem)
 
 
 def default_camera() -> OceanCamera:
@@ -162,6 +164,56 @@ class SurfaceSampler:
         self.sample_plane_foam_device(camera, res, out.ptr)
         self.fft.synchronize()
         return out.to_host((pts, FLOATS_PER_VERTEX))
+
+    # ---- spray impacts into the persistent foam (Generator.AdvanceFoam or ResetFoam first) ----
+    def _deposit_settings(self, settings):
+        n = len(self.pairs)
+        if isinstance(settings, (OceanFoamDepositSettings, dict)):
+            settings = [settings] * n
+        if len(settings) != n:
+            raise ValueError("one ocean_foam_deposit_settings per (generator, cascade) pair")
+        arr = (OceanFoamDepositSettings * n)()
+        for i, s in enumerate(settings):
+            if isinstance(s, dict):
+                lib().ocean_default_foam_deposit_settings(ctypes.byref(arr[i]))
+                for k, v in s.items():
+                    if k not in ("amount", "per_speed"):
+                        raise AttributeError(f"ocean_foam_deposit_settings has no field {k!r}")
+                    setattr(arr[i], k, v)
+            else:
+                arr[i] = OceanFoamDepositSettings(s.amount, s.per_speed)
+        return arr
+
+    def deposit_foam(self, records_ptr: int, max_records: int, settings, count_device: int = 0) -> None:
+        """Enqueue ocean_foam_deposit on the plan's stream: device records (max_records, 8) in the layout of a
+        particle step's impacts, counted by the int64 at count_device (SprayParticles.counts_device() + 32 for an
+        impact list; 0: all max_records). settings: one OceanFoamDepositSettings or dict of its fields for every
+        pair, or a list of them."""
+        arr = self._deposit_settings(settings)
+        check(lib().ocean_foam_deposit(self._gens, self._cas, len(self.pairs), arr, ctypes.c_void_p(records_ptr or 0),
+                                       ctypes.c_void_p(count_device or 0), ctypes.c_int64(max_records)),
+              "ocean_foam_deposit")
+
+    def deposit_foam_host(self, records: np.ndarray, settings) -> np.ndarray:
+        """Deposit host records (n, 8) of 4-byte words, all of them; returns deposit_counts()."""
+        records = np.ascontiguousarray(records).reshape(-1, FLOATS_PER_VERTEX)
+        assert records.dtype.itemsize == 4
+        src = DeviceBuffer.from_array(records) if records.shape[0] else None
+        self.deposit_foam(src.ptr if src else 0, records.shape[0], settings)
+        return self.deposit_counts()  # synchronises: src is freed on return
+
+    def deposit_counts(self) -> np.ndarray:
+        """The int64[50] counts of the last deposit on the host (n, offered, then taps, touched, saturated per
+        pair); synchronises the plan's stream."""
+        out = (ctypes.c_int64 * DEPOSIT_COUNTS)()
+        check(lib().ocean_foam_deposit_counts(self._gens[0], out), "ocean_foam_deposit_counts")
+        return np.array(out[:], np.int64)
+
+    def deposit_counts_device(self) -> int:
+        ptr = lib().ocean_foam_deposit_counts_device(self._gens[0])
+        if not ptr:
+            raise OceanError(OCEAN_ERR_INVALID, "ocean_foam_deposit_counts_device")
+        return int(ptr)
 
     # ---- footprint-aware sampling of the mip pyramids (Generator.build_mips first) ----
     def sample_lod(self, xzf_ptr: int, points: int, out_ptr: int) -> None:
@@ -565,4 +617,4 @@ def host_cascades(pairs):
 
 __all__ = ["SurfaceSampler", "HullSet", "SprayEmitter", "SprayParticles", "PARTICLE_ITEM", "host_cascades", "FLOATS_PER_VERTEX", "hip", "camera_pose",
            "default_camera", "default_shading", "default_march", "camera_rays_host", "default_camera_layers",
-           "camera_layers_scratch_bytes", "OceanCameraLayers"]
+           "camera_layers_scratch_bytes", "OceanCameraLayers", "DEPOSIT_COUNTS", "DEPOSIT_ITEM"]

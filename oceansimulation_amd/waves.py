@@ -11,7 +11,8 @@ import ctypes
 import numpy as np
 
 from . import capi, hip
-from .capi import OceanFoamSettings, OceanParticleSettings, OceanSettings, OceanSpraySettings, check, lib
+from .capi import (OceanFoamDepositSettings, OceanFoamSettings, OceanParticleSettings, OceanSettings, OceanSpraySettings,
+                   check, lib)
 
 
 def default_settings(**overrides) -> OceanSettings:
@@ -42,6 +43,21 @@ def apply_foam_settings(s: OceanFoamSettings, **overrides) -> OceanFoamSettings:
     for k, v in overrides.items():
         if k not in ("bias", "gain", "decay", "level"):
             raise AttributeError(f"ocean_foam_settings has no field {k!r}")
+        setattr(s, k, v)
+    return s
+
+
+def default_foam_deposit_settings(**overrides) -> OceanFoamDepositSettings:
+    """ocean_foam_deposit_settings defaults (amount 0.05, per_speed 0.01) with keyword overrides."""
+    s = OceanFoamDepositSettings()
+    lib().ocean_default_foam_deposit_settings(ctypes.byref(s))
+    return apply_foam_deposit_settings(s, **overrides)
+
+
+def apply_foam_deposit_settings(s: OceanFoamDepositSettings, **overrides) -> OceanFoamDepositSettings:
+    for k, v in overrides.items():
+        if k not in ("amount", "per_speed"):
+            raise AttributeError(f"ocean_foam_deposit_settings has no field {k!r}")
         setattr(s, k, v)
     return s
 
