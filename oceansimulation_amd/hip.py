@@ -69,6 +69,79 @@ def stream_destroy(stream: int) -> None:
     _check(h.hipStreamDestroy(ctypes.c_void_p(stream)), "hipStreamDestroy")
 
 
+STREAM_NON_BLOCKING = 1  # hipStreamNonBlocking: no implicit ordering against the null stream
+_NOT_READY = 600         # hipErrorNotReady
+
+
+def stream_create(flags: int = STREAM_NON_BLOCKING) -> int:
+    """hipStreamCreateWithFlags -> the hipStream_t as an int; release with stream_destroy."""
+    h = hip()
+    h.hipStreamCreateWithFlags.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint]
+    h.hipStreamCreateWithFlags.restype = ctypes.c_int
+    s = ctypes.c_void_p()
+    _check(h.hipStreamCreateWithFlags(ctypes.byref(s), flags), "hipStreamCreateWithFlags")
+    return int(s.value)
+
+
+def stream_flags(stream: int) -> int:
+    h = hip()
+    h.hipStreamGetFlags.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint)]
+    h.hipStreamGetFlags.restype = ctypes.c_int
+    f = ctypes.c_uint()
+    _check(h.hipStreamGetFlags(ctypes.c_void_p(stream), ctypes.byref(f)), "hipStreamGetFlags")
+    return int(f.value)
+
+
+def _done(rc: int, what: str) -> bool:
+    if rc == _NOT_READY:
+        return False
+    _check(rc, what)
+    return True
+
+
+def stream_query(stream: int) -> bool:
+    """True when everything enqueued on the stream has completed (no wait)."""
+    h = hip()
+    h.hipStreamQuery.argtypes = [ctypes.c_void_p]
+    h.hipStreamQuery.restype = ctypes.c_int
+    return _done(h.hipStreamQuery(ctypes.c_void_p(stream)), "hipStreamQuery")
+
+
+def stream_synchronize(stream: int) -> None:
+    _check(hip().hipStreamSynchronize(ctypes.c_void_p(stream)), "hipStreamSynchronize")
+
+
+def event_create() -> int:
+    h = hip()
+    h.hipEventCreate.argtypes = [ctypes.POINTER(ctypes.c_void_p)]
+    h.hipEventCreate.restype = ctypes.c_int
+    e = ctypes.c_void_p()
+    _check(h.hipEventCreate(ctypes.byref(e)), "hipEventCreate")
+    return int(e.value)
+
+
+def event_record(event: int, stream: int) -> None:
+    h = hip()
+    h.hipEventRecord.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    h.hipEventRecord.restype = ctypes.c_int
+    _check(h.hipEventRecord(ctypes.c_void_p(event), ctypes.c_void_p(stream)), "hipEventRecord")
+
+
+def event_query(event: int) -> bool:
+    """True when the work recorded before the event has completed (no wait)."""
+    h = hip()
+    h.hipEventQuery.argtypes = [ctypes.c_void_p]
+    h.hipEventQuery.restype = ctypes.c_int
+    return _done(h.hipEventQuery(ctypes.c_void_p(event)), "hipEventQuery")
+
+
+def event_destroy(event: int) -> None:
+    h = hip()
+    h.hipEventDestroy.argtypes = [ctypes.c_void_p]
+    h.hipEventDestroy.restype = ctypes.c_int
+    _check(h.hipEventDestroy(ctypes.c_void_p(event)), "hipEventDestroy")
+
+
 def synchronize() -> None:
     _check(hip().hipDeviceSynchronize(), "hipDeviceSynchronize")
 

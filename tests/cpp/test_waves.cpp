@@ -7,8 +7,12 @@
 // FFTCalculator::EncodeIFFT on a random image, and Waves::SlabGenerator at world size 1 (the RCCL
 // exchange with one rank, pipelined and not) against a whole-grid Waves::Generator, bit for bit, and
 // two Waves::SlabGenerator ranks of one process over the one-sided exchange (Waves::SlabPeers joined
-// locally), serial and pipelined, against the whole grid, bit for bit.
-// Usage: test_waves [n] [frames] [slab n, 0 = skip] [put n, 0 = skip]. Exit code 0 = all within tolerance.
+// locally), serial and pipelined, against the whole grid, bit for bit. Last, the scene and one surface
+// request on a Vision::RenderDevice whose stream the caller created with hipStreamNonBlocking, every
+// frame issued behind a one-workgroup copy that keeps the stream busy, against the default-stream
+// device, bit for bit.
+// Usage: test_waves [n] [frames] [slab n, 0 = skip] [put n, 0 = skip] [stream mode, 0 = skip].
+// Exit code 0 = all within tolerance.
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
@@ -19,9 +23,11 @@
 #include <vector>
 
 #include "ocean_oracle.h"
+#include "oceanfft.h"
 #include "waves/FFTCalculator.h"
 #include "waves/Generator.h"
 #include "waves/SlabGenerator.h"
+#include "waves/Surface.h"
 
 static double rel_err(const std::vector<float>& got, const std::vector<float>& ref, int stride, int ch)
 {
@@ -135,12 +141,106 @@ static int slab_put_two_ranks(Vision::RenderDevice& device, int n, int frames)
   return failures;
 }
 
+// WaveApp's scene and one surface request on `device`: the three generators' maps and the sampled plane mesh
+// as bytes. With stall buffers, a one-workgroup copy is enqueued on the device's stream ahead of every frame
+// and of the request, so the calls return while the stream is still busy with earlier work.
+static std::vector<std::vector<float>> scene_bytes(Vision::RenderDevice& device, int n, int frames, void* stall_dst,
+                                                   const void* stall_src, size_t stall_bytes)
+{
+  Waves::FFTCalculator fft(&device, n);
+  std::vector<Waves::Generator*> generators;
+  static const float planes[] = {5.0f, 17.0f, 101.0f};
+  for (int i = 0; i < 3; i++)
+  {
+    auto* g = new Waves::Generator(&device, &fft);
+    Waves::GeneratorSettings& s = g->GetOceanSettings();
+    s.planeSize = planes[i];
+    s.boundWavelength = 1;
+    s.wavelengthMax = s.planeSize / 2.0;
+    s.wavelengthMin = (i == 0) ? 0.0 : planes[i - 1] / 2.0;
+    generators.push_back(g);
+  }
+  auto stall = [&] {
+    if (stall_dst && ocean_debug_copy(stall_dst, stall_src, stall_bytes, 1, device.GetStream()) != OCEAN_OK)
+      std::printf("stream mode: %s\n", ocean_last_error());
+  };
+  for (int f = 0; f < frames; f++)
+  {
+    device.BeginCommandBuffer();
+    stall();
+    for (auto* g : generators)
+      g->CalculateOcean(1.0f / 60.0f, true);
+    device.SubmitCommandBuffer();
+  }
+  const int res = 32;
+  const float camera[5] = {3.0f, 12.0f, -7.0f, 0.6f, 0.8f};
+  Waves::SurfaceSampler sampler(&device);
+  stall();
+  const Vision::ID mesh = sampler.Sample(generators, camera, res);
+  const size_t texels = (size_t)n * n;
+  std::vector<std::vector<float>> out;
+  for (auto* g : generators)
+  {
+    out.emplace_back(texels * 4);
+    device.GetTexture2DDataRaw(g->GetHeightMap(), out.back().data());
+    out.emplace_back(texels * 4);
+    device.GetTexture2DDataRaw(g->GetDisplacementMap(), out.back().data());
+    out.emplace_back(texels);
+    device.GetTexture2DDataRaw(g->GetJacobianMap(), out.back().data());
+  }
+  out.emplace_back((size_t)2 * (res + 1) * (res + 1) * 4);
+  device.GetTexture2DDataRaw(mesh, out.back().data());
+  for (auto* g : generators)
+    delete g;
+  return out;
+}
+
+// The drop-in on a caller's non-blocking stream against the default stream, bit for bit.
+static int scene_on_a_non_blocking_stream(Vision::RenderDevice& device0, int n, int frames)
+{
+  hipStream_t stream = nullptr;
+  unsigned flags = 0;
+  const size_t stall_bytes = (size_t)64 << 20;
+  void *a = nullptr, *b = nullptr;
+  if (hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess ||
+      hipStreamGetFlags(stream, &flags) != hipSuccess || !(flags & hipStreamNonBlocking) ||
+      hipMalloc(&a, stall_bytes) != hipSuccess || hipMalloc(&b, stall_bytes) != hipSuccess)
+  {
+    std::printf("stream mode: no non-blocking stream or stall buffers\n");
+    return 1;
+  }
+  int failures = 0;
+  const auto want = scene_bytes(device0, n, frames, nullptr, nullptr, 0);
+  {
+    Vision::RenderDevice device(stream);
+    const auto got = scene_bytes(device, n, frames, b, a, stall_bytes);
+    static const char* names[4] = {"heightMap", "displacementMap", "jacobian", "surface mesh"};
+    for (size_t k = 0; k < want.size(); k++)
+    {
+      bool nonzero = false;
+      for (float v : got[k])
+        nonzero = nonzero || v != 0.0f;
+      const bool ok = got[k].size() == want[k].size() && nonzero &&
+                      std::memcmp(got[k].data(), want[k].data(), want[k].size() * sizeof(float)) == 0;
+      std::printf("non-blocking stream n=%d %s %zu: %s\n", n, names[k + 1 == want.size() ? 3 : k % 3], k / 3,
+                  ok ? "bit-exact" : "DIFFERS");
+      failures += !ok;
+    }
+  }
+  (void)hipStreamSynchronize(stream);
+  (void)hipFree(a);
+  (void)hipFree(b);
+  (void)hipStreamDestroy(stream);
+  return failures;
+}
+
 int main(int argc, char** argv)
 {
   const int n = argc > 1 ? std::atoi(argv[1]) : 256;
   const int frames = argc > 2 ? std::atoi(argv[2]) : 3;
   const int slab_n = argc > 3 ? std::atoi(argv[3]) : 1024;
   const int put_n = argc > 4 ? std::atoi(argv[4]) : 8192;
+  const int stream_mode = argc > 5 ? std::atoi(argv[5]) : 1;
   int failures = 0;
 
   Vision::RenderDevice device;  // default stream
@@ -235,6 +335,8 @@ int main(int argc, char** argv)
     failures += slab_world1(device, slab_n, frames);
   if (put_n > 0)
     failures += slab_put_two_ranks(device, put_n, frames);
+  if (stream_mode > 0)
+    failures += scene_on_a_non_blocking_stream(device, n, frames);
   std::printf("%s (%d failures)\n", failures ? "FAIL" : "PASS", failures);
   return failures ? 1 : 0;
 }

@@ -389,6 +389,44 @@ def test_layer_zero_is_the_rate_maps_bit_for_bit(ocean):
     fft.close()
 
 
+@gpu
+def test_layers_two_column_h0_strips(ocean):
+    """N = 2048, one cascade, layers (0, 1 m): k_kinematics_pack<true> on the 2-column h0 strips of the half-strip
+    column pass (lcw = 3: a block is 8 columns x 128 rows). Layer 0 is the rate maps bit for bit, and image 1 .z
+    the height map's h as far as test_layer_zero_is_the_rate_maps_bit_for_bit holds it (the frame and EncodeIFFT
+    transform one spectrum with different kernels: within twice the frame's gate, and the test prints whether the
+    bits agree); layer 1 against the reference."""
+    from oceansimulation_amd import capi
+
+    depths = (0.0, 1.0)
+    fft = ocean.FFTCalculator(2048)
+    gen = ocean.Generator(fft, 1)
+    ocean.apply_settings(gen.GetOceanSettings(0), planeSize=401.0)
+    gen.set_depth_layers(depths)
+    gen.CalculateOcean(1.0)
+    assert int(capi.lib().ocean_generator_spectrum_block(gen.handle)) == 2
+    gen.calculate_rates()
+    gen.calculate_kinematics()
+    i0, i1 = gen.kinematics_map_host(0, 0, 0), gen.kinematics_map_host(0, 0, 1)
+    rh, rd, hm = gen.height_rate_map_host(0), gen.displacement_rate_map_host(0), gen.height_map_host(0)
+    assert np.array_equal(_bits(i0[..., 0]), _bits(rh[..., 0])) and rh[..., 0].any()
+    assert np.array_equal(_bits(i0[..., 3]), _bits(rh[..., 3])) and rh[..., 3].any()
+    assert np.array_equal(_bits(i1[..., 0]), _bits(rd[..., 0])) and rd[..., 0].any()
+    h_err = channel_err(i1[..., 2:3], hm[..., 0:1])[0]
+    print(f"N = 2048: image 1 .z against h: {h_err:.2e}, bit for bit: "
+          f"{np.array_equal(_bits(i1[..., 2]), _bits(hm[..., 0]))}")
+    assert h_err <= 2.0 * FRAME_TOL_GPU, h_err  # each side is held to FRAME_TOL_GPU of the float64 transform
+    s = R.settings_dict(gen.GetOceanSettings(0))
+    want = K.layer_maps(s, gen.n, gen.initial_spectrum_host(0), depths[1:])[0]
+    got = [gen.kinematics_map_host(0, 1, image) for image in range(2)]
+    per_image = [channel_err(got[image], want[image]) for image in range(2)]
+    errs = [per_image[i][ch] for i, ch in NAMED]
+    print("N = 2048, 2-column strips, depth 1 m: " + " ".join(f"{e:.2e}" for e in errs))
+    assert max(errs) <= FRAME_TOL_GPU, errs
+    gen.close()
+    fft.close()
+
+
 class _DevicePtr:
     """A device buffer of the library seen by torch (no copy)."""
 

@@ -193,6 +193,37 @@ def test_rate_maps_half_spectrum_path_after_fused_reseed(ocean):
 
 
 @pytest.mark.gpu
+def test_rate_maps_two_column_h0_strips(ocean):
+    """N = 2048, one cascade: the half-strip column pass keeps h0 in 2-column strips (k_rates_pack<true> with
+    lcw = 3: a block is 8 columns x 128 rows), the default path of a one-cascade 2048^2 or 4096^2 ocean. Then the
+    full-spectrum path: h0 goes back to 4-column strips, the same values, and the rates still pass."""
+    from oceansimulation_amd import capi
+
+    L = capi.lib()
+    fft = ocean.FFTCalculator(2048)
+    gen = ocean.Generator(fft, 1)
+    ocean.apply_settings(gen.GetOceanSettings(0), planeSize=401.0)
+    gen.CalculateOcean(1.0)
+    assert int(L.ocean_generator_spectrum_block(gen.handle)) == 2
+    gen.calculate_rates()
+    errs = _rate_errs(gen)
+    print("N = 2048, 2-column strips: " + " ".join(f"{e:.2e}" for e in errs))
+    assert max(errs) <= FRAME_TOL_GPU, errs
+    h0 = gen.initial_spectrum_host(0)
+    assert h0.any()
+    gen.set_half_spectrum(False)
+    gen.CalculateOcean(1.0 / 60.0)
+    assert int(L.ocean_generator_spectrum_block(gen.handle)) == 4
+    gen.calculate_rates()
+    errs = _rate_errs(gen)
+    print("N = 2048, full spectrum, 4-column strips: " + " ".join(f"{e:.2e}" for e in errs))
+    assert max(errs) <= FRAME_TOL_GPU, errs
+    assert np.array_equal(gen.initial_spectrum_host(0).view(np.uint32), h0.view(np.uint32))
+    gen.close()
+    fft.close()
+
+
+@pytest.mark.gpu
 def test_rate_maps_of_a_batched_generator(ocean):
     gen = ocean.Generator(ocean.FFTCalculator(64), 3)
     for c, plane in enumerate(PLANES):
