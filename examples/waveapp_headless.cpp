@@ -17,7 +17,7 @@
 // Usage: waveapp_headless [--n 256] [--frames 600] [--dt 0.0166667] [--freeze A:B]...
 //                         [--edit F:G.field=value]... [--reseed reference|on-edit]
 //                         [--mesh RES (0 = no surface step)] [--probes K] [--velocity] [--mips] [--bodies K]
-//                         [--rays K] [--image WxH] [--dump DIR]
+//                         [--float-bodies] [--rays K] [--image WxH] [--dump DIR]
 // Prints one JSON line. --dump DIR writes height_G.npy, disp_G.npy, jac_G.npy (G = 0..2),
 // surface.npy ((RES+1)^2 x 8 floats) and scene.json for the last frame.
 // --probes K (default 0: nothing changes): after the last frame, the water surface above K points on a
@@ -38,6 +38,13 @@
 // 8 iterations, tolerance 0, water velocity on). The JSON line gains "bodies" and "body_max_residual"; --dump
 // adds hull_points.npy (64 x 8), hull_ranges.npy (K x 2, int32), body_poses.npy (K x 20), body_loads.npy
 // (K x 8), body_points.npy (64 K x 8) and height_rate_G.npy / disp_rate_G.npy of the last frame.
+// --float-bodies (default off: nothing changes; honoured with --bodies K): the bodies are released. Each gets
+// the mass of half its displaced volume of water (so it floats half submerged), the moments of inertia of a
+// uniform box, damping 0.5 / s, and is stepped every frame by Waves::HullSet::Step (dt as the frame's, 2
+// substeps, gravity (0, -9.8, 0), the loads' settings) in place of the loads call; the loads and point rows
+// are those of the last substep. The JSON line gains "body_poses" (K rows of 20, the poses after the last
+// frame); --dump writes the poses before the first frame to body_poses.npy and adds body_props.npy (K x 8) and
+// body_poses_final.npy (K x 20).
 // --rays K (default 0: nothing changes): a lidar ring, K rays from a mast at (0, 10, 0), azimuths evenly
 // spaced, 5 degrees below the horizon, tmax 400 m. Every frame builds the generators' bounds
 // (Generator::BuildBounds) and casts the ring (SurfaceSampler::Raycast: step 0.25, 256 steps, 10 bisections,
@@ -121,7 +128,7 @@ void usage()
 {
   std::fprintf(stderr, "usage: waveapp_headless [--n N] [--frames K] [--dt S] [--freeze A:B]... "
                        "[--edit F:G.field=value]... [--reseed reference|on-edit] [--mesh RES] [--probes K] "
-                       "[--velocity] [--mips] [--bodies K] [--rays K] [--image WxH] [--dump DIR]\n");
+                       "[--velocity] [--mips] [--bodies K] [--float-bodies] [--rays K] [--image WxH] [--dump DIR]\n");
 }
 
 }  // namespace
@@ -130,16 +137,16 @@ int main(int argc, char** argv)
 {
   int n = 256, frames = 600, mesh = 1024, probes = 0, bodies = 0, rays = 0, imageW = 0, imageH = 0;
   float dt = 1.0f / 60.0f;
-  bool reseed_every_frame = true, mips = false, velocity = false;
+  bool reseed_every_frame = true, mips = false, velocity = false, floatBodies = false;
   std::string dump;
   std::vector<std::pair<int, int>> freezes;
   std::vector<Edit> edits;
   for (int i = 1; i < argc; i++)
   {
     const std::string a = argv[i];
-    if (a == "--mips" || a == "--velocity")  // the switches without a value
+    if (a == "--mips" || a == "--velocity" || a == "--float-bodies")  // the switches without a value
     {
-      (a == "--mips" ? mips : velocity) = true;
+      (a == "--mips" ? mips : a == "--velocity" ? velocity : floatBodies) = true;
       continue;
     }
     const char* v = i + 1 < argc ? argv[i + 1] : nullptr;
@@ -228,6 +235,13 @@ int main(int argc, char** argv)
     Waves::HullSet* hulls = nullptr;
     float* posesDevice = nullptr;
     Vision::ID bodyLoads = 0;
+    std::vector<float> bodyProps, bodyPosesFinal;
+    ocean_hull_step_settings bodyStep;
+    ocean_default_hull_step_settings(&bodyStep);
+    bodyStep.substeps = 2;
+    bodyStep.rho_g = rhoG;
+    bodyStep.water_velocity = 1;
+    floatBodies = floatBodies && bodies > 0;
     if (bodies > 0)
     {
       for (int k = 0; k < 4; k++)      // z
@@ -253,6 +267,16 @@ int main(int argc, char** argv)
         hullRanges.push_back(64);
       }
       hulls = new Waves::HullSet(&device, &fft, hullPoints.data(), 64, hullRanges.data(), bodies);
+      if (floatBodies)
+      {
+        // half the displaced volume of the 2 x 1 x 4 m box in water of rhoG / 9.8 kg/m^3; a uniform box's moments
+        const float mass = 0.5f * 8.0f * (rhoG / 9.8f);
+        for (int b = 0; b < bodies; b++)
+          for (float f : {mass, mass * (1.0f + 16.0f) / 12.0f, mass * (4.0f + 16.0f) / 12.0f, mass * (4.0f + 1.0f) / 12.0f,
+                          0.5f, 0.5f, 0.0f, 0.0f})
+            bodyProps.push_back(f);
+        hulls->SetBodies(bodyProps.data());
+      }
       if (hipMalloc(reinterpret_cast<void**>(&posesDevice), bodyPoses.size() * sizeof(float)) != hipSuccess ||
           hipMemcpy(posesDevice, bodyPoses.data(), bodyPoses.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
       {
@@ -335,7 +359,16 @@ int main(int argc, char** argv)
       {
         for (auto* g : generators)
           g->CalculateRates();
-        bodyLoads = hulls->Loads(generators, posesDevice, rhoG, 8, 0.0f, true, true);
+        if (floatBodies)
+        {
+          if (step > 0.0f)  // a frozen frame moves nothing
+          {
+            bodyStep.dt = step;
+            bodyLoads = hulls->Step(generators, posesDevice, bodyStep, nullptr, true);
+          }
+        }
+        else
+          bodyLoads = hulls->Loads(generators, posesDevice, rhoG, 8, 0.0f, true, true);
       }
       if (rays > 0)
       {
@@ -356,8 +389,18 @@ int main(int argc, char** argv)
 
     std::vector<float> bodyLoadsHost, bodyPointsHost;
     float bodyMaxResidual = 0.0f;
-    if (bodies > 0 && frames > 0)
+    if (bodies > 0 && frames > 0 && bodyLoads)
     {
+      if (floatBodies)
+      {
+        bodyPosesFinal.resize(bodyPoses.size());  // the last frame's submit has waited for the stream
+        if (hipMemcpy(bodyPosesFinal.data(), posesDevice, bodyPoses.size() * sizeof(float), hipMemcpyDeviceToHost) !=
+            hipSuccess)
+        {
+          std::fprintf(stderr, "waveapp_headless: cannot read the body poses\n");
+          return 1;
+        }
+      }
       bodyLoadsHost.resize((size_t)bodies * 8);
       bodyPointsHost.resize((size_t)bodies * 64 * 8);
       device.GetTexture2DDataRaw(bodyLoads, bodyLoadsHost.data());
@@ -540,7 +583,10 @@ int main(int argc, char** argv)
             write_npy(dump + "/hull_ranges.npy", hullRanges.data(), {(size_t)bodies, 2}, "<i4") &&
             write_npy(dump + "/body_poses.npy", bodyPoses.data(), {(size_t)bodies, 20}) &&
             write_npy(dump + "/body_loads.npy", bodyLoadsHost.data(), {(size_t)bodies, 8}) &&
-            write_npy(dump + "/body_points.npy", bodyPointsHost.data(), {(size_t)bodies * 64, 8})))
+            write_npy(dump + "/body_points.npy", bodyPointsHost.data(), {(size_t)bodies * 64, 8}) &&
+            (bodyPosesFinal.empty() ||
+             (write_npy(dump + "/body_props.npy", bodyProps.data(), {(size_t)bodies, 8}) &&
+              write_npy(dump + "/body_poses_final.npy", bodyPosesFinal.data(), {(size_t)bodies, 20})))))
       {
         std::fprintf(stderr, "cannot write %s\n", dump.c_str());
         return 1;
@@ -579,8 +625,13 @@ int main(int argc, char** argv)
         }
         std::fprintf(js, "]");
         if (bodies > 0)
-          std::fprintf(js, ", \"bodies\": {\"count\": %d, \"rho_g\": %.9g, \"iterations\": 8, \"tolerance\": 0}", bodies,
-                       rhoG);
+        {
+          std::fprintf(js, ", \"bodies\": {\"count\": %d, \"rho_g\": %.9g, \"iterations\": 8, \"tolerance\": 0", bodies, rhoG);
+          if (floatBodies)
+            std::fprintf(js, ", \"dt\": %.9g, \"substeps\": %d, \"gravity\": [%.9g, %.9g, %.9g]", dt, bodyStep.substeps,
+                         bodyStep.gravity[0], bodyStep.gravity[1], bodyStep.gravity[2]);
+          std::fprintf(js, "}");
+        }
         std::fprintf(js, "}\n");
         std::fclose(js);
       }
@@ -605,6 +656,21 @@ int main(int argc, char** argv)
       char b[96];
       std::snprintf(b, sizeof b, ", \"bodies\": %d, \"body_max_residual\": %.9g", bodies, bodyMaxResidual);
       probeJson += b;
+      if (!bodyPosesFinal.empty())
+      {
+        probeJson += ", \"body_poses\": [";
+        for (int k = 0; k < bodies; k++)
+        {
+          probeJson += k ? ", [" : "[";
+          for (int j = 0; j < 20; j++)
+          {
+            std::snprintf(b, sizeof b, "%s%.9g", j ? ", " : "", bodyPosesFinal[20 * (size_t)k + j]);
+            probeJson += b;
+          }
+          probeJson += "]";
+        }
+        probeJson += "]";
+      }
     }
     if (!rayHitsHost.empty())
       probeJson += ", \"rays\": " + std::to_string(rays) + ", \"ray_hits\": " + std::to_string(rayHitCount);

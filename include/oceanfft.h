@@ -894,6 +894,83 @@ int ocean_hulls_loads(ocean_hulls* hulls, ocean_generator* const* gens, const in
                       const float* poses, float rho_g, int iterations, float tolerance, int water_velocity,
                       float* loads, float* point_out);
 
+/* ---- Hull dynamics: bodies stepped on the device from their wave loads ---------------------------
+ * ocean_hulls_loads gives a wrench per body; ocean_hulls_step also moves the bodies with it, so that
+ * boats, buoys and debris float without leaving the device: rigid bodies with a diagonal inertia, integrated
+ * by semi-implicit Euler in substeps, the loads evaluated anew at every substep's pose. The water is frozen
+ * during a call and the bodies do not interact. Like the loads the step is unfused fp32 in a fixed order, so
+ * a run replays bit for bit.
+ *
+ * ocean_hulls_set_bodies. props: host, bodies x 8 floats (mass, Ix, Iy, Iz, lin_damp, ang_damp, kinematic,
+ * 0): the principal moments of inertia (the principal axes are the body-frame axes), linear and angular
+ * damping in 1/s, and kinematic = 1 for a body that keeps its velocities (moved by the caller, loaded by the
+ * water) or 0 for a dynamic one. Copied to the set's device; the only allocation of the dynamics, made by
+ * the first call (the step keeps its sums on chip and needs no buffer for a caller that passes no loads).
+ * A later call replaces the properties after waiting for the plan's stream.
+ * OCEAN_ERR_INVALID, before any device call: a null argument; a non-finite field; mass or a moment <= 0; a
+ * negative damping; kinematic other than 0 or 1. */
+int ocean_hulls_set_bodies(ocean_hulls* hulls, const float* props);
+
+typedef struct ocean_hull_step_settings {
+  float dt; int32_t substeps;        /* dt finite > 0; substeps 1..64 */
+  float gravity[3];                  /* default (0, -9.8, 0) */
+  float rho_g; int32_t iterations; float tolerance; int32_t water_velocity;  /* as ocean_hulls_loads */
+} ocean_hull_step_settings;
+/* dt 1/60, substeps 1, gravity (0, -9.8, 0), rho_g 9810, iterations 8, tolerance 0, water_velocity 0 */
+void ocean_default_hull_step_settings(ocean_hull_step_settings* settings);
+
+/* poses: device, bodies x 20 floats in the layout of ocean_hulls_loads, updated in place. wrench_ext: device,
+ * bodies x 8 floats or null: an external force in slots 0..2 and a torque about the centre in slots 4..6,
+ * both in the world frame (thrust, mooring, towing); slots 3 and 7 are not read. loads (bodies x 8) and
+ * point_out (instance_points x 8): device or null; they receive what ocean_hulls_loads returns for the pose
+ * at the start of the last substep.
+ *
+ * Contract, in unfused fp32, every expression in the order written. h = dt / (float)substeps, computed on the
+ * host. Per substep and body, with R (row-major, R[i][j] = slot 3i + j), c, v, w from the pose, (mass, I,
+ * lin_damp, ang_damp, kinematic) from its properties, E its wrench_ext row and g = gravity:
+ *     Lb  = the ocean_hulls_loads result for this pose: the same arithmetic, fold64 tree and bits
+ *     F   = Lb[0..2] + E[0..2],  T = Lb[4..6] + E[4..6]      wrench_ext null: F = Lb[0..2], T = Lb[4..6]
+ *   dynamic body (kinematic == 0), for k = x, y, z:
+ *     v'.k  = (v.k + h * (F.k / mass + g.k)) / (1.0f + h * lin_damp)
+ *     wb.k  = (R[0][k]*w.x + R[1][k]*w.y) + R[2][k]*w.z              wb = R^T w, the spin in the body frame
+ *     Tb.k  = (R[0][k]*T.x + R[1][k]*T.y) + R[2][k]*T.z
+ *     L     = (I.x*wb.x, I.y*wb.y, I.z*wb.z)
+ *     G     = (wb.y*L.z - wb.z*L.y,  wb.z*L.x - wb.x*L.z,  wb.x*L.y - wb.y*L.x)
+ *     wb'.k = (wb.k + h * ((Tb.k - G.k) / I.k)) / (1.0f + h * ang_damp)
+ *     w'.k  = (R[k][0]*wb'.x + R[k][1]*wb'.y) + R[k][2]*wb'.z
+ *   kinematic body: v' = v, w' = w
+ *   both kinds:
+ *     c'.k  = c.k + h * v'.k
+ *     a     = ((0.5f*h)*w'.x, (0.5f*h)*w'.y, (0.5f*h)*w'.z);   n = (a.x*a.x + a.y*a.y) + a.z*a.z
+ *     p = 1.0f - n;  q = 1.0f + n                    the Cayley map Q = ((1 - n) I + 2 a a^T + 2 [a]x) / (1 + n)
+ *     Q[0][0] = (p + 2.0f*(a.x*a.x)) / q    Q[0][1] = (2.0f*(a.x*a.y) - 2.0f*a.z) / q    Q[0][2] = (2.0f*(a.x*a.z) + 2.0f*a.y) / q
+ *     Q[1][0] = (2.0f*(a.x*a.y) + 2.0f*a.z) / q    Q[1][1] = (p + 2.0f*(a.y*a.y)) / q    Q[1][2] = (2.0f*(a.y*a.z) - 2.0f*a.x) / q
+ *     Q[2][0] = (2.0f*(a.x*a.z) - 2.0f*a.y) / q    Q[2][1] = (2.0f*(a.y*a.z) + 2.0f*a.x) / q    Q[2][2] = (p + 2.0f*(a.z*a.z)) / q
+ *     R1[i][j] = (Q[i][0]*R[0][j] + Q[i][1]*R[1][j]) + Q[i][2]*R[2][j]
+ *   one Gram-Schmidt pass over the rows r0, r1 of R1:
+ *     l0 = sqrtf((r0.x*r0.x + r0.y*r0.y) + r0.z*r0.z);   e0 = r0 / l0
+ *     d  = (e0.x*r1.x + e0.y*r1.y) + e0.z*r1.z;          u = r1 - d*e0     (u.k = r1.k - d*e0.k)
+ *     l1 = sqrtf((u.x*u.x + u.y*u.y) + u.z*u.z);         e1 = u / l1
+ *     e2 = (e0.y*e1.z - e0.z*e1.y,  e0.z*e1.x - e0.x*e1.z,  e0.x*e1.y - e0.y*e1.x)
+ *   the new pose: rows e0, e1, e2, then c', v', w', and slots 18 and 19 written as 0.
+ * No transcendental: sqrtf and the divisions are correctly rounded in this build, as the loads contract
+ * relies on, so a float32 restatement agrees to the bit (tests/hull_step_ref.py). A rotation about a fixed
+ * axis turns by 2 atan(h |w| / 2) per substep. The gyroscopic term G is explicit: a fast spin about a
+ * non-principal direction gains energy unless it is resolved by substeps or held by ang_damp.
+ *
+ * Launches, on the plan's stream, with no host synchronisation and no allocation, on top of the atlas repack
+ * under the rule of ocean_hulls_loads. Every body of at most 64 points: one launch for the whole call,
+ * whatever substeps is; a body's pose stays in the registers of its wave, or its segment of a wave, across
+ * the substeps. Otherwise two launches per substep: bodies of one tile integrate in the first, bodies of
+ * several tiles in the second, after their last fold. Only the owner of a body writes its pose, and the tiles
+ * of a larger body read it in the launch before the one that writes it, so the update in place is safe.
+ * OCEAN_ERR_INVALID, before any device call: a null hull set, settings or poses; dt not finite or <= 0;
+ * substeps outside 1..64; a non-finite gravity; everything ocean_hulls_loads rejects (but loads may be
+ * null); properties that were never set. No reference counterpart. */
+int ocean_hulls_step(ocean_hulls* hulls, ocean_generator* const* gens, const int* cascades, int count,
+                     const ocean_hull_step_settings* settings, float* poses, const float* wrench_ext,
+                     float* loads, float* point_out);
+
 /* Debug: hull sets created after enable = 0 give every body its own waves; by default consecutive bodies
  * of at most 32 points share a wave (the same bits either way; tools/hulls_bench.py times both). */
 int ocean_debug_hulls_packing(int enable);

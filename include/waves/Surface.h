@@ -178,6 +178,18 @@ public:
                    float tolerance, bool waterVelocity, bool pointOutput = false);
   Vision::ID GetPointOutput() const { return pointRows; }
 
+  // Hull dynamics (ocean_hulls_set_bodies / ocean_hulls_step, oceanfft.h). props: bodies x 8 host floats
+  // (mass, Ix, Iy, Iz, lin_damp, ang_damp, kinematic, 0); may be called again to replace them.
+  void SetBodies(const float* props);
+  // Steps posesDevice in place by settings.dt in settings.substeps substeps under the wave loads, gravity and
+  // the optional external wrenches (wrenchExtDevice: bodies x 8 device floats, force in 0..2 and torque about
+  // the centre in 4..6, world frame). Returns the loads texture of Loads(), holding the loads at the start of
+  // the last substep; with pointOutput the per-point rows land in GetPointOutput(). Enqueued on the device's
+  // stream: no host synchronisation.
+  Vision::ID Step(const std::vector<Generator*>& generators, float* posesDevice,
+                  const ocean_hull_step_settings& settings, const float* wrenchExtDevice = nullptr,
+                  bool pointOutput = false);
+
 private:
   Vision::RenderDevice* renderDevice = nullptr;
   ocean_hulls* hulls = nullptr;

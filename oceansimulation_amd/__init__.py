@@ -6,7 +6,7 @@ include/oceanfft.h); this package is its ctypes binding plus a Python mirror of 
 classes used by the tests and bench.py.
 """
 from .capi import (OceanCamera, OceanCameraLayers, OceanError, OceanFoamDepositSettings, OceanFoamSettings, OceanMarch,  # noqa: F401
-                   OceanParticleSettings, OceanSettings, OceanShading, OceanSpraySettings, lib)
+                   OceanHullStepSettings, OceanParticleSettings, OceanSettings, OceanShading, OceanSpraySettings, lib)
 from .waves import (FFTCalculator, Generator, default_settings, apply_settings,  # noqa: F401
                     default_foam_settings, apply_foam_settings, default_spray_settings, apply_spray_settings,
                     default_particle_settings, apply_particle_settings, default_foam_deposit_settings,
@@ -15,7 +15,7 @@ from .surface import (SprayEmitter, SprayParticles, camera_pose, default_camera,
                       default_shading, default_camera_layers, camera_rays_host)
 
 __all__ = ["FFTCalculator", "Generator", "OceanSettings", "OceanFoamSettings", "OceanSpraySettings",
-           "OceanParticleSettings", "OceanFoamDepositSettings", "OceanError",
+           "OceanParticleSettings", "OceanFoamDepositSettings", "OceanHullStepSettings", "OceanError",
            "default_settings", "apply_settings", "default_foam_settings", "apply_foam_settings",
            "default_spray_settings", "apply_spray_settings", "default_particle_settings", "apply_particle_settings",
            "default_foam_deposit_settings", "apply_foam_deposit_settings",

@@ -104,6 +104,23 @@ class OceanParticleSettings(ctypes.Structure):
 assert ctypes.sizeof(OceanParticleSettings) == 40
 
 
+class OceanHullStepSettings(ctypes.Structure):
+    """ocean_hull_step_settings: one ocean_hulls_step call's parameters, 36 bytes."""
+
+    _fields_ = [
+        ("dt", ctypes.c_float),
+        ("substeps", ctypes.c_int32),
+        ("gravity", ctypes.c_float * 3),
+        ("rho_g", ctypes.c_float),
+        ("iterations", ctypes.c_int32),
+        ("tolerance", ctypes.c_float),
+        ("water_velocity", ctypes.c_int32),
+    ]
+
+
+assert ctypes.sizeof(OceanHullStepSettings) == 36
+
+
 class OceanCamera(ctypes.Structure):
     """ocean_camera: position, world-space basis (viewInverse columns 0, 1 and -column 2), lens, 64 bytes."""
 
@@ -266,6 +283,9 @@ SIGNATURES = {
     "ocean_hulls_instance_points": (ctypes.c_int64, [_vp]),
     "ocean_debug_hulls_packing": (_i, [_i]),
     "ocean_hulls_loads": (_i, [_vp, _vp, _vp, _i, _vp, _f, _i, _f, _i, _vp, _vp]),
+    "ocean_hulls_set_bodies": (_i, [_vp, _vp]),
+    "ocean_default_hull_step_settings": (None, [ctypes.POINTER(OceanHullStepSettings)]),
+    "ocean_hulls_step": (_i, [_vp, _vp, _vp, _i, ctypes.POINTER(OceanHullStepSettings), _vp, _vp, _vp, _vp]),
     "ocean_default_spray_settings": (None, [ctypes.POINTER(OceanSpraySettings)]),
     "ocean_spray_create": (_i, [ctypes.POINTER(_vp), _vp]),
     "ocean_spray_destroy": (_i, [_vp]),

@@ -80,6 +80,85 @@ __device__ __forceinline__ float wave_fold_segments(float v, int seg)
 
 // HullTile, HullFold and HullCall: ocean_internal.h (the host builds the tables)
 
+// The lane's body, point and point_out row in a work item: a tile of one body, or (tile.seg > 0) tile.count
+// small bodies from tile.body on, one per aligned segment of tile.seg lanes
+struct HullLane
+{
+  int64_t row;
+  int body, point;
+  bool active, active_segment;  // the lane holds a point; its segment holds a body
+};
+
+__device__ __forceinline__ HullLane hull_tile_lane(const HullCall& h, const HullTile& tile, int lane)
+{
+  HullLane l{tile.offset + lane, tile.body, tile.first + lane, lane < tile.count, true};
+  if (tile.seg > 0)
+  {
+    const int j = lane >> (31 - __clz(tile.seg)), i = lane & (tile.seg - 1);
+    l.active = false;
+    l.active_segment = j < tile.count;
+    if (l.active_segment)
+    {
+      l.body += j;
+      const HullBody hb = h.bodies[l.body];
+      l.active = i < hb.count;
+      l.point = hb.first + i;
+      l.row = hb.offset + i;
+    }
+  }
+  return l;
+}
+
+// One point's load (the contract's a_i) from its row L = (l0, l1) of the points and its body's pose P (R, c, v, w: the
+// first 18 floats of a poses row), and its point_out rows when point_out is not null. P may be device memory (k_hulls_loads) or
+// a pose kept in registers (k_hulls_step, device/k_hulls_step.h): the same expressions, the same bits.
+template <bool ATLAS, bool VELOCITY>
+__device__ __forceinline__ void hull_point_load(const SurfaceParams& p, const SurfaceRates& r, const HullCall& h,
+                                                const float4 l0, const float4 l1, const float* P, int64_t row,
+                                                float4* point_out, float (&a)[8])
+{
+#pragma clang fp contract(off)
+  const float dx = (P[0] * l0.x + P[1] * l0.y) + P[2] * l0.z;
+  const float dy = (P[3] * l0.x + P[4] * l0.y) + P[5] * l0.z;
+  const float dz = (P[6] * l0.x + P[7] * l0.y) + P[8] * l0.z;
+  const float xx = P[9] + dx, xy = P[10] + dy, xz = P[11] + dz;
+  // ocean_surface_query at q = (xx, xz), vertex stage only
+  float bx = xx, bz = xz;
+  float vx, vy, vz;
+  surface_base_point<ATLAS>(p, xx, xz, h.iterations, h.tolerance, bx, bz, vx, vy, vz);
+  const float res = surface_residual(xx, xz, vx, vz);
+  const float t = (vy - xy) / (l1.x + l1.x) + 0.5f;
+  const float s = t > 0.0f ? (t < 1.0f ? t : 1.0f) : 0.0f;  // NaN -> 0
+  float ux = 0.0f, uy = 0.0f, uz = 0.0f;
+  if constexpr (VELOCITY)
+  {
+    float px = bx, py = 0.0f, pz = bz;
+    surface_particle_velocity(p, r, px, py, pz, ux, uy, uz);
+  }
+  const float wx = P[15], wy = P[16], wz = P[17];
+  const float vpx = P[12] + (wy * dz - wz * dy);
+  const float vpy = P[13] + (wz * dx - wx * dz);
+  const float vpz = P[14] + (wx * dy - wy * dx);
+  const float rx = ux - vpx, ry = uy - vpy, rz = uz - vpz;
+  const float m = sqrtf((rx * rx + ry * ry) + rz * rz);
+  const float k = s * (l1.y + l1.z * m);
+  const float vs = l0.w * s;
+  const float fx = k * rx, fy = h.rho_g * vs + k * ry, fz = k * rz;
+  a[0] = fx;
+  a[1] = fy;
+  a[2] = fz;
+  a[3] = vs;
+  a[4] = dy * fz - dz * fy;
+  a[5] = dz * fx - dx * fz;
+  a[6] = dx * fy - dy * fx;
+  a[7] = s > 0.0f ? 1.0f : 0.0f;
+  if (point_out)
+  {
+    point_out[2 * row] = make_float4(bx, vy, bz, res);
+    point_out[2 * row + 1] = make_float4(fx, fy, fz, s);
+  }
+}
+
 template <bool ATLAS, bool VELOCITY>
 __global__ __launch_bounds__(kHullTile) void k_hulls_loads(SurfaceParams p, SurfaceRates r, HullCall h)
 {
@@ -88,86 +167,71 @@ __global__ __launch_bounds__(kHullTile) void k_hulls_loads(SurfaceParams p, Surf
   for (int item = blockIdx.x; item < h.items; item += gridDim.x)
   {
     const HullTile tile = h.tiles[item];
-    // the lane's body, point and point_out row: a tile of one body, or (tile.seg > 0) tile.count small
-    // bodies from tile.body on, one per aligned segment of tile.seg lanes
-    int body = tile.body, point = tile.first + lane;
-    int64_t row = tile.offset + lane;
-    bool active = lane < tile.count, active_segment = true;  // the segment holds a body
-    if (tile.seg > 0)
-    {
-      const int j = lane >> (31 - __clz(tile.seg)), i = lane & (tile.seg - 1);
-      active = false;
-      active_segment = j < tile.count;
-      if (active_segment)
-      {
-        body += j;
-        const HullBody hb = h.bodies[body];
-        active = i < hb.count;
-        point = hb.first + i;
-        row = hb.offset + i;
-      }
-    }
+    const HullLane l = hull_tile_lane(h, tile, lane);
     float a[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    if (active)
-    {
-      const float4 l0 = h.points[2 * (size_t)point], l1 = h.points[2 * (size_t)point + 1];
-      const float* P = h.poses + (size_t)body * 20;
-      const float dx = (P[0] * l0.x + P[1] * l0.y) + P[2] * l0.z;
-      const float dy = (P[3] * l0.x + P[4] * l0.y) + P[5] * l0.z;
-      const float dz = (P[6] * l0.x + P[7] * l0.y) + P[8] * l0.z;
-      const float xx = P[9] + dx, xy = P[10] + dy, xz = P[11] + dz;
-      // ocean_surface_query at q = (xx, xz), vertex stage only
-      float bx = xx, bz = xz;
-      float vx, vy, vz;
-      surface_base_point<ATLAS>(p, xx, xz, h.iterations, h.tolerance, bx, bz, vx, vy, vz);
-      const float res = surface_residual(xx, xz, vx, vz);
-      const float t = (vy - xy) / (l1.x + l1.x) + 0.5f;
-      const float s = t > 0.0f ? (t < 1.0f ? t : 1.0f) : 0.0f;  // NaN -> 0
-      float ux = 0.0f, uy = 0.0f, uz = 0.0f;
-      if constexpr (VELOCITY)
-      {
-        float px = bx, py = 0.0f, pz = bz;
-        surface_particle_velocity(p, r, px, py, pz, ux, uy, uz);
-      }
-      const float wx = P[15], wy = P[16], wz = P[17];
-      const float vpx = P[12] + (wy * dz - wz * dy);
-      const float vpy = P[13] + (wz * dx - wx * dz);
-      const float vpz = P[14] + (wx * dy - wy * dx);
-      const float rx = ux - vpx, ry = uy - vpy, rz = uz - vpz;
-      const float m = sqrtf((rx * rx + ry * ry) + rz * rz);
-      const float k = s * (l1.y + l1.z * m);
-      const float vs = l0.w * s;
-      const float fx = k * rx, fy = h.rho_g * vs + k * ry, fz = k * rz;
-      a[0] = fx;
-      a[1] = fy;
-      a[2] = fz;
-      a[3] = vs;
-      a[4] = dy * fz - dz * fy;
-      a[5] = dz * fx - dx * fz;
-      a[6] = dx * fy - dy * fx;
-      a[7] = s > 0.0f ? 1.0f : 0.0f;
-      if (h.point_out)
-      {
-        h.point_out[2 * row] = make_float4(bx, vy, bz, res);
-        h.point_out[2 * row + 1] = make_float4(fx, fy, fz, s);
-      }
-    }
+    if (l.active)
+      hull_point_load<ATLAS, VELOCITY>(p, r, h, h.points[2 * (size_t)l.point], h.points[2 * (size_t)l.point + 1],
+                                       h.poses + (size_t)l.body * 20, l.row, h.point_out, a);
     const int seg = tile.seg > 0 ? tile.seg : kHullTile;  // wave-uniform
 #pragma unroll
     for (int c = 0; c < 8; c++)
       a[c] = wave_fold_segments(a[c], seg);
-    if ((lane & (seg - 1)) == 0 && active_segment)
+    if ((lane & (seg - 1)) == 0 && l.active_segment)
     {
-      float4* dst = tile.slot < 0 ? h.loads + 2 * (size_t)body : h.partial + 2 * (size_t)tile.slot;
+      float4* dst = tile.slot < 0 ? h.loads + 2 * (size_t)l.body : h.partial + 2 * (size_t)tile.slot;
       dst[0] = make_float4(a[0], a[1], a[2], a[3]);
       dst[1] = make_float4(a[4], a[5], a[6], a[7]);
     }
   }
 }
 
-// The partials of the bodies of more than one tile -> their loads. One workgroup per body: wave w folds
-// the runs w, w + 4, ... of 64 partials, run j's fold lands in slot j of the LDS, and when there is more
-// than one run wave 0 folds those (at most 64).
+// The partials of one body of more than one tile -> its loads, in a[] of wave 0 (the other waves' a[] is left
+// alone). The whole workgroup calls it: wave w folds the runs w, w + 4, ... of 64 partials, run j's fold
+// lands in slot j of the LDS, and when there is more than one run wave 0 folds those (at most 64).
+__device__ __forceinline__ void hull_fold_partials(const HullFold& f, const float4* __restrict__ partial,
+                                                   float (*runs)[8], int lane, int wave, float (&out)[8])
+{
+#pragma clang fp contract(off)
+  const int nruns = (f.tiles + 63) >> 6;  // <= 64
+  // the bound depends on the wave alone: every lane of a wave runs the same steps (whole-wave exchanges)
+  for (int j = wave; j < nruns; j += kHullFoldThreads / 64)
+  {
+    const int t = j * 64 + lane;
+    float a[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (t < f.tiles)
+    {
+      const float4 lo = partial[2 * (size_t)(f.slot + t)], hi = partial[2 * (size_t)(f.slot + t) + 1];
+      a[0] = lo.x, a[1] = lo.y, a[2] = lo.z, a[3] = lo.w;
+      a[4] = hi.x, a[5] = hi.y, a[6] = hi.z, a[7] = hi.w;
+    }
+#pragma unroll
+    for (int c = 0; c < 8; c++)
+      a[c] = wave_fold64(a[c]);
+    if (lane < 8)
+    {
+      float v = a[0];
+#pragma unroll
+      for (int c = 1; c < 8; c++)
+        v = lane == c ? a[c] : v;
+      runs[j][lane] = v;
+    }
+  }
+  __syncthreads();
+  if (wave == 0)
+  {
+#pragma unroll
+    for (int c = 0; c < 8; c++)
+      out[c] = lane < nruns ? runs[lane][c] : 0.0f;
+    if (nruns > 1)  // uniform over the workgroup
+    {
+#pragma unroll
+      for (int c = 0; c < 8; c++)
+        out[c] = wave_fold64(out[c]);
+    }
+  }
+}
+
+// The bodies of more than one tile: one workgroup per body (hull_fold_partials), its lane 0 writes the loads.
 __global__ __launch_bounds__(kHullFoldThreads) void k_hulls_fold(const HullFold* __restrict__ folds, int count,
                                                                 const float4* __restrict__ partial,
                                                                 float4* __restrict__ loads)
@@ -178,48 +242,12 @@ __global__ __launch_bounds__(kHullFoldThreads) void k_hulls_fold(const HullFold*
   for (int item = blockIdx.x; item < count; item += gridDim.x)
   {
     const HullFold f = folds[item];
-    const int nruns = (f.tiles + 63) >> 6;  // <= 64
-    // the bound depends on the wave alone: every lane of a wave runs the same steps (whole-wave exchanges)
-    for (int j = wave; j < nruns; j += kHullFoldThreads / 64)
+    float a[8];
+    hull_fold_partials(f, partial, runs, lane, wave, a);
+    if (wave == 0 && lane == 0)
     {
-      const int t = j * 64 + lane;
-      float a[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-      if (t < f.tiles)
-      {
-        const float4 lo = partial[2 * (size_t)(f.slot + t)], hi = partial[2 * (size_t)(f.slot + t) + 1];
-        a[0] = lo.x, a[1] = lo.y, a[2] = lo.z, a[3] = lo.w;
-        a[4] = hi.x, a[5] = hi.y, a[6] = hi.z, a[7] = hi.w;
-      }
-#pragma unroll
-      for (int c = 0; c < 8; c++)
-        a[c] = wave_fold64(a[c]);
-      if (lane < 8)
-      {
-        float v = a[0];
-#pragma unroll
-        for (int c = 1; c < 8; c++)
-          v = lane == c ? a[c] : v;
-        runs[j][lane] = v;
-      }
-    }
-    __syncthreads();
-    if (wave == 0)
-    {
-      float a[8];
-#pragma unroll
-      for (int c = 0; c < 8; c++)
-        a[c] = lane < nruns ? runs[lane][c] : 0.0f;
-      if (nruns > 1)  // uniform over the workgroup
-      {
-#pragma unroll
-        for (int c = 0; c < 8; c++)
-          a[c] = wave_fold64(a[c]);
-      }
-      if (lane == 0)
-      {
-        loads[2 * (size_t)f.body] = make_float4(a[0], a[1], a[2], a[3]);
-        loads[2 * (size_t)f.body + 1] = make_float4(a[4], a[5], a[6], a[7]);
-      }
+      loads[2 * (size_t)f.body] = make_float4(a[0], a[1], a[2], a[3]);
+      loads[2 * (size_t)f.body + 1] = make_float4(a[4], a[5], a[6], a[7]);
     }
     __syncthreads();  // the LDS is rewritten by the next body
   }

@@ -1204,6 +1204,7 @@ struct ocean_hulls
   HullBody* body_table = nullptr;
   HullFold* folds = nullptr;
   float4* partial = nullptr;  // one 8-float partial per tile of a body in `folds`
+  float4* props = nullptr;    // ocean_hulls_set_bodies: two float4 per body
 };
 
 int ocean_hulls_destroy(ocean_hulls* h)
@@ -1212,7 +1213,8 @@ int ocean_hulls_destroy(ocean_hulls* h)
     return OCEAN_OK;
   if (h->fft)
     (void)hipStreamSynchronize(h->fft->stream);
-  for (void* p : {(void*)h->points, (void*)h->tiles, (void*)h->body_table, (void*)h->folds, (void*)h->partial})
+  for (void* p : {(void*)h->points, (void*)h->tiles, (void*)h->body_table, (void*)h->folds, (void*)h->partial,
+                  (void*)h->props})
     if (p)
       (void)hipFree(p);
   delete h;
@@ -1377,6 +1379,102 @@ int ocean_hulls_loads(ocean_hulls* h, ocean_generator* const* gens, const int* c
   call.rho_g = rho_g;
   HIP_TRY(launch_hulls_loads(p, r, water_velocity != 0, call, h->folds, h->n_folds, fft->stream, fft->cus),
           "ocean_hulls_loads");
+  return OCEAN_OK;
+}
+
+// ---- hull dynamics: the bodies stepped from their loads (device/k_hulls_step.h) ----
+int ocean_hulls_set_bodies(ocean_hulls* h, const float* props)
+{
+  if (!h || !props)
+    return fail(OCEAN_ERR_INVALID, "ocean_hulls_set_bodies: null argument");
+  for (int b = 0; b < h->bodies; b++)
+  {
+    const float* q = props + 8 * (size_t)b;
+    const std::string who = "ocean_hulls_set_bodies: body " + std::to_string(b);
+    for (int k = 0; k < 8; k++)
+      if (!std::isfinite(q[k]))
+        return fail(OCEAN_ERR_INVALID, who + " has a non-finite field");
+    if (!(q[0] > 0.0f) || !(q[1] > 0.0f) || !(q[2] > 0.0f) || !(q[3] > 0.0f))
+      return fail(OCEAN_ERR_INVALID, who + " needs a mass and moments > 0");
+    if (q[4] < 0.0f || q[5] < 0.0f)
+      return fail(OCEAN_ERR_INVALID, who + " has a negative damping");
+    if (q[6] != 0.0f && q[6] != 1.0f)
+      return fail(OCEAN_ERR_INVALID, who + " needs kinematic 0 or 1");
+  }
+  // the one allocation of the dynamics: ocean_hulls_step keeps the sums in registers and needs no buffer of
+  // its own for a caller that passes no loads. A later call replaces the properties behind the stream's work.
+  const size_t bytes = (size_t)h->bodies * 2 * sizeof(float4);
+  hipError_t e = hipSuccess;
+  if (!h->props)
+    e = hipMalloc(&h->props, bytes);
+  else
+    e = hipStreamSynchronize(h->fft->stream);
+  if (e != hipSuccess)
+    return alloc_fail(e, "ocean_hulls_set_bodies");
+  HIP_TRY(hipMemcpy(h->props, props, bytes, hipMemcpyHostToDevice), "ocean_hulls_set_bodies");
+  return OCEAN_OK;
+}
+
+void ocean_default_hull_step_settings(ocean_hull_step_settings* s)
+{
+  if (s)
+    *s = ocean_hull_step_settings{1.0f / 60.0f, 1, {0.0f, -9.8f, 0.0f}, 9810.0f, 8, 0.0f, 0};
+}
+
+int ocean_hulls_step(ocean_hulls* h, ocean_generator* const* gens, const int* cascades, int count,
+                     const ocean_hull_step_settings* s, float* poses, const float* wrench_ext, float* loads,
+                     float* point_out)
+{
+  if (!h)
+    return fail(OCEAN_ERR_INVALID, "ocean_hulls_step: null hull set");
+  if (!s || !poses)
+    return fail(OCEAN_ERR_INVALID, "ocean_hulls_step: null settings/poses");
+  // the settings' own rules first: they need neither the set nor a generator
+  if (!(s->dt > 0.0f) || !std::isfinite(s->dt))
+    return fail(OCEAN_ERR_INVALID, "ocean_hulls_step: dt must be finite and > 0");
+  if (s->substeps < 1 || s->substeps > 64)
+    return fail(OCEAN_ERR_INVALID, "ocean_hulls_step: substeps outside 1..64");
+  if (!std::isfinite(s->gravity[0]) || !std::isfinite(s->gravity[1]) || !std::isfinite(s->gravity[2]))
+    return fail(OCEAN_ERR_INVALID, "ocean_hulls_step: gravity must be finite");
+  TRY(check_fixed_point(s->iterations, s->tolerance, "ocean_hulls_step"));
+  if (!(s->rho_g >= 0.0f) || !std::isfinite(s->rho_g))
+    return fail(OCEAN_ERR_INVALID, "ocean_hulls_step: rho_g must be finite and >= 0");
+  if (s->water_velocity != 0 && s->water_velocity != 1)
+    return fail(OCEAN_ERR_INVALID, "ocean_hulls_step: water_velocity must be 0 or 1");
+  SurfaceParams p;
+  ocean_fft* fft;
+  TRY(surface_params(gens, cascades, count, p, fft, "ocean_hulls_step"));
+  TRY(same_plan(gens[0], h->fft, "hull set", "ocean_hulls_step"));
+  if (!h->props)
+    return fail(OCEAN_ERR_INVALID, "ocean_hulls_step: the bodies' properties were never set (ocean_hulls_set_bodies)");
+  SurfaceRates r{};
+  if (s->water_velocity)
+    TRY(surface_rates(gens, cascades, count, fft, r, "ocean_hulls_step"));
+  const bool atlas = surface_query_use_atlas(p, h->instance_points, s->iterations);
+  TRY(surface_atlas(fft, p, atlas, "ocean_hulls_step"));
+  if (atlas)
+    launch_surface_atlas(p, fft->stream, fft->cus);
+  HullCall call{};
+  call.points = h->points;
+  call.tiles = h->tiles;
+  call.bodies = h->body_table;
+  call.poses = poses;
+  call.loads = reinterpret_cast<float4*>(loads);
+  call.partial = h->partial;
+  call.point_out = reinterpret_cast<float4*>(point_out);
+  call.items = h->items;
+  call.iterations = s->iterations;
+  call.tolerance = s->tolerance;
+  call.rho_g = s->rho_g;
+  HullStep st{};
+  st.poses = poses;
+  st.props = h->props;
+  st.ext = reinterpret_cast<const float4*>(wrench_ext);
+  st.h = s->dt / (float)s->substeps;
+  st.gx = s->gravity[0], st.gy = s->gravity[1], st.gz = s->gravity[2];
+  HIP_TRY(launch_hulls_step(p, r, s->water_velocity != 0, call, st, s->substeps, h->folds, h->n_folds, fft->stream,
+                            fft->cus),
+          "ocean_hulls_step");
   return OCEAN_OK;
 }
 

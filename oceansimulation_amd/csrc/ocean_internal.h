@@ -475,6 +475,23 @@ struct HullCall
 // p.atlas non-null: sampled from the atlas, which the caller has repacked (launch_surface_atlas).
 hipError_t launch_hulls_loads(const SurfaceParams& p, const SurfaceRates& r, bool velocity, const HullCall& h,
                               const HullFold* folds, int n_folds, hipStream_t stream, int cus);
+// ocean_hulls_step (device/k_hulls_step.h): what a launch needs besides the HullCall of the loads
+struct HullStep
+{
+  float* poses;         // [bodies][20], stepped in place (HullCall::poses is the same pointer)
+  const float4* props;  // [bodies][2]: (mass, Ix, Iy, Iz), (lin_damp, ang_damp, kinematic, 0)
+  const float4* ext;    // [bodies][2]: (force, 0), (torque about the centre, 0), or null
+  float h;              // dt / substeps
+  float gx, gy, gz;     // gravity
+  int substeps;         // of this launch
+  int last;             // the launch ends with the call's last substep: loads and point_out are written
+};
+
+// `substeps` substeps: one launch when the set has no body of more than one tile (n_folds == 0), else two per
+// substep. h.loads and h.point_out may be null; st.substeps and st.last are set here.
+hipError_t launch_hulls_step(const SurfaceParams& p, const SurfaceRates& r, bool velocity, const HullCall& h,
+                             HullStep st, int substeps, const HullFold* folds, int n_folds, hipStream_t stream,
+                             int cus);
 // Spray emitters (ocean_spray_emit, include/oceanfft.h, device/k_spray.h): the ordered compaction of the
 // emitting texels of the pairs' Jacobian maps into 8-float records. One emitting pair (rate != 0) of the
 // launch: its map and settings, and its index in the request (the id's top four bits).

@@ -396,6 +396,38 @@ Vision::ID HullSet::Loads(const std::vector<Generator*>& generators, const float
   return loads;
 }
 
+void HullSet::SetBodies(const float* props)
+{
+  if (ocean_hulls_set_bodies(hulls, props) != OCEAN_OK)
+    throw std::runtime_error(std::string("HullSet::SetBodies: ") + ocean_last_error());
+}
+
+Vision::ID HullSet::Step(const std::vector<Generator*>& generators, float* posesDevice,
+                         const ocean_hull_step_settings& settings, const float* wrenchExtDevice, bool pointOutput)
+{
+  if (pointOutput && !pointRows)
+  {
+    Vision::Texture2DDesc desc;
+    desc.Width = 2 * (std::size_t)GetInstancePoints();
+    desc.Height = 1;
+    desc.PixelType = Vision::PixelType::RGBA32Float;
+    pointRows = renderDevice->CreateTexture2D(desc);
+  }
+  std::vector<ocean_generator*> gens;
+  std::vector<int> cascades;
+  for (auto* g : generators)
+  {
+    gens.push_back(g->GetHandle());
+    cascades.push_back(0);
+  }
+  const int rc = ocean_hulls_step(hulls, gens.data(), cascades.data(), (int)gens.size(), &settings, posesDevice,
+                                  wrenchExtDevice, static_cast<float*>(renderDevice->GetTexturePointer(loads)),
+                                  pointOutput ? static_cast<float*>(renderDevice->GetTexturePointer(pointRows)) : nullptr);
+  if (rc != OCEAN_OK)
+    throw std::runtime_error(std::string("HullSet::Step: ") + ocean_last_error());
+  return loads;
+}
+
 SprayEmitter::SprayEmitter(Vision::RenderDevice* device, FFTCalculator* fft) : renderDevice(device)
 {
   if (ocean_spray_create(&spray, fft ? fft->GetPlan() : nullptr) != OCEAN_OK)

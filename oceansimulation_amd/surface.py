@@ -13,7 +13,7 @@ import numpy as np
 
 from . import hip
 from .capi import (OCEAN_ERR_INVALID, OceanCamera, OceanCameraLayers, OceanError, OceanFoamDepositSettings, OceanMarch,
-                   OceanShading, OceanSpraySettings, check, lib)
+                   OceanHullStepSettings, OceanShading, OceanSpraySettings, check, lib)
 from .hip import DeviceBuffer
 
 FLOATS_PER_VERTEX = 8  # x, y, z, jacobian, nx, ny, nz, 0 (query: base x, height, base z, ..., residual)
@@ -418,6 +418,57 @@ class HullSet:
         self.loads(sampler, src.ptr, out.ptr, pts.ptr, rho_g, iterations, tolerance, water_velocity)
         self.fft.synchronize()
         return out.to_host((self.bodies, FLOATS_PER_VERTEX)), pts.to_host((self.instance_points, FLOATS_PER_VERTEX))
+
+    def set_bodies(self, props: np.ndarray) -> None:
+        """props: (bodies, 8) float32 (mass, Ix, Iy, Iz, lin_damp, ang_damp, kinematic, 0); what step needs."""
+        props = np.ascontiguousarray(props, np.float32).reshape(self.bodies, FLOATS_PER_VERTEX)
+        check(lib().ocean_hulls_set_bodies(self._h, props.ctypes.data), "ocean_hulls_set_bodies")
+
+    @staticmethod
+    def step_settings(**overrides) -> OceanHullStepSettings:
+        """The library's defaults with `overrides` (dt, substeps, gravity, rho_g, iterations, tolerance,
+        water_velocity)."""
+        s = OceanHullStepSettings()
+        lib().ocean_default_hull_step_settings(ctypes.byref(s))
+        for k, v in overrides.items():
+            if k == "gravity":
+                s.gravity[:] = [float(x) for x in v]
+            elif k in ("substeps", "iterations", "water_velocity"):
+                setattr(s, k, int(v))
+            else:
+                getattr(OceanHullStepSettings, k)  # an unknown name is an AttributeError
+                setattr(s, k, float(v))
+        return s
+
+    def step(self, sampler: SurfaceSampler, poses_ptr: int, settings: OceanHullStepSettings = None, ext_ptr: int = 0,
+             loads_ptr: int = 0, point_out_ptr: int = 0, **overrides) -> None:
+        """Enqueue one ocean_hulls_step on the plan's stream: the device poses (bodies, 20) are stepped in place
+        by settings.dt in settings.substeps substeps under the wave loads, gravity and the device wrenches at
+        ext_ptr (bodies, 8); loads_ptr and point_out_ptr receive the last substep's loads. `overrides` are
+        fields of the settings (step_settings)."""
+        if settings is None:
+            settings = self.step_settings(**overrides)
+        elif overrides:
+            raise TypeError("HullSet.step: pass settings or their fields, not both")
+        check(lib().ocean_hulls_step(self._h, sampler._gens, sampler._cas, len(sampler.pairs), ctypes.byref(settings),
+                                     ctypes.c_void_p(poses_ptr), ctypes.c_void_p(ext_ptr), ctypes.c_void_p(loads_ptr),
+                                     ctypes.c_void_p(point_out_ptr)), "ocean_hulls_step")
+
+    def step_host(self, sampler: SurfaceSampler, poses: np.ndarray, settings: OceanHullStepSettings = None,
+                  ext: np.ndarray = None, calls: int = 1, **overrides):
+        """`calls` successive steps of host poses (bodies, 20): a list of (poses, loads, point_out) after each."""
+        poses = np.ascontiguousarray(poses, np.float32).reshape(self.bodies, 20)
+        buf = DeviceBuffer.from_array(poses)
+        e = DeviceBuffer.from_array(np.ascontiguousarray(ext, np.float32).reshape(self.bodies, 8)) if ext is not None else None
+        out = DeviceBuffer(self.bodies * FLOATS_PER_VERTEX * 4)
+        pts = DeviceBuffer(self.instance_points * FLOATS_PER_VERTEX * 4)
+        results = []
+        for _ in range(calls):
+            self.step(sampler, buf.ptr, settings, e.ptr if e else 0, out.ptr, pts.ptr, **overrides)
+            self.fft.synchronize()
+            results.append((buf.to_host((self.bodies, 20)), out.to_host((self.bodies, FLOATS_PER_VERTEX)),
+                            pts.to_host((self.instance_points, FLOATS_PER_VERTEX))))
+        return results
 
     def close(self) -> None:
         if self._h:
