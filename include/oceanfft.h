@@ -975,6 +975,128 @@ int ocean_hulls_step(ocean_hulls* hulls, ocean_generator* const* gens, const int
  * of at most 32 points share a wave (the same bits either way; tools/hulls_bench.py times both). */
 int ocean_debug_hulls_packing(int enable);
 
+/* ---- Mooring lines: cable chains stepped on the device, wrenches for hulls --------------------------
+ * What produces ocean_hulls_step's wrench_ext for a moored body (a buoy, a barge, a fish-farm cage): every
+ * line is a chain of 2 .. 64 lumped nodes joined by springs that carry tension only, hanging in the water of
+ * ocean_water_kinematics (or in still water), resting on a flat bed, between an anchor fixed in the world and
+ * a fairlead fixed in the frame of a body. One call steps every line through all its substeps in one kernel,
+ * the line's state held on chip in between, and sums the lines' pulls into one wrench per body. Unfused fp32
+ * in a fixed order, so a run replays bit for bit, and a numpy float32 restatement agrees to the bit
+ * (tests/moorings_ref.py).
+ *
+ * ocean_moorings_create. lines: host, n_lines x 16 floats
+ *     0..2 anchor A (world)    3..5 fairlead Lf (body frame; world when the line has no body)
+ *     6 length (unstretched, > 0)    7 EA (> 0, N)    8 CA (internal damping, >= 0, N s)
+ *     9 mass_per_m (> 0)    10 volume_per_m (>= 0)    11 drag_lin per metre (>= 0)    12 drag_quad per metre (>= 0)
+ *     13..15 zero
+ * attach: host, n_lines x 2 int32 (body, nodes): body in -1 .. bodies - 1, -1 for a line with both ends fixed
+ * in the world; nodes in 2 .. 64, both ends counted. The host builds, in fp32, the per-line constants
+ *     l0 = length / (float)(nodes - 1)
+ *     mn = mass_per_m * l0,  vn = volume_per_m * l0,  dl = drag_lin * l0,  dq = drag_quad * l0     (per node)
+ * the table of work items (one wave per item, one lane per node; consecutive lines of at most 32 nodes share
+ * a wave in aligned power-of-two segments, the packing of the hull sets, which ocean_debug_hulls_packing
+ * switches for mooring sets created after it too) and a CSR of the lines of each body in ascending line
+ * index, and copies them to the device of `fft` with the storage of the nodes (32 B per node) and 16 B per
+ * line; later calls run on its stream and allocate nothing.
+ * OCEAN_ERR_INVALID, before any device call: a null out / fft / lines / attach; n_lines outside 1 .. 1048576;
+ * bodies outside 0 .. 1048576; a body or a node count out of range; a non-finite field; a sign rule above
+ * broken or a slot 13..15 that is not zero. */
+typedef struct ocean_moorings ocean_moorings;
+int ocean_moorings_create(ocean_moorings** out, ocean_fft* fft, const float* lines, const int32_t* attach,
+                          int n_lines, int bodies);
+/* Waits for the plan's stream, then frees the set. */
+int ocean_moorings_destroy(ocean_moorings* moorings);
+int ocean_moorings_lines(const ocean_moorings* moorings);
+int64_t ocean_moorings_total_nodes(const ocean_moorings* moorings);   /* sum of the node counts */
+/* The nodes: device, total_nodes x 8 floats, the lines' nodes one after another from the anchor to the
+ * fairlead, rows (x, y, z, T, vx, vy, vz, flags): T the tension of the segment from this node to the next in
+ * the last substep (0 in a line's last node), flags = 1 * wet + 2 * on_bed of the last substep (0 in the end
+ * nodes, which have no water state). The caller may read and write them between calls on the plan's stream
+ * (a checkpoint, a pre-laid catenary); a step reads x, y, z and vx, vy, vz of the interior nodes only. Asking
+ * for the pointer counts as writing the nodes. Null for a null set. */
+float* ocean_moorings_nodes(ocean_moorings* moorings);
+/* One launch: every line's nodes on the straight segment from A to the fairlead's world position P (below),
+ * node i at  A.k + ((float)i / (float)(nodes - 1)) * (P.k - A.k),  velocities, T and flags 0. poses: device,
+ * bodies x 20 floats in the layout of ocean_hulls_loads; null only when no line has a body, else
+ * OCEAN_ERR_INVALID (and for a null set). */
+int ocean_moorings_reset(ocean_moorings* moorings, const float* poses);
+
+typedef struct ocean_mooring_settings {
+  float dt; int32_t substeps;        /* dt finite > 0; substeps 1..256 */
+  float gravity[3];                  /* finite */
+  float rho_g;                       /* finite, >= 0 */
+  int32_t iterations; float tolerance;  /* as ocean_water_kinematics; read when water == 1 */
+  int32_t water;                     /* 0: still water (eta = 0, u = 0); 1: ocean_water_kinematics at the node */
+  float bed_y;                       /* the flat bed's height, finite */
+  float bed_k, bed_c;                /* the bed's stiffness and damping per metre of line, >= 0 */
+} ocean_mooring_settings;
+/* dt 1/60, substeps 8, gravity (0, -9.8, 0), rho_g 9810, iterations 4, tolerance 0, water 0, bed_y -100,
+ * bed_k 1e5, bed_c 1e3. A null pointer is ignored. */
+void ocean_default_mooring_settings(ocean_mooring_settings* settings);
+
+/* Steps the nodes in place by settings.dt in settings.substeps substeps. poses: device, bodies x 20 floats,
+ * read once: the fairleads are frozen during a call (null only when no line has a body). wrench_ext: device,
+ * bodies x 8 floats, every row overwritten, in ocean_hulls_step's layout so that it can be passed straight
+ * on; null only when bodies == 0. line_out: device, n_lines x 8 floats, or null.
+ *
+ * Contract, in unfused fp32, every expression in the order written. h = dt / (float)substeps, computed on the
+ * host; g = gravity; kb = bed_k * l0, cb = bed_c * l0. Per line with n nodes on body b:
+ *   the fairlead, with R, c, v, w from poses[b], the expressions of ocean_hulls_loads:
+ *     d   = (R0*Lf.x + R1*Lf.y) + R2*Lf.z,  (R3*Lf.x + R4*Lf.y) + R5*Lf.z,  (R6*Lf.x + R7*Lf.y) + R8*Lf.z
+ *     P   = c + d;    vp = v + (w.y*d.z - w.z*d.y, w.z*d.x - w.x*d.z, w.x*d.y - w.y*d.x)
+ *     b == -1:  d = 0, P = Lf, vp = 0
+ *   node 0 is held at A with velocity 0 and node n-1 at P with velocity vp, whatever their rows hold.
+ *   Per substep, from the nodes' x and v at its start:
+ *   every segment j = 0 .. n-2, between nodes j and j+1:
+ *     dv    = x[j+1] - x[j];   len = sqrtf((dv.x*dv.x + dv.y*dv.y) + dv.z*dv.z)
+ *     e.k   = len > 0 ? dv.k / len : 0
+ *     strain = (len - l0) / l0
+ *     rate  = (((v[j+1].x - v[j].x)*e.x + (v[j+1].y - v[j].y)*e.y) + (v[j+1].z - v[j].z)*e.z) / l0
+ *     t     = EA*strain + CA*rate;   T[j] = t > 0 ? t : 0        no compression; NaN -> 0
+ *     S[j].k = T[j] * e.k
+ *   every interior node i = 1 .. n-2:
+ *     water == 1:  eta, u, wet = slots 1, 4..6 and 11 of ocean_water_kinematics at (x, y, z): the same
+ *                  arithmetic, the same bits;    water == 0:  u = 0,  wet = (0.0f - y) > 0
+ *     rel   = u - v;   m = sqrtf((rel.x*rel.x + rel.y*rel.y) + rel.z*rel.z)
+ *     k     = wet ? dl + dq*m : 0
+ *     F.k   = ((S[i].k - S[i-1].k) + k*rel.k) + mn*g.k
+ *     wet:       F.y = F.y + rho_g*vn
+ *     pen   = bed_y - y;   pen > 0:   F.y = F.y + kb*pen;   then F.k = F.k - cb*v.k for k = x, y, z;   on_bed
+ *     v'.k  = v.k + h*(F.k / mn);    x'.k = x.k + h*v'.k
+ *   the fairlead: Ff = -S[n-2] is summed over the substeps, sum.k = sum.k + (-S[n-2].k) from +0.0f; after the
+ *   last substep Fm.k = sum.k / (float)substeps. The mean, so that the impulse dt * Fm handed to the hull is the
+ *   one the line received over the call.
+ * line_out row: (Fm.x, Fm.y, Fm.z, T[n-2] of the last substep, T[0] of the last substep, the exact maximum of
+ * T over the line's segments in the last substep, the number of nodes on the bed, the number of wet nodes,
+ * both of the last substep, as floats).
+ * wrench_ext row of body b: (F, the number of its lines as a float, Tq, 0) with, over the body's lines in
+ * ascending line index from +0.0f,  F.k = F.k + Fm.k  and  Tq = Tq + (d.y*Fm.z - d.z*Fm.y, d.z*Fm.x - d.x*Fm.z,
+ * d.x*Fm.y - d.y*Fm.x), the torque about the centre in the hull contract's order; a body without a line gets
+ * zeros.
+ * No transcendental outside the water query: sqrtf and the divisions are correctly rounded.
+ *
+ * The scheme is explicit (semi-implicit Euler per node), so the axial mode of a line bounds the substep:
+ *     h < l0 * sqrt(mass_per_m / EA)
+ * (a steel chain of EA = 1e8 N and 100 kg/m in 2 m segments: h < 2 ms); past it the tensions grow without
+ * bound. This is why substeps go to 256, four times ocean_hulls_step's. CA damps the axial mode.
+ *
+ * Two launches on the plan's stream whatever substeps is, the lines' and the per-body sum's (one when
+ * bodies == 0); a line's positions, velocities and fairlead sum stay in the registers of its wave, or its
+ * segment of a wave, across the substeps. No atomics, no host synchronisation, no allocation.
+ * OCEAN_ERR_INVALID, before any device call: a null set or settings; dt not finite or <= 0; substeps outside
+ * 1..256; a non-finite gravity or bed_y; rho_g, bed_k or bed_c negative or not finite; water other than 0 or
+ * 1; iterations or tolerance outside ocean_water_kinematics' ranges; null poses while a line has a body; a
+ * null wrench_ext while bodies > 0; nodes that were never reset nor written by the caller
+ * (ocean_moorings_nodes). With water == 1 also everything else ocean_water_kinematics rejects (the
+ * (generator, cascade) rules; depth layers that are not set, calculated,
+ * fresh and identical across gens, naming the index in `gens`) and gens[0] on another plan than the set's.
+ * With water == 0 no generator is needed: gens, cascades and count are not read and count may be 0.
+ * Not modelled: bending stiffness, contact between lines or with hulls, bed friction beyond bed_c, lines
+ * of more than 64 nodes. No reference counterpart. */
+int ocean_moorings_step(ocean_moorings* moorings, ocean_generator* const* gens, const int* cascades, int count,
+                        const ocean_mooring_settings* settings, const float* poses, float* wrench_ext,
+                        float* line_out);
+
 /* ---- Persistent foam: per-cascade accumulation, coverage counts, sampler ------------------------
  * The Jacobian map and slot 3 of the samplers say where the surface is folding now. Foam is a history:
  * whitecaps are born where the surface compresses, ride with the water and fade over seconds. The

@@ -197,6 +197,50 @@ private:
   Vision::ID pointRows = 0;
 };
 
+// Mooring lines (ocean_moorings, oceanfft.h): chains of lumped nodes between anchors fixed in the world and
+// fairleads on the bodies of a HullSet, stepped on the device; per call one wrench per body out, in the layout
+// HullSet::Step takes as wrenchExtDevice.
+class MooringSet
+{
+public:
+  // lines: nLines x 16 host floats (anchor, fairlead, length, EA, CA, mass_per_m, volume_per_m, drag_lin,
+  // drag_quad, 0, 0, 0); attach: nLines x 2 host int32 (body or -1, nodes 2..64). Copied to the device; throws
+  // std::runtime_error on invalid arguments.
+  MooringSet(Vision::RenderDevice* device, FFTCalculator* fft, const float* lines, const int32_t* attach, int nLines,
+             int bodies);
+  ~MooringSet();
+  MooringSet(const MooringSet&) = delete;
+  MooringSet& operator=(const MooringSet&) = delete;
+
+  int GetLines() const { return ocean_moorings_lines(moorings); }
+  int64_t GetTotalNodes() const { return ocean_moorings_total_nodes(moorings); }
+  ocean_moorings* GetHandle() const { return moorings; }
+  // The nodes, totalNodes x 8 device floats (x, y, z, T, vx, vy, vz, flags), for the caller to read and write.
+  float* GetNodesDevice() { return ocean_moorings_nodes(moorings); }
+
+  // Every line straight from its anchor to its fairlead, at rest. posesDevice: bodies x 20 device floats (null
+  // when no line has a body).
+  void Reset(const float* posesDevice);
+  // Steps the nodes by settings.dt under the frozen posesDevice. generators: the water of settings.water == 1
+  // (each with Generator::SetDepthLayers() and a CalculateKinematics() since its last CalculateOcean); empty
+  // for still water. Returns the wrench texture, 2*bodies x 1 RGBA32F texels: per body (Fx, Fy, Fz, lines),
+  // (Tx, Ty, Tz about the centre, 0); GetWrenchDevice() is its device pointer for HullSet::Step. With
+  // lineOutput the per-line rows (mean fairlead force, fairlead tension), (anchor tension, largest tension,
+  // nodes on the bed, wet nodes) land in GetLineOutput() (2*lines x 1 texels). Enqueued on the device's
+  // stream: no host synchronisation.
+  Vision::ID Step(const std::vector<Generator*>& generators, const ocean_mooring_settings& settings,
+                  const float* posesDevice, bool lineOutput = false);
+  const float* GetWrenchDevice() const;
+  Vision::ID GetLineOutput() const { return lineRows; }
+
+private:
+  Vision::RenderDevice* renderDevice = nullptr;
+  ocean_moorings* moorings = nullptr;
+  int bodyCount = 0;
+  Vision::ID wrench = 0;
+  Vision::ID lineRows = 0;
+};
+
 // Emitters at breaking crests (ocean_spray, oceanfft.h): spray, whitecap sprites, splash sounds. Per call the
 // texels of the generators' Jacobian maps under their thresholds, thinned by rate * dt, become one ordered,
 // dense list of records with the position and velocity of their water particles; the count stays on the

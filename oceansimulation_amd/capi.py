@@ -121,6 +121,26 @@ class OceanHullStepSettings(ctypes.Structure):
 assert ctypes.sizeof(OceanHullStepSettings) == 36
 
 
+class OceanMooringSettings(ctypes.Structure):
+    """ocean_mooring_settings: one ocean_moorings_step call's parameters, 48 bytes."""
+
+    _fields_ = [
+        ("dt", ctypes.c_float),
+        ("substeps", ctypes.c_int32),
+        ("gravity", ctypes.c_float * 3),
+        ("rho_g", ctypes.c_float),
+        ("iterations", ctypes.c_int32),
+        ("tolerance", ctypes.c_float),
+        ("water", ctypes.c_int32),
+        ("bed_y", ctypes.c_float),
+        ("bed_k", ctypes.c_float),
+        ("bed_c", ctypes.c_float),
+    ]
+
+
+assert ctypes.sizeof(OceanMooringSettings) == 48
+
+
 class OceanCamera(ctypes.Structure):
     """ocean_camera: position, world-space basis (viewInverse columns 0, 1 and -column 2), lens, 64 bytes."""
 
@@ -286,6 +306,14 @@ SIGNATURES = {
     "ocean_hulls_set_bodies": (_i, [_vp, _vp]),
     "ocean_default_hull_step_settings": (None, [ctypes.POINTER(OceanHullStepSettings)]),
     "ocean_hulls_step": (_i, [_vp, _vp, _vp, _i, ctypes.POINTER(OceanHullStepSettings), _vp, _vp, _vp, _vp]),
+    "ocean_moorings_create": (_i, [ctypes.POINTER(_vp), _vp, _vp, _vp, _i, _i]),
+    "ocean_moorings_destroy": (_i, [_vp]),
+    "ocean_moorings_lines": (_i, [_vp]),
+    "ocean_moorings_total_nodes": (ctypes.c_int64, [_vp]),
+    "ocean_moorings_nodes": (_vp, [_vp]),
+    "ocean_moorings_reset": (_i, [_vp, _vp]),
+    "ocean_default_mooring_settings": (None, [ctypes.POINTER(OceanMooringSettings)]),
+    "ocean_moorings_step": (_i, [_vp, _vp, _vp, _i, ctypes.POINTER(OceanMooringSettings), _vp, _vp, _vp]),
     "ocean_default_spray_settings": (None, [ctypes.POINTER(OceanSpraySettings)]),
     "ocean_spray_create": (_i, [ctypes.POINTER(_vp), _vp]),
     "ocean_spray_destroy": (_i, [_vp]),

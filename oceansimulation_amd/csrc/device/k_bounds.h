@@ -20,6 +20,7 @@
 
 #include "device/lane_xchg.h"
 #include "device/memory.h"
+#include "device/wave_tile.h"
 
 namespace oceanfft
 {
@@ -40,15 +41,7 @@ struct BoundsBuild
   int cascades;
 };
 
-// min (MAX false) or max (MAX true) of v and the value of lane (lane ^ STRIDE), in every lane
-template <int STRIDE, bool MAX>
-__device__ __forceinline__ float bounds_fold_step(float v)
-{
-  float a, b;
-  xor_lane_pair<STRIDE>(v, a, b);
-  return MAX ? fmaxf(a, b) : fminf(a, b);
-}
-
+// bounds_fold_step: device/wave_tile.h (device/k_moorings.h folds a line's largest tension with it)
 template <bool MAX>
 __device__ __forceinline__ float bounds_wave_fold(float v)
 {

@@ -29,6 +29,7 @@
 
 #include "device/lane_xchg.h"
 #include "device/surface_sample.h"
+#include "device/wave_tile.h"
 
 namespace oceanfft
 {
@@ -78,35 +79,10 @@ __device__ __forceinline__ float wave_fold_segments(float v, int seg)
   return v;
 }
 
-// HullTile, HullFold and HullCall: ocean_internal.h (the host builds the tables)
-
-// The lane's body, point and point_out row in a work item: a tile of one body, or (tile.seg > 0) tile.count
-// small bodies from tile.body on, one per aligned segment of tile.seg lanes
-struct HullLane
-{
-  int64_t row;
-  int body, point;
-  bool active, active_segment;  // the lane holds a point; its segment holds a body
-};
-
+// HullTile, HullFold and HullCall: ocean_internal.h (the host builds the tables); HullLane: device/wave_tile.h
 __device__ __forceinline__ HullLane hull_tile_lane(const HullCall& h, const HullTile& tile, int lane)
 {
-  HullLane l{tile.offset + lane, tile.body, tile.first + lane, lane < tile.count, true};
-  if (tile.seg > 0)
-  {
-    const int j = lane >> (31 - __clz(tile.seg)), i = lane & (tile.seg - 1);
-    l.active = false;
-    l.active_segment = j < tile.count;
-    if (l.active_segment)
-    {
-      l.body += j;
-      const HullBody hb = h.bodies[l.body];
-      l.active = i < hb.count;
-      l.point = hb.first + i;
-      l.row = hb.offset + i;
-    }
-  }
-  return l;
+  return hull_tile_lane(h.bodies, tile, lane);
 }
 
 // One point's load (the contract's a_i) from its row L = (l0, l1) of the points and its body's pose P (R, c, v, w: the

@@ -99,71 +99,96 @@ __global__ __launch_bounds__(kKinematicsTile) void k_kinematics_pack(FrameParams
   }
 }
 
-// ocean_water_kinematics (include/oceanfft.h): one lane per world position. The fixed point is the
+// What ocean_water_kinematics returns for one world position (include/oceanfft.h): the fixed point is the
 // query's (surface_base_point on the maps); the chain then runs once more from the base point with the
-// layers' taps beside the maps', layer l and, where the blend factor is not 0, layer l + 1.
-__global__ __launch_bounds__(256) void k_water_kinematics(SurfaceParams p, WaterLayers w, const float* __restrict__ xyz,
+// layers' taps beside the maps', layer l and, where the blend factor is not 0, layer l + 1. The fixed-point
+// loop is lane-divergent. One definition for k_water_kinematics and the mooring lines' nodes
+// (device/k_moorings.h): the same expressions, the same bits.
+struct WaterPoint
+{
+  float bx, eta, bz, res;
+  float ux, uy, uz, head;
+  float d, f;
+  int l;
+  bool wet;
+};
+
+__device__ __forceinline__ WaterPoint water_point_kinematics(const SurfaceParams& p, const WaterLayers& w, float qx,
+                                                             float qy, float qz, int iterations, float tolerance)
+{
+#pragma clang fp contract(off)
+  const size_t nn = (size_t)p.n * p.n;
+  float bx = qx, bz = qz;  // the base point p
+  float vx, eta, vz;
+  surface_base_point<false>(p, qx, qz, iterations, tolerance, bx, bz, vx, eta, vz);
+  const float res = surface_residual(qx, qz, vx, vz);
+  const float s = eta - qy;
+  const bool wet = s > 0.0f;
+  const float d = wet ? s : 0.0f;  // max(s, 0), NaN -> 0
+  int l = 0;
+  float f = 0.0f;
+  if (d > w.d[0])
+  {
+    l = w.layers - 1;
+    if (!(d >= w.d[l]))
+    {
+      l = 0;
+      while (w.d[l + 1] <= d)  // ends: d < d[layers - 1]
+        l++;
+      f = (d - w.d[l]) / (w.d[l + 1] - w.d[l]);
+    }
+  }
+  float px = bx, pz = bz, ux = 0.0f, uy = 0.0f, uz = 0.0f, head = 0.0f;
+  for (int c = 0; c < p.count; c++)
+  {
+    const float u = px / p.c[c].plane, v = pz / p.c[c].plane;
+    const LinearTaps k = linear_repeat_taps(p.n, u, v);
+    const float sc = p.c[c].scale;
+    const float* a0 = reinterpret_cast<const float*>(w.map[c] + (size_t)(2 * l) * nn);
+    const float* a1 = reinterpret_cast<const float*>(w.map[c] + (size_t)(2 * l + 1) * nn);
+    float v0w = linear_channel<4>(a0, k, 3), v0x = linear_channel<4>(a0, k, 0);
+    float v1x = linear_channel<4>(a1, k, 0), v1z = linear_channel<4>(a1, k, 2);
+    if (f != 0.0f)
+    {
+      const float* b0 = a0 + 8 * nn;
+      const float* b1 = a1 + 8 * nn;
+      v0w = v0w + f * (linear_channel<4>(b0, k, 3) - v0w);
+      v0x = v0x + f * (linear_channel<4>(b0, k, 0) - v0x);
+      v1x = v1x + f * (linear_channel<4>(b1, k, 0) - v1x);
+      v1z = v1z + f * (linear_channel<4>(b1, k, 2) - v1z);
+    }
+    ux += sc * v0w;
+    uy += v0x;
+    uz += sc * v1x;
+    head += v1z;
+    const float* hm = reinterpret_cast<const float*>(p.c[c].height);
+    const float* dm = reinterpret_cast<const float*>(p.c[c].disp);
+    px += sc * linear_channel<4>(hm, k, 3);
+    pz += sc * linear_channel<4>(dm, k, 0);
+  }
+  return WaterPoint{bx, eta, bz, res, ux, uy, uz, head, d, f, l, wet};
+}
+
+// ocean_water_kinematics (include/oceanfft.h): one lane per world position. `inline` for its linkage: this
+// header is also included by launch_moorings.hip, which does not launch the kernel and must not define it again
+// (clang notes that CUDA would ignore the keyword on a kernel; it does give the host stub vague linkage).
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wcuda-compat"
+inline __global__ __launch_bounds__(256) void k_water_kinematics(SurfaceParams p, WaterLayers w, const float* __restrict__ xyz,
                                                           int64_t count, int iterations, float tolerance,
                                                           float4* __restrict__ out)
 {
 #pragma clang fp contract(off)
-  const size_t nn = (size_t)p.n * p.n;
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < count;
        idx += (int64_t)gridDim.x * blockDim.x)
   {
-    const float qx = xyz[3 * idx], qy = xyz[3 * idx + 1], qz = xyz[3 * idx + 2];
-    float bx = qx, bz = qz;  // the base point p
-    float vx, eta, vz;
-    surface_base_point<false>(p, qx, qz, iterations, tolerance, bx, bz, vx, eta, vz);
-    const float res = surface_residual(qx, qz, vx, vz);
-    const float s = eta - qy;
-    const bool wet = s > 0.0f;
-    const float d = wet ? s : 0.0f;  // max(s, 0), NaN -> 0
-    int l = 0;
-    float f = 0.0f;
-    if (d > w.d[0])
-    {
-      l = w.layers - 1;
-      if (!(d >= w.d[l]))
-      {
-        l = 0;
-        while (w.d[l + 1] <= d)  // ends: d < d[layers - 1]
-          l++;
-        f = (d - w.d[l]) / (w.d[l + 1] - w.d[l]);
-      }
-    }
-    float px = bx, pz = bz, ux = 0.0f, uy = 0.0f, uz = 0.0f, head = 0.0f;
-    for (int c = 0; c < p.count; c++)
-    {
-      const float u = px / p.c[c].plane, v = pz / p.c[c].plane;
-      const LinearTaps k = linear_repeat_taps(p.n, u, v);
-      const float sc = p.c[c].scale;
-      const float* a0 = reinterpret_cast<const float*>(w.map[c] + (size_t)(2 * l) * nn);
-      const float* a1 = reinterpret_cast<const float*>(w.map[c] + (size_t)(2 * l + 1) * nn);
-      float v0w = linear_channel<4>(a0, k, 3), v0x = linear_channel<4>(a0, k, 0);
-      float v1x = linear_channel<4>(a1, k, 0), v1z = linear_channel<4>(a1, k, 2);
-      if (f != 0.0f)
-      {
-        const float* b0 = a0 + 8 * nn;
-        const float* b1 = a1 + 8 * nn;
-        v0w = v0w + f * (linear_channel<4>(b0, k, 3) - v0w);
-        v0x = v0x + f * (linear_channel<4>(b0, k, 0) - v0x);
-        v1x = v1x + f * (linear_channel<4>(b1, k, 0) - v1x);
-        v1z = v1z + f * (linear_channel<4>(b1, k, 2) - v1z);
-      }
-      ux += sc * v0w;
-      uy += v0x;
-      uz += sc * v1x;
-      head += v1z;
-      const float* hm = reinterpret_cast<const float*>(p.c[c].height);
-      const float* dm = reinterpret_cast<const float*>(p.c[c].disp);
-      px += sc * linear_channel<4>(hm, k, 3);
-      pz += sc * linear_channel<4>(dm, k, 0);
-    }
-    out[3 * idx] = make_float4(bx, eta, bz, res);
-    out[3 * idx + 1] = make_float4(ux, uy, uz, head);
-    out[3 * idx + 2] = make_float4(d, (float)l, f, wet ? 1.0f : 0.0f);
+    const WaterPoint q =
+        water_point_kinematics(p, w, xyz[3 * idx], xyz[3 * idx + 1], xyz[3 * idx + 2], iterations, tolerance);
+    out[3 * idx] = make_float4(q.bx, q.eta, q.bz, q.res);
+    out[3 * idx + 1] = make_float4(q.ux, q.uy, q.uz, q.head);
+    out[3 * idx + 2] = make_float4(q.d, (float)q.l, q.f, q.wet ? 1.0f : 0.0f);
   }
 }
+#pragma clang diagnostic pop
 
 }  // namespace oceanfft

@@ -88,6 +88,21 @@ __device__ __forceinline__ void xor_lane_pair(float v, float& a, float& b)
   }
 }
 
+// Beside the xor exchange, the shift of a chain (a mooring line's nodes, device/k_moorings.h): within aligned
+// segments of `seg` lanes (a power of two; 64: the whole wave) every lane gets the value of the lane STEP
+// places on in its own segment, STEP = +1 the next lane's, -1 the previous one's. One ds_bpermute_b32, the LDS
+// crossbar without LDS memory or a barrier. The source index wraps inside the segment, so no lane reads across
+// a segment boundary: a segment's last (first) lane gets its first (last) lane's value, which callers do not
+// use. A bpermute reads the registers of lanes that EXEC leaves out as undefined: callers keep the whole wave
+// active, as for xor_lane_pair.
+template <int STEP>
+__device__ __forceinline__ float segment_shift(float v, int lane, int seg)
+{
+  static_assert(STEP == 1 || STEP == -1, "the next or the previous lane");
+  const int src = (lane & ~(seg - 1)) | ((lane + STEP) & (seg - 1));
+  return __int_as_float(__builtin_amdgcn_ds_bpermute(src << 2, __float_as_int(v)));
+}
+
 template <int LB>
 __device__ __forceinline__ void swap_lane_bit_f(float& lo, float& hi)
 {

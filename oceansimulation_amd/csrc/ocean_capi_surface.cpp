@@ -530,15 +530,12 @@ float* ocean_generator_kinematics_map(ocean_generator* g, int c, int layer, int 
   return reinterpret_cast<float*>(g->kin + nn * (((size_t)c * g->depths.layers + layer) * 2 + image));
 }
 
-int ocean_water_kinematics(ocean_generator* const* gens, const int* cascades, int count, const float* xyz,
-                           int64_t points, int iterations, float tolerance, float* out)
+// The layer maps of the pairs surface_params accepted, beside SurfaceParams' maps: every generator's layers
+// calculated, fresh and of gens[0]'s depth list
+static int water_layers(ocean_generator* const* gens, const int* cascades, int count, const ocean_fft* fft,
+                        WaterLayers& w, const char* who)
 {
-  const char* who = "ocean_water_kinematics";
-  SurfaceParams p;
-  ocean_fft* fft;
-  TRY(surface_params(gens, cascades, count, p, fft, who));
-  TRY(check_fixed_point(iterations, tolerance, who));
-  WaterLayers w{};
+  w = WaterLayers{};
   const KinematicsDepths& first = gens[0]->depths;
   const size_t nn = (size_t)fft->n * fft->n;
   for (int i = 0; i < count; i++)
@@ -557,6 +554,19 @@ int ocean_water_kinematics(ocean_generator* const* gens, const int* cascades, in
   w.layers = first.layers;
   for (int l = 0; l < first.layers; l++)
     w.d[l] = first.d[l];
+  return OCEAN_OK;
+}
+
+int ocean_water_kinematics(ocean_generator* const* gens, const int* cascades, int count, const float* xyz,
+                           int64_t points, int iterations, float tolerance, float* out)
+{
+  const char* who = "ocean_water_kinematics";
+  SurfaceParams p;
+  ocean_fft* fft;
+  TRY(surface_params(gens, cascades, count, p, fft, who));
+  TRY(check_fixed_point(iterations, tolerance, who));
+  WaterLayers w;
+  TRY(water_layers(gens, cascades, count, fft, w, who));
   TRY(check_points(points, xyz, out, who));
   HIP_TRY(launch_water_kinematics(p, w, xyz, points, iterations, tolerance, reinterpret_cast<float4*>(out),
                                   fft->stream, fft->cus),
@@ -1192,6 +1202,28 @@ int ocean_debug_hulls_packing(int enable)
   return OCEAN_OK;
 }
 
+// The power of two `count` lanes fit in
+static int lane_segment(int count)
+{
+  int seg = 1;
+  while (seg < count)
+    seg *= 2;
+  return seg;
+}
+
+// The consecutive entries from b on that share a wave: those with b's segment size, as many as fit (1: b has
+// waves of its own). counts: n x 2 int32 with the lane count second (a hull set's ranges, a mooring set's
+// attach): the packing of the hull sets' bodies and the mooring sets' lines.
+static int packed_run(int b, int n, const int32_t* counts)
+{
+  const int seg = lane_segment(counts[2 * b + 1]);
+  int run = 1;
+  while (g_hulls_pack && seg <= kHullTilePoints / 2 && run < kHullTilePoints / seg && b + run < n &&
+         lane_segment(counts[2 * (b + run) + 1]) == seg)
+    run++;
+  return run;
+}
+
 struct ocean_hulls
 {
   ocean_fft* fft = nullptr;
@@ -1262,12 +1294,6 @@ int ocean_hulls_create(ocean_hulls** out, ocean_fft* fft, const float* points, i
   std::vector<HullFold> folds;
   tiles.reserve((size_t)n_tiles);
   int slot = 0;
-  auto segment = [&](int b) {  // the power of two body b's points fit in
-    int seg = 1;
-    while (seg < ranges[2 * b + 1])
-      seg *= 2;
-    return seg;
-  };
   int64_t rows = 0;
   for (int b = 0; b < bodies; b++)
   {
@@ -1277,11 +1303,8 @@ int ocean_hulls_create(ocean_hulls** out, ocean_fft* fft, const float* points, i
   for (int b = 0; b < bodies; b++)
   {
     const int first = ranges[2 * b], count = ranges[2 * b + 1];
-    const int seg = segment(b);
-    int run = 1;  // consecutive bodies with this segment size, as many as fit a wave
-    while (g_hulls_pack && seg <= kHullTilePoints / 2 && run < kHullTilePoints / seg && b + run < bodies &&
-           segment(b + run) == seg)
-      run++;
+    const int seg = lane_segment(count);
+    const int run = packed_run(b, bodies, ranges);
     if (run > 1)
     {
       HullTile t{};
@@ -1475,6 +1498,268 @@ int ocean_hulls_step(ocean_hulls* h, ocean_generator* const* gens, const int* ca
   HIP_TRY(launch_hulls_step(p, r, s->water_velocity != 0, call, st, s->substeps, h->folds, h->n_folds, fft->stream,
                             fft->cus),
           "ocean_hulls_step");
+  return OCEAN_OK;
+}
+
+// ---- mooring lines: cable chains stepped on the device, wrenches for hulls (device/k_moorings.h) ----
+struct ocean_moorings
+{
+  ocean_fft* fft = nullptr;
+  int lines = 0, bodies = 0;
+  int attached = 0;  // lines with a body
+  int64_t total_nodes = 0;
+  int items = 0;
+  bool placed = false;  // the nodes were reset, or handed to the caller to write
+  HullTile* tiles = nullptr;
+  HullBody* table = nullptr;
+  MooringLine* consts = nullptr;
+  int* start = nullptr;  // [bodies + 1]
+  int* order = nullptr;  // [attached]
+  float4* nodes = nullptr;
+  float4* fm = nullptr;
+};
+
+int ocean_moorings_destroy(ocean_moorings* m)
+{
+  if (!m)
+    return OCEAN_OK;
+  if (m->fft)
+    (void)hipStreamSynchronize(m->fft->stream);
+  for (void* p : {(void*)m->tiles, (void*)m->table, (void*)m->consts, (void*)m->start, (void*)m->order,
+                  (void*)m->nodes, (void*)m->fm})
+    if (p)
+      (void)hipFree(p);
+  delete m;
+  return OCEAN_OK;
+}
+
+int ocean_moorings_create(ocean_moorings** out, ocean_fft* fft, const float* lines, const int32_t* attach, int n_lines,
+                          int bodies)
+{
+  if (!out || !fft || !lines || !attach)
+    return fail(OCEAN_ERR_INVALID, "ocean_moorings_create: null argument");
+  *out = nullptr;
+  if (n_lines < 1 || n_lines > 1048576)
+    return fail(OCEAN_ERR_INVALID, "ocean_moorings_create: n_lines outside 1..1048576");
+  if (bodies < 0 || bodies > 1048576)
+    return fail(OCEAN_ERR_INVALID, "ocean_moorings_create: bodies outside 0..1048576");
+  for (int i = 0; i < n_lines; i++)
+  {
+    const float* l = lines + 16 * (size_t)i;
+    const std::string who = "ocean_moorings_create: line " + std::to_string(i);
+    if (attach[2 * i] < -1 || attach[2 * i] >= bodies)
+      return fail(OCEAN_ERR_INVALID, who + " has a body outside -1.." + std::to_string(bodies - 1));
+    if (attach[2 * i + 1] < 2 || attach[2 * i + 1] > kMooringMaxNodes)
+      return fail(OCEAN_ERR_INVALID, who + " has a node count outside 2..64");
+    for (int k = 0; k < 16; k++)
+      if (!std::isfinite(l[k]))
+        return fail(OCEAN_ERR_INVALID, who + " has a non-finite field");
+    if (!(l[6] > 0.0f) || !(l[7] > 0.0f) || !(l[9] > 0.0f))
+      return fail(OCEAN_ERR_INVALID, who + " needs length, EA and mass_per_m > 0");
+    if (l[8] < 0.0f || l[10] < 0.0f || l[11] < 0.0f || l[12] < 0.0f)
+      return fail(OCEAN_ERR_INVALID, who + " needs CA, volume_per_m and drag coefficients >= 0");
+    if (l[13] != 0.0f || l[14] != 0.0f || l[15] != 0.0f)
+      return fail(OCEAN_ERR_INVALID, who + " needs slots 13..15 zero");
+  }
+
+  // the lines' constants and node rows, the work items in the order of the lines (ocean_hulls_create's
+  // packing), and the CSR of each body's lines in ascending line index
+  std::vector<MooringLine> consts((size_t)n_lines);
+  std::vector<HullBody> table((size_t)n_lines);
+  std::vector<HullTile> tiles;
+  std::vector<int> start((size_t)bodies + 1, 0), order;
+  int64_t rows = 0;
+  for (int i = 0; i < n_lines; i++)
+  {
+    const float* l = lines + 16 * (size_t)i;
+    const int nodes = attach[2 * i + 1];
+    const float l0 = l[6] / (float)(nodes - 1);
+    MooringLine c{};
+    c.a = make_float4(l[0], l[1], l[2], l0);
+    c.f = make_float4(l[3], l[4], l[5], l[7]);
+    c.c = make_float4(l[8], l[9] * l0, l[10] * l0, l[11] * l0);
+    c.dq = l[12] * l0;
+    c.body = attach[2 * i];
+    c.nodes = nodes;
+    consts[i] = c;
+    table[i] = HullBody{rows, (int)rows, nodes};
+    rows += nodes;
+    if (c.body >= 0)
+      start[(size_t)c.body + 1]++;
+  }
+  for (int b = 0; b < bodies; b++)
+    start[(size_t)b + 1] += start[b];
+  order.resize((size_t)start[bodies]);
+  {
+    std::vector<int> fill(start.begin(), start.end() - 1);
+    for (int i = 0; i < n_lines; i++)
+      if (consts[i].body >= 0)
+        order[(size_t)fill[consts[i].body]++] = i;
+  }
+  for (int i = 0; i < n_lines; i++)
+  {
+    const int run = packed_run(i, n_lines, attach);
+    HullTile t{};
+    t.body = i;
+    t.slot = -1;
+    if (run > 1)
+    {
+      t.count = run;
+      t.seg = lane_segment(attach[2 * i + 1]);
+      i += run - 1;
+    }
+    else
+    {
+      t.offset = table[i].offset;
+      t.first = table[i].first;
+      t.count = table[i].count;
+    }
+    tiles.push_back(t);
+  }
+
+  auto* m = new ocean_moorings();
+  m->fft = fft;
+  m->lines = n_lines;
+  m->bodies = bodies;
+  m->attached = (int)order.size();
+  m->total_nodes = rows;
+  m->items = (int)tiles.size();
+  hipError_t e = hipMalloc(&m->tiles, tiles.size() * sizeof(HullTile));
+  if (e == hipSuccess)
+    e = hipMalloc(&m->table, table.size() * sizeof(HullBody));
+  if (e == hipSuccess)
+    e = hipMalloc(&m->consts, consts.size() * sizeof(MooringLine));
+  if (e == hipSuccess)
+    e = hipMalloc(&m->start, start.size() * sizeof(int));
+  if (e == hipSuccess && !order.empty())
+    e = hipMalloc(&m->order, order.size() * sizeof(int));
+  if (e == hipSuccess)
+    e = hipMalloc(&m->nodes, (size_t)rows * 2 * sizeof(float4));
+  if (e == hipSuccess)
+    e = hipMalloc(&m->fm, (size_t)n_lines * sizeof(float4));
+  // synchronous copies from these pageable buffers: complete on return
+  if (e == hipSuccess)
+    e = hipMemcpy(m->tiles, tiles.data(), tiles.size() * sizeof(HullTile), hipMemcpyHostToDevice);
+  if (e == hipSuccess)
+    e = hipMemcpy(m->table, table.data(), table.size() * sizeof(HullBody), hipMemcpyHostToDevice);
+  if (e == hipSuccess)
+    e = hipMemcpy(m->consts, consts.data(), consts.size() * sizeof(MooringLine), hipMemcpyHostToDevice);
+  if (e == hipSuccess)
+    e = hipMemcpy(m->start, start.data(), start.size() * sizeof(int), hipMemcpyHostToDevice);
+  if (e == hipSuccess && !order.empty())
+    e = hipMemcpy(m->order, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice);
+  if (e != hipSuccess)
+  {
+    m->fft = nullptr;
+    ocean_moorings_destroy(m);
+    return alloc_fail(e, "ocean_moorings_create");
+  }
+  *out = m;
+  return OCEAN_OK;
+}
+
+int ocean_moorings_lines(const ocean_moorings* m) { return m ? m->lines : 0; }
+
+int64_t ocean_moorings_total_nodes(const ocean_moorings* m) { return m ? m->total_nodes : 0; }
+
+float* ocean_moorings_nodes(ocean_moorings* m)
+{
+  if (!m)
+    return nullptr;
+  m->placed = true;  // the caller may write them
+  return reinterpret_cast<float*>(m->nodes);
+}
+
+// What both launches of a set share
+static MooringCall mooring_call(const ocean_moorings* m, const float* poses)
+{
+  MooringCall c{};
+  c.tiles = m->tiles;
+  c.table = m->table;
+  c.lines = m->consts;
+  c.poses = poses;
+  c.nodes = m->nodes;
+  c.fm = m->fm;
+  c.items = m->items;
+  return c;
+}
+
+int ocean_moorings_reset(ocean_moorings* m, const float* poses)
+{
+  if (!m)
+    return fail(OCEAN_ERR_INVALID, "ocean_moorings_reset: null mooring set");
+  if (!poses && m->attached > 0)
+    return fail(OCEAN_ERR_INVALID, "ocean_moorings_reset: null poses, and a line has a body");
+  HIP_TRY(launch_moorings_reset(mooring_call(m, poses), m->fft->stream, m->fft->cus), "ocean_moorings_reset");
+  m->placed = true;
+  return OCEAN_OK;
+}
+
+void ocean_default_mooring_settings(ocean_mooring_settings* s)
+{
+  if (s)
+    *s = ocean_mooring_settings{1.0f / 60.0f, 8, {0.0f, -9.8f, 0.0f}, 9810.0f, 4, 0.0f, 0, -100.0f, 1e5f, 1e3f};
+}
+
+int ocean_moorings_step(ocean_moorings* m, ocean_generator* const* gens, const int* cascades, int count,
+                        const ocean_mooring_settings* s, const float* poses, float* wrench_ext, float* line_out)
+{
+  const char* who = "ocean_moorings_step";
+  if (!m)
+    return fail(OCEAN_ERR_INVALID, "ocean_moorings_step: null mooring set");
+  if (!s)
+    return fail(OCEAN_ERR_INVALID, "ocean_moorings_step: null settings");
+  // the settings' own rules first: they need neither the set nor a generator
+  if (!(s->dt > 0.0f) || !std::isfinite(s->dt))
+    return fail(OCEAN_ERR_INVALID, "ocean_moorings_step: dt must be finite and > 0");
+  if (s->substeps < 1 || s->substeps > 256)
+    return fail(OCEAN_ERR_INVALID, "ocean_moorings_step: substeps outside 1..256");
+  if (!std::isfinite(s->gravity[0]) || !std::isfinite(s->gravity[1]) || !std::isfinite(s->gravity[2]))
+    return fail(OCEAN_ERR_INVALID, "ocean_moorings_step: gravity must be finite");
+  if (!(s->rho_g >= 0.0f) || !std::isfinite(s->rho_g))
+    return fail(OCEAN_ERR_INVALID, "ocean_moorings_step: rho_g must be finite and >= 0");
+  TRY(check_fixed_point(s->iterations, s->tolerance, who));
+  if (s->water != 0 && s->water != 1)
+    return fail(OCEAN_ERR_INVALID, "ocean_moorings_step: water must be 0 or 1");
+  if (!std::isfinite(s->bed_y))
+    return fail(OCEAN_ERR_INVALID, "ocean_moorings_step: bed_y must be finite");
+  if (!(s->bed_k >= 0.0f) || !std::isfinite(s->bed_k) || !(s->bed_c >= 0.0f) || !std::isfinite(s->bed_c))
+    return fail(OCEAN_ERR_INVALID, "ocean_moorings_step: bed_k and bed_c must be finite and >= 0");
+  if (!poses && m->attached > 0)
+    return fail(OCEAN_ERR_INVALID, "ocean_moorings_step: null poses, and a line has a body");
+  if (!wrench_ext && m->bodies > 0)
+    return fail(OCEAN_ERR_INVALID, "ocean_moorings_step: null wrench_ext, and the set has bodies");
+  if (!m->placed)
+    return fail(OCEAN_ERR_INVALID, "ocean_moorings_step: the nodes were never reset nor written "
+                                   "(ocean_moorings_reset, ocean_moorings_nodes)");
+  SurfaceParams p{};
+  WaterLayers w{};
+  if (s->water)
+  {
+    ocean_fft* fft;
+    TRY(surface_params(gens, cascades, count, p, fft, who));
+    TRY(same_plan(gens[0], m->fft, "mooring set", who));
+    TRY(water_layers(gens, cascades, count, fft, w, who));
+  }
+  MooringCall c = mooring_call(m, poses);
+  c.line_out = reinterpret_cast<float4*>(line_out);
+  c.substeps = s->substeps;
+  c.fsubsteps = (float)s->substeps;
+  c.h = s->dt / (float)s->substeps;
+  c.gx = s->gravity[0], c.gy = s->gravity[1], c.gz = s->gravity[2];
+  c.rho_g = s->rho_g;
+  c.bed_y = s->bed_y, c.bed_k = s->bed_k, c.bed_c = s->bed_c;
+  c.iterations = s->iterations;
+  c.tolerance = s->tolerance;
+  MooringWrench q{};
+  q.start = m->start;
+  q.order = m->order;
+  q.lines = m->consts;
+  q.fm = m->fm;
+  q.poses = poses;
+  q.out = reinterpret_cast<float4*>(wrench_ext);
+  q.bodies = m->bodies;
+  HIP_TRY(launch_moorings_step(p, w, s->water != 0, c, q, m->fft->stream, m->fft->cus), who);
   return OCEAN_OK;
 }
 

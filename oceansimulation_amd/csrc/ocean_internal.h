@@ -492,6 +492,60 @@ struct HullStep
 hipError_t launch_hulls_step(const SurfaceParams& p, const SurfaceRates& r, bool velocity, const HullCall& h,
                              HullStep st, int substeps, const HullFold* folds, int n_folds, hipStream_t stream,
                              int cus);
+// ocean_moorings (include/oceanfft.h, device/k_moorings.h). The work items are the hull sets': HullTile and
+// HullBody with "body" read as line and "point" as node (offset and first: the line's first node row, count:
+// its nodes), a line of more than 32 nodes on a wave of its own, smaller ones packed in segments.
+constexpr int kMooringMaxNodes = 64;  // nodes per line: the lanes of one wave
+// One line's constants, built on the host at ocean_moorings_create
+struct MooringLine
+{
+  float4 a;  // anchor, l0 = length / (float)(nodes - 1)
+  float4 f;  // fairlead in the body frame (body < 0: in the world), EA
+  float4 c;  // CA, and the lumps per node: mass_per_m * l0, volume_per_m * l0, drag_lin * l0
+  float dq;  // drag_quad * l0
+  int body;  // -1: both ends fixed in the world
+  int nodes;
+  int pad;
+};
+static_assert(sizeof(MooringLine) == 64, "four float4 rows");
+
+struct MooringCall
+{
+  const HullTile* tiles;
+  const HullBody* table;  // [lines]
+  const MooringLine* lines;
+  const float* poses;  // [bodies][20], frozen during the call; null when no line has a body
+  float4* nodes;       // [total nodes][2], stepped in place
+  float4* fm;          // [lines]: (Fm, the fairlead segment's T), what k_moorings_wrench reads
+  float4* line_out;    // [lines][2] or null
+  int items;
+  int substeps;
+  float fsubsteps;  // (float)substeps
+  float h;          // dt / substeps
+  float gx, gy, gz, rho_g;
+  float bed_y, bed_k, bed_c;
+  int iterations;
+  float tolerance;
+};
+
+// The per-body sum: the CSR of each body's lines (start [bodies + 1], order [lines with a body], ascending)
+struct MooringWrench
+{
+  const int* start;
+  const int* order;
+  const MooringLine* lines;
+  const float4* fm;
+  const float* poses;
+  float4* out;  // [bodies][2]
+  int bodies;
+};
+
+// One launch (ocean_moorings_reset)
+hipError_t launch_moorings_reset(const MooringCall& m, hipStream_t stream, int cus);
+// One launch for all substeps, then k_moorings_wrench when q.bodies > 0. water: p and w as
+// launch_water_kinematics takes them; else neither is read.
+hipError_t launch_moorings_step(const SurfaceParams& p, const WaterLayers& w, bool water, const MooringCall& m,
+                                const MooringWrench& q, hipStream_t stream, int cus);
 // Spray emitters (ocean_spray_emit, include/oceanfft.h, device/k_spray.h): the ordered compaction of the
 // emitting texels of the pairs' Jacobian maps into 8-float records. One emitting pair (rate != 0) of the
 // launch: its map and settings, and its index in the request (the id's top four bits).

@@ -428,6 +428,68 @@ Vision::ID HullSet::Step(const std::vector<Generator*>& generators, float* poses
   return loads;
 }
 
+MooringSet::MooringSet(Vision::RenderDevice* device, FFTCalculator* fft, const float* lines, const int32_t* attach,
+                       int nLines, int bodies)
+    : renderDevice(device), bodyCount(bodies)
+{
+  if (ocean_moorings_create(&moorings, fft ? fft->GetPlan() : nullptr, lines, attach, nLines, bodies) != OCEAN_OK)
+    throw std::runtime_error(std::string("MooringSet: ") + ocean_last_error());
+  if (bodies > 0)
+  {
+    Vision::Texture2DDesc desc;
+    desc.Width = 2 * (std::size_t)bodies;
+    desc.Height = 1;
+    desc.PixelType = Vision::PixelType::RGBA32Float;
+    wrench = renderDevice->CreateTexture2D(desc);
+  }
+}
+
+MooringSet::~MooringSet()
+{
+  ocean_moorings_destroy(moorings);
+  if (wrench)
+    renderDevice->DestroyTexture2D(wrench);
+  if (lineRows)
+    renderDevice->DestroyTexture2D(lineRows);
+}
+
+void MooringSet::Reset(const float* posesDevice)
+{
+  if (ocean_moorings_reset(moorings, posesDevice) != OCEAN_OK)
+    throw std::runtime_error(std::string("MooringSet::Reset: ") + ocean_last_error());
+}
+
+const float* MooringSet::GetWrenchDevice() const
+{
+  return wrench ? static_cast<const float*>(renderDevice->GetTexturePointer(wrench)) : nullptr;
+}
+
+Vision::ID MooringSet::Step(const std::vector<Generator*>& generators, const ocean_mooring_settings& settings,
+                            const float* posesDevice, bool lineOutput)
+{
+  if (lineOutput && !lineRows)
+  {
+    Vision::Texture2DDesc desc;
+    desc.Width = 2 * (std::size_t)GetLines();
+    desc.Height = 1;
+    desc.PixelType = Vision::PixelType::RGBA32Float;
+    lineRows = renderDevice->CreateTexture2D(desc);
+  }
+  std::vector<ocean_generator*> gens;
+  std::vector<int> cascades;
+  for (auto* g : generators)
+  {
+    gens.push_back(g->GetHandle());
+    cascades.push_back(0);
+  }
+  const int rc = ocean_moorings_step(moorings, gens.data(), cascades.data(), (int)gens.size(), &settings, posesDevice,
+                                     wrench ? static_cast<float*>(renderDevice->GetTexturePointer(wrench)) : nullptr,
+                                     lineOutput ? static_cast<float*>(renderDevice->GetTexturePointer(lineRows)) : nullptr);
+  if (rc != OCEAN_OK)
+    throw std::runtime_error(std::string("MooringSet::Step: ") + ocean_last_error());
+  return wrench;
+}
+
 SprayEmitter::SprayEmitter(Vision::RenderDevice* device, FFTCalculator* fft) : renderDevice(device)
 {
   if (ocean_spray_create(&spray, fft ? fft->GetPlan() : nullptr) != OCEAN_OK)

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import hip
 from .capi import (OCEAN_ERR_INVALID, OceanCamera, OceanCameraLayers, OceanError, OceanFoamDepositSettings, OceanMarch,
-                   OceanHullStepSettings, OceanShading, OceanSpraySettings, check, lib)
+                   OceanHullStepSettings, OceanMooringSettings, OceanShading, OceanSpraySettings, check, lib)
 from .hip import DeviceBuffer
 
 FLOATS_PER_VERTEX = 8  # x, y, z, jacobian, nx, ny, nz, 0 (query: base x, height, base z, ..., residual)
@@ -473,6 +473,105 @@ class HullSet:
     def close(self) -> None:
         if self._h:
             lib().ocean_hulls_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MooringSet:
+    """Mooring lines (ocean_moorings, include/oceanfft.h): chains of lumped nodes between anchors fixed in the
+    world and fairleads on the bodies of a hull set. lines: (L, 16) float32 (anchor, fairlead, length, EA, CA,
+    mass_per_m, volume_per_m, drag_lin, drag_quad, 0, 0, 0); attach: (L, 2) int32 (body or -1, nodes 2..64)."""
+
+    def __init__(self, fft, lines: np.ndarray, attach: np.ndarray, bodies: int):
+        self._lines = np.ascontiguousarray(lines, np.float32).reshape(-1, 16)
+        self._attach = np.ascontiguousarray(attach, np.int32).reshape(-1, 2)
+        self.fft = fft
+        self.bodies = int(bodies)
+        h = ctypes.c_void_p()
+        check(lib().ocean_moorings_create(ctypes.byref(h), fft.handle, self._lines.ctypes.data, self._attach.ctypes.data,
+                                          self._lines.shape[0], self.bodies), "ocean_moorings_create")
+        self._h = h
+        self.lines = int(lib().ocean_moorings_lines(h))
+        self.total_nodes = int(lib().ocean_moorings_total_nodes(h))
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def nodes_ptr(self) -> int:
+        """The device nodes (total_nodes, 8), for the caller to read and write on the plan's stream."""
+        return int(lib().ocean_moorings_nodes(self._h) or 0)
+
+    @staticmethod
+    def settings(**overrides) -> OceanMooringSettings:
+        """The library's defaults with `overrides` (dt, substeps, gravity, rho_g, iterations, tolerance, water,
+        bed_y, bed_k, bed_c)."""
+        s = OceanMooringSettings()
+        lib().ocean_default_mooring_settings(ctypes.byref(s))
+        for k, v in overrides.items():
+            if k == "gravity":
+                s.gravity[:] = [float(x) for x in v]
+            elif k in ("substeps", "iterations", "water"):
+                setattr(s, k, int(v))
+            else:
+                getattr(OceanMooringSettings, k)  # an unknown name is an AttributeError
+                setattr(s, k, float(v))
+        return s
+
+    def reset(self, poses_ptr: int = 0) -> None:
+        """Enqueue ocean_moorings_reset: every line straight from its anchor to its fairlead, at rest."""
+        check(lib().ocean_moorings_reset(self._h, ctypes.c_void_p(poses_ptr)), "ocean_moorings_reset")
+
+    def step(self, sampler: "SurfaceSampler" = None, poses_ptr: int = 0, wrench_ptr: int = 0, line_out_ptr: int = 0,
+             settings: OceanMooringSettings = None, **overrides) -> None:
+        """Enqueue one ocean_moorings_step on the plan's stream: the nodes are stepped in place under the frozen
+        device poses (bodies, 20); wrench_ptr (bodies, 8) receives ocean_hulls_step's wrench_ext, line_out_ptr
+        (lines, 8) the per-line rows. sampler: the water of settings.water == 1 (None for still water).
+        `overrides` are fields of the settings."""
+        if settings is None:
+            settings = self.settings(**overrides)
+        elif overrides:
+            raise TypeError("MooringSet.step: pass settings or their fields, not both")
+        gens, cas, count = (sampler._gens, sampler._cas, len(sampler.pairs)) if sampler is not None else (None, None, 0)
+        check(lib().ocean_moorings_step(self._h, gens, cas, count, ctypes.byref(settings), ctypes.c_void_p(poses_ptr),
+                                        ctypes.c_void_p(wrench_ptr), ctypes.c_void_p(line_out_ptr)),
+              "ocean_moorings_step")
+
+    def nodes_host(self) -> np.ndarray:
+        """The nodes (total_nodes, 8) after the stream's work."""
+        self.fft.synchronize()
+        return hip.to_host(self.nodes_ptr, (self.total_nodes, 8))
+
+    def set_nodes_host(self, nodes: np.ndarray) -> None:
+        """Write the nodes (total_nodes, 8) from the host, after the stream's work."""
+        nodes = np.ascontiguousarray(nodes, np.float32).reshape(self.total_nodes, 8)
+        self.fft.synchronize()
+        hip.from_host(self.nodes_ptr, nodes)
+
+    def step_host(self, sampler: "SurfaceSampler" = None, poses: np.ndarray = None, settings: OceanMooringSettings = None,
+                  calls: int = 1, **overrides):
+        """`calls` successive steps under host poses (bodies, 20): a list of (nodes, line_out, wrench_ext) after
+        each; line_out and wrench_ext start as NaN."""
+        p = DeviceBuffer.from_array(np.ascontiguousarray(poses, np.float32).reshape(self.bodies, 20)) if self.bodies else None
+        nan = np.float32(np.nan)
+        results = []
+        for _ in range(calls):
+            lines = DeviceBuffer.from_array(np.full((self.lines, 8), nan, np.float32))
+            wrench = DeviceBuffer.from_array(np.full((self.bodies, 8), nan, np.float32)) if self.bodies else None
+            self.step(sampler, p.ptr if p else 0, wrench.ptr if wrench else 0, lines.ptr, settings, **overrides)
+            results.append((self.nodes_host(), lines.to_host((self.lines, 8)),
+                            wrench.to_host((self.bodies, 8)) if wrench else np.zeros((0, 8), np.float32)))
+        return results
+
+    def close(self) -> None:
+        if self._h:
+            lib().ocean_moorings_destroy(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):
