@@ -25,7 +25,7 @@ DEVICE_H := $(wildcard $(CSRC)/device/*.h) $(CSRC)/ocean_internal.h $(CSRC)/laun
 # one translation unit per frame path, compiled in parallel
 KERNEL_TUS := ocean_kernels launch_half launch_slab launch_fft launch_mips launch_rates launch_hulls launch_bounds \
               launch_raycast launch_camera launch_surface launch_foam launch_kinematics launch_spray launch_particles \
-              launch_foam_deposit launch_moorings
+              launch_foam_deposit launch_moorings launch_wake
 KERNEL_OBJS := $(KERNEL_TUS:%=$(CSRC)/build/%.o)
 # hipcc gives every HIP translation unit an exported id symbol (__hip_cuid_<hash>; only relocatable device
 # code, which this build does not use, refers to it). The units split off from ocean_kernels and ocean_capi

@@ -1097,6 +1097,140 @@ int ocean_moorings_step(ocean_moorings* moorings, ocean_generator* const* gens, 
                         const ocean_mooring_settings* settings, const float* poses, float* wrench_ext,
                         float* line_out);
 
+/* ---- Wake windows: hull loads drive local surface waves on the device -------------------------------
+ * No reference counterpart (the reference has no bodies). Every section above freezes the water during a call:
+ * the water pushes the hulls and nothing pushes back. A wake window adds that state as a separate, linear
+ * layer on top of the ambient ocean: a square height field h in base-point space (the space of the maps and
+ * of the persistent foam), stepped with Tessendorf's local deep-water operator ("Interactive Water Surfaces"),
+ *     h_tt = -(g / dx) G * (h + P),
+ * G a 13 x 13 convolution whose symbol approximates |k|, and forced by the vertical loads that
+ * ocean_hulls_loads / ocean_hulls_step write to point_out: the hull's vertical load on the water is a surface
+ * pressure, which the dynamic boundary condition turns into a head P added to h under the operator. A body at
+ * rest makes the depression Archimedes asks for (h = -P is the fixed point), a moving body a Kelvin-type wake.
+ * The caller adds ocean_wake_sample's values to what ocean_surface_query returns (linear superposition);
+ * the ambient surface, the hull loads, the ray cast and the camera do not read a window.
+ *
+ * ocean_wake_create. size = M, a multiple of 16 in 32..4096; dx (m) finite and > 0; a finite origin;
+ * smoothing = sigma in 0.3..0.55, 0 standing for the default 0.5. Texel (i, j), i along x and fastest (index
+ * j * M + i), sits at the base point (ox + i * dx, oz + j * dx) with ox = origin_x + (float)off_i * dx and oz
+ * likewise; the integer offsets off_i, off_j are changed only by ocean_wake_shift, so repeated shifts do not
+ * drift. Storage: h and h_prev (4 B each) and one signed 64-bit accumulator A per texel, 16 B per texel,
+ * allocated and zeroed at create (OCEAN_ERR_OOM when that fails); no later call allocates. Every call runs on
+ * the stream of `fft` under its CU budget with no host synchronisation.
+ * The taps are built on the host in double, before any device call, and rounded once to float:
+ *     T[a][b] = (1 / 2 pi) int_0^inf q^2 exp(-sigma q^2) J0(q sqrt(a^2 + b^2)) dq,   0 <= a, b <= 6
+ *             = sqrt(pi) / (4 sigma^1.5) exp(-x / 2) ((1 - x) I0(x / 2) + x I1(x / 2)) / (2 pi),  x = r^2 / (4 sigma).
+ * The symbol of the truncated operator, the double cosine sum of the float taps, is evaluated on 257^2 points
+ * of [-pi, pi]^2 and a sigma whose minimum is not > 0 is refused: a negative symbol is a growing mode (0.3 ..
+ * 0.55 pass, minimum 1.3e-4 at 0.55; 0.6 fails). The operator is exact only for wavelengths well inside its
+ * 13-texel support: its symbol at k = 0 is about 0.14 instead of 0 (the dropped r^-3 tail), so waves longer
+ * than about 30 texels travel too fast (the table in DESIGN.md).
+ * OCEAN_ERR_INVALID, naming the field: a null out or fft, and each rule above.
+ *
+ * ocean_wake_step. records: device, rows of 8 floats in the layout of point_out: slot 0 = x and slot 2 = z of
+ * the base point, slot 5 = F.y, the water's vertical force on the point (N); a caller may fabricate rows (a
+ * pressure source, a dropped object). n = min(*count_device, max_records), read on the device; a null
+ * count_device gives n = max_records, a negative count 0. max_records in 0..2^28; null records with
+ * max_records == 0 is a free step.
+ * Contract, in unfused fp32, every expression in the order written. Host constants, with s = *settings:
+ *     hs = s.dt / (float)s.substeps      c = ((hs * hs) * s.gravity) / dx
+ *     hb = 0.5f * hs                     inv = 1.0f / ((s.rho_g * dx) * dx)
+ * Splat, per record r < n with (x, z, F):
+ *     m = F * inv;   u = (x - ox) / dx;   v = (z - oz) / dx
+ *     culled unless u >= -1 && u < (float)M && v >= -1 && v < (float)M        (a NaN culls)
+ *     i0 = floorf(u), fx = u - i0, and likewise j0, fz
+ *     taps (i0, j0), (i0+1, j0), (i0, j0+1), (i0+1, j0+1), weights (1-fx)*(1-fz), fx*(1-fz), (1-fx)*fz, fx*fz;
+ *     a tap whose index leaves 0..M-1 is dropped; for each kept tap t
+ *     p = m * w;   p' = (p == p) ? min(max(p, -1048576.0f), 1048576.0f) : 0
+ *     A[t] += (int64)(p' * 1048576.0f)             truncating toward zero; a no-return 64-bit integer atomic
+ * Integer adds commute, so the words do not depend on the order of the list. P[t] = (float)A[t] * 0x1p-20f is
+ * held fixed for the whole call.
+ * Substep, s.substeps times, for every texel t = (i, j), from h and h_prev at its start:
+ *     e[t] = h[t] + P[t], and 0 outside the window
+ *     d = (float)min(i, j, M-1-i, M-1-j)
+ *     r = s.border > 0 ? max((float)s.border - d, 0) / (float)s.border : 0
+ *     alpha = s.damp + s.edge_damp * (r * r);   b = hb * alpha
+ *     acc = +0.0f; then for a = 0..6 and b' = 0..a in that order acc = acc + T[a][b'] * S with
+ *       (0, 0):      S = e[i, j]
+ *       (a, 0):      S = (e[i+a, j] + e[i-a, j]) + (e[i, j+a] + e[i, j-a])
+ *       (a, a):      S = (e[i+a, j+a] + e[i-a, j-a]) + (e[i+a, j-a] + e[i-a, j+a])
+ *       0 < b' < a:  S = ((e[i+a, j+b'] + e[i-a, j-b']) + (e[i+a, j-b'] + e[i-a, j+b']))
+ *                      + ((e[i+b', j+a] + e[i-b', j-a]) + (e[i+b', j-a] + e[i-b', j+a]))
+ *     h_new[t] = (((2.0f * h[t]) - (1.0f - b) * h_prev[t]) - c * acc) / (1.0f + b)
+ *     then h_prev = h and h = h_new.
+ * The damping acts on the velocity, and the centred form has h = -P as its fixed point (Tessendorf's printed
+ * form pulls the height to zero and does not). After the call every A[t] is 0 again.
+ * Launches: at most substeps + 2: the splat (skipped when max_records == 0), one per substep (the 6-texel halo
+ * makes a substep a global dependency) and one that zeroes the accumulators the splat touched.
+ * Stability: with sum|T| over all 169 float taps in double, ocean_wake_max_substep returns
+ * 2 sqrt(dx / (gravity sum|T|)) (0.29 s at dx = 0.25, sigma = 0.5; 0 for a null wake or a gravity that is not
+ * > 0), and ocean_wake_step refuses hs at or above it. The bound is sufficient, not tight: the true limit is
+ * about sqrt(2) higher.
+ * OCEAN_ERR_INVALID, before any device call, naming the field: a null wake or settings; dt not finite or <= 0;
+ * substeps outside 1..64; gravity or rho_g not finite or <= 0; a negative or non-finite damp or edge_damp;
+ * border outside 0..size/2; max_records outside 0..2^28; null records with max_records > 0; hs at or above the
+ * bound. After OCEAN_ERR_HIP (a launch failed part way) the maps hold an unfinished step and the accumulators
+ * are zeroed again; reset the window before using it further.
+ *
+ *     dt, substeps   (s) the call advances dt in `substeps` substeps            defaults 1/60, 4
+ *     gravity        (m/s^2)                                                     9.8
+ *     rho_g          (N/m^3) the hulls'                                          9810
+ *     damp           (1/s) on the velocity, everywhere                           0.05
+ *     edge_damp      (1/s) added at the window's edge, falling to 0 over border  8
+ *     border         (texels) width of the absorbing frame                       16 */
+typedef struct ocean_wake_settings {
+  float dt;
+  int32_t substeps;
+  float gravity;
+  float rho_g;
+  float damp;
+  float edge_damp;
+  int32_t border;
+  int32_t reserved;  /* not read */
+} ocean_wake_settings;
+void ocean_default_wake_settings(ocean_wake_settings* out);
+typedef struct ocean_wake ocean_wake;
+int ocean_wake_create(ocean_wake** out, ocean_fft* fft, int size, float dx, float origin_x, float origin_z,
+                      float smoothing);
+/* Waits for the plan's stream, then frees the window. A null wake is accepted. */
+int ocean_wake_destroy(ocean_wake* wake);
+int ocean_wake_size(const ocean_wake* wake);   /* M; 0 for a null wake */
+/* The taps T[a][b], a, b in 0..6, row-major, as the device uses them. Needs no device. */
+int ocean_wake_kernel(const ocean_wake* wake, float out[49]);
+double ocean_wake_max_substep(const ocean_wake* wake, float gravity);
+int ocean_wake_origin(const ocean_wake* wake, float out[2]);   /* (ox, oz) of texel (0, 0) */
+/* Device, size x size floats, the current h; null for a null wake. A step of an odd number of substeps makes
+ * the other map current, so the pointer is valid until the next ocean_wake_step: ask again after it. The
+ * caller may write it in stream order (an initial condition, a restored state). */
+float* ocean_wake_height(ocean_wake* wake);
+/* h = h_prev = 0: one memset on the plan's stream; ocean_wake_sample's dh/dt is 0 until the next step. */
+int ocean_wake_reset(ocean_wake* wake);
+/* off_i += di and off_j += dj, and both maps move: h'[i, j] = h[i + di, j + dj] where that lies inside, else
+ * 0. |di|, |dj| <= 2^20; a shift of M or more in either direction clears the window, (0, 0) launches nothing.
+ * It follows a body by whole texels, so the contents never resample. Two launches through the accumulators'
+ * storage and a memset that leaves it zero. */
+int ocean_wake_shift(ocean_wake* wake, int di, int dj);
+int ocean_wake_step(ocean_wake* wake, const ocean_wake_settings* settings, const float* records,
+                    const int64_t* count_device, int64_t max_records);
+/* xz: device, n x 2 floats of base points (slots 0 and 2 of ocean_surface_query); out: device, n x 4 floats
+ * (h, dh/dx, dh/dz, dh/dt). In unfused fp32:
+ *     u = (x - ox) / dx;   v = (z - oz) / dx
+ *     inside iff u >= 0 && u <= (float)(M-1), and the same for v; outside, or NaN, gives four zeros
+ *     i0 = min((int)floorf(u), M-2), fx = u - (float)i0, and likewise j0, fz; hab = h[i0+a, j0+b]
+ *     x0 = h00 + fx * (h10 - h00);   x1 = h01 + fx * (h11 - h01);   h = x0 + fz * (x1 - x0)
+ *     gx = ((h10 - h00) + fz * ((h11 - h01) - (h10 - h00))) / dx
+ *     gz = ((h01 - h00) + fx * ((h11 - h10) - (h01 - h00))) / dx
+ *     dh/dt = the bilinear form of h over (h - h_prev) per tap, divided by the last call's hs; 0 before any
+ *             step and after a reset
+ * n in 0..2^31-1. One launch. OCEAN_ERR_INVALID for a null wake, n outside its range, null xz or out with n > 0. */
+int ocean_wake_sample(ocean_wake* wake, const float* xz, int64_t n, float* out);
+/* A window without a plan and without device storage, for checking the argument rules, the taps and the bound
+ * where there is no device: ocean_wake_create's rules and taps; ocean_wake_kernel, _max_substep, _origin, _size
+ * and _destroy work on it; every call that would launch is refused with OCEAN_ERR_INVALID after its other
+ * checks. */
+int ocean_debug_wake_create_host(ocean_wake** out, int size, float dx, float origin_x, float origin_z,
+                                 float smoothing);
+
 /* ---- Persistent foam: per-cascade accumulation, coverage counts, sampler ------------------------
  * The Jacobian map and slot 3 of the samplers say where the surface is folding now. Foam is a history:
  * whitecaps are born where the surface compresses, ride with the water and fade over seconds. The

@@ -6,13 +6,15 @@ include/oceanfft.h); this package is its ctypes binding plus a Python mirror of 
 classes used by the tests and bench.py.
 """
 from .capi import (OceanCamera, OceanCameraLayers, OceanError, OceanFoamDepositSettings, OceanFoamSettings, OceanMarch,  # noqa: F401
-                   OceanHullStepSettings, OceanParticleSettings, OceanSettings, OceanShading, OceanSpraySettings, lib)
+                   OceanHullStepSettings, OceanParticleSettings, OceanSettings, OceanShading, OceanSpraySettings,
+                   OceanWakeSettings, lib)
 from .waves import (FFTCalculator, Generator, default_settings, apply_settings,  # noqa: F401
                     default_foam_settings, apply_foam_settings, default_spray_settings, apply_spray_settings,
                     default_particle_settings, apply_particle_settings, default_foam_deposit_settings,
                     apply_foam_deposit_settings)
 from .surface import (SprayEmitter, SprayParticles, camera_pose, default_camera, default_march,  # noqa: F401
                       default_shading, default_camera_layers, camera_rays_host)
+from .wake import Wake, default_wake_settings, apply_wake_settings  # noqa: F401
 
 __all__ = ["FFTCalculator", "Generator", "OceanSettings", "OceanFoamSettings", "OceanSpraySettings",
            "OceanParticleSettings", "OceanFoamDepositSettings", "OceanHullStepSettings", "OceanError",
@@ -21,4 +23,4 @@ __all__ = ["FFTCalculator", "Generator", "OceanSettings", "OceanFoamSettings", "
            "default_foam_deposit_settings", "apply_foam_deposit_settings",
            "SprayEmitter", "SprayParticles", "OceanCamera", "OceanShading", "OceanMarch", "OceanCameraLayers",
            "camera_pose", "default_camera", "default_shading", "default_march", "default_camera_layers",
-           "camera_rays_host", "lib"]
+           "camera_rays_host", "Wake", "OceanWakeSettings", "default_wake_settings", "apply_wake_settings", "lib"]

@@ -141,6 +141,24 @@ class OceanMooringSettings(ctypes.Structure):
 assert ctypes.sizeof(OceanMooringSettings) == 48
 
 
+class OceanWakeSettings(ctypes.Structure):
+    """ocean_wake_settings: one ocean_wake_step call's parameters, 32 bytes."""
+
+    _fields_ = [
+        ("dt", ctypes.c_float),
+        ("substeps", ctypes.c_int32),
+        ("gravity", ctypes.c_float),
+        ("rho_g", ctypes.c_float),
+        ("damp", ctypes.c_float),
+        ("edge_damp", ctypes.c_float),
+        ("border", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+assert ctypes.sizeof(OceanWakeSettings) == 32
+
+
 class OceanCamera(ctypes.Structure):
     """ocean_camera: position, world-space basis (viewInverse columns 0, 1 and -column 2), lens, 64 bytes."""
 
@@ -314,6 +332,19 @@ SIGNATURES = {
     "ocean_moorings_reset": (_i, [_vp, _vp]),
     "ocean_default_mooring_settings": (None, [ctypes.POINTER(OceanMooringSettings)]),
     "ocean_moorings_step": (_i, [_vp, _vp, _vp, _i, ctypes.POINTER(OceanMooringSettings), _vp, _vp, _vp]),
+    "ocean_default_wake_settings": (None, [ctypes.POINTER(OceanWakeSettings)]),
+    "ocean_wake_create": (_i, [ctypes.POINTER(_vp), _vp, _i, _f, _f, _f, _f]),
+    "ocean_wake_destroy": (_i, [_vp]),
+    "ocean_wake_size": (_i, [_vp]),
+    "ocean_wake_kernel": (_i, [_vp, _fp]),
+    "ocean_wake_max_substep": (ctypes.c_double, [_vp, _f]),
+    "ocean_wake_origin": (_i, [_vp, _fp]),
+    "ocean_wake_height": (_vp, [_vp]),
+    "ocean_wake_reset": (_i, [_vp]),
+    "ocean_wake_shift": (_i, [_vp, _i, _i]),
+    "ocean_wake_step": (_i, [_vp, ctypes.POINTER(OceanWakeSettings), _vp, _vp, ctypes.c_int64]),
+    "ocean_wake_sample": (_i, [_vp, _vp, ctypes.c_int64, _vp]),
+    "ocean_debug_wake_create_host": (_i, [ctypes.POINTER(_vp), _i, _f, _f, _f, _f]),
     "ocean_default_spray_settings": (None, [ctypes.POINTER(OceanSpraySettings)]),
     "ocean_spray_create": (_i, [ctypes.POINTER(_vp), _vp]),
     "ocean_spray_destroy": (_i, [_vp]),

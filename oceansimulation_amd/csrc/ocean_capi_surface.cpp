@@ -1,8 +1,8 @@
 // ocean_capi_surface.cpp — the part of the C ABI (include/oceanfft.h) that consumes a generator's maps:
 // the map getters, ocean_surface_sample / _query / _sample_plane, the mip pyramids and the *_lod requests,
 // the rate maps and ocean_surface_velocity, the depth layers and ocean_water_kinematics, the bounds and ocean_surface_raycast, the persistent foam with
-// ocean_surface_sample_foam and ocean_foam_deposit, the camera images (ocean_camera_render, ocean_camera_render_layers), the hull sets, the spray emitters and the
-// spray particles.
+// ocean_surface_sample_foam and ocean_foam_deposit, the camera images (ocean_camera_render, ocean_camera_render_layers), the hull sets, the mooring
+// lines, the wake windows, the spray emitters and the spray particles.
 // The plans and generators themselves are in ocean_capi.cpp, their exchanges in ocean_capi_exchange.cpp;
 // ocean_capi_internal.h has what the three share.
 //
@@ -1760,6 +1760,332 @@ int ocean_moorings_step(ocean_moorings* m, ocean_generator* const* gens, const i
   q.out = reinterpret_cast<float4*>(wrench_ext);
   q.bodies = m->bodies;
   HIP_TRY(launch_moorings_step(p, w, s->water != 0, c, q, m->fft->stream, m->fft->cus), who);
+  return OCEAN_OK;
+}
+
+// ---- wake windows: hull loads drive local surface waves (device/k_wake.h) ----
+struct ocean_wake
+{
+  ocean_fft* fft = nullptr;  // null: a host-only window (ocean_debug_wake_create_host), no device storage
+  int m = 0;
+  float dx = 0, origin_x = 0, origin_z = 0, sigma = 0;
+  int64_t off_i = 0, off_j = 0;
+  float taps[49] = {};
+  double sum_abs = 0;  // of all 169 float taps
+  float hs = 0;        // the last call's substep; 0: no step since the creation or the last reset
+  void* storage = nullptr;  // acc | map | map
+  long long* acc = nullptr;
+  float* h = nullptr;
+  float* h_prev = nullptr;
+};
+
+namespace
+{
+
+// I0(z) and I1(z) by their power series: every term is positive, z <= 30 here (x / 2, x = 72 / (4 * 0.3))
+void bessel_i01(double z, double& i0, double& i1)
+{
+  const double q = 0.25 * z * z;
+  double t0 = 1.0, t1 = 1.0;
+  i0 = 1.0, i1 = 1.0;
+  for (int k = 1; k < 200; k++)
+  {
+    t0 *= q / ((double)k * k);
+    t1 *= q / ((double)k * (k + 1));
+    i0 += t0;
+    i1 += t1;
+  }
+  i1 *= 0.5 * z;
+}
+
+// T[a][b] = (1 / 2 pi) int_0^inf q^2 exp(-sigma q^2) J0(q r) dq, r^2 = a^2 + b^2, by its closed form
+//   sqrt(pi) / (4 sigma^1.5) exp(-x / 2) ((1 - x) I0(x / 2) + x I1(x / 2)) / (2 pi),   x = r^2 / (4 sigma),
+// in double, rounded once to float
+void wake_taps(double sigma, float out[49])
+{
+  const double pi = 3.14159265358979323846;
+  const double lead = std::sqrt(pi) / (4.0 * sigma * std::sqrt(sigma)) / (2.0 * pi);
+  for (int a = 0; a <= kWakeRadius; a++)
+    for (int b = 0; b <= kWakeRadius; b++)
+    {
+      const double x = (double)(a * a + b * b) / (4.0 * sigma);
+      double i0, i1;
+      bessel_i01(0.5 * x, i0, i1);
+      out[a * 7 + b] = (float)(lead * std::exp(-0.5 * x) * ((1.0 - x) * i0 + x * i1));
+    }
+}
+
+// The smallest value of the 13 x 13 operator's symbol, the double cosine sum of the float taps, on 257^2
+// points of [-pi, pi]^2. A value <= 0 is a mode that does not oscillate but grows.
+double wake_symbol_min(const float taps[49])
+{
+  const double pi = 3.14159265358979323846;
+  const int grid = 257;
+  std::vector<double> c((size_t)grid * 7);
+  for (int p = 0; p < grid; p++)
+    for (int a = 0; a < 7; a++)
+      c[(size_t)p * 7 + a] = (a ? 2.0 : 1.0) * std::cos((double)a * (-pi + 2.0 * pi * p / (grid - 1)));
+  double least = INFINITY;
+  for (int p = 0; p < grid; p++)
+  {
+    double row[7];  // sum over a of c[p][a] T[a][b]
+    for (int b = 0; b < 7; b++)
+    {
+      row[b] = 0.0;
+      for (int a = 0; a < 7; a++)
+        row[b] += c[(size_t)p * 7 + a] * (double)taps[a * 7 + b];
+    }
+    for (int q = 0; q < grid; q++)
+    {
+      double v = 0.0;
+      for (int b = 0; b < 7; b++)
+        v += row[b] * c[(size_t)q * 7 + b];
+      least = std::min(least, v);
+    }
+  }
+  return least;
+}
+
+// Everything of a window that needs no device: the argument rules, the taps, the symbol's sign
+int wake_host(ocean_wake** out, int size, float dx, float origin_x, float origin_z, float smoothing, const std::string& who)
+{
+  if (!out)
+    return fail(OCEAN_ERR_INVALID, who + ": null output");
+  *out = nullptr;
+  if (size < 32 || size > 4096 || size % 16 != 0)
+    return fail(OCEAN_ERR_INVALID, who + ": size must be a multiple of 16 in 32..4096");
+  if (!std::isfinite(dx) || !(dx > 0.0f))
+    return fail(OCEAN_ERR_INVALID, who + ": dx must be finite and > 0");
+  if (!std::isfinite(origin_x) || !std::isfinite(origin_z))
+    return fail(OCEAN_ERR_INVALID, who + ": the origin must be finite");
+  if (smoothing == 0.0f)
+    smoothing = 0.5f;
+  if (!(smoothing >= 0.3f) || !(smoothing <= 0.55f))
+    return fail(OCEAN_ERR_INVALID, who + ": smoothing outside 0.3..0.55 (0: the default 0.5)");
+  auto* w = new ocean_wake();
+  w->m = size;
+  w->dx = dx;
+  w->origin_x = origin_x;
+  w->origin_z = origin_z;
+  w->sigma = smoothing;
+  wake_taps((double)smoothing, w->taps);
+  if (!(wake_symbol_min(w->taps) > 0.0))
+  {
+    delete w;
+    return fail(OCEAN_ERR_INVALID, who + ": smoothing gives an operator whose symbol is not positive");
+  }
+  for (int a = -kWakeRadius; a <= kWakeRadius; a++)
+    for (int b = -kWakeRadius; b <= kWakeRadius; b++)
+      w->sum_abs += std::fabs((double)w->taps[std::abs(a) * 7 + std::abs(b)]);
+  *out = w;
+  return OCEAN_OK;
+}
+
+int wake_device(const ocean_wake* w, const std::string& who)
+{
+  if (!w->fft)
+    return fail(OCEAN_ERR_INVALID, who + ": the window has no device storage (ocean_debug_wake_create_host)");
+  return OCEAN_OK;
+}
+
+// What every launch of a window shares
+WakeCall wake_call(const ocean_wake* w)
+{
+#pragma clang fp contract(off)
+  WakeCall c{};
+  c.h = w->h;
+  c.h_prev = w->h_prev;
+  c.acc = w->acc;
+  c.m = w->m;
+  c.dx = w->dx;
+  c.ox = w->origin_x + (float)w->off_i * w->dx;
+  c.oz = w->origin_z + (float)w->off_j * w->dx;
+  c.hs = w->hs;
+  for (int a = 0; a <= kWakeRadius; a++)
+    for (int b = 0; b <= a; b++)
+      c.taps[a * (a + 1) / 2 + b] = w->taps[a * 7 + b];
+  return c;
+}
+
+}  // namespace
+
+int ocean_wake_destroy(ocean_wake* w)
+{
+  if (!w)
+    return OCEAN_OK;
+  if (w->fft)
+    (void)hipStreamSynchronize(w->fft->stream);
+  if (w->storage)
+    (void)hipFree(w->storage);
+  delete w;
+  return OCEAN_OK;
+}
+
+int ocean_debug_wake_create_host(ocean_wake** out, int size, float dx, float origin_x, float origin_z, float smoothing)
+{
+  return wake_host(out, size, dx, origin_x, origin_z, smoothing, "ocean_debug_wake_create_host");
+}
+
+int ocean_wake_create(ocean_wake** out, ocean_fft* fft, int size, float dx, float origin_x, float origin_z,
+                      float smoothing)
+{
+  const std::string who = "ocean_wake_create";
+  if (out)
+    *out = nullptr;
+  if (!out || !fft)
+    return fail(OCEAN_ERR_INVALID, who + ": null argument");
+  ocean_wake* w = nullptr;
+  TRY(wake_host(&w, size, dx, origin_x, origin_z, smoothing, who));
+  const size_t mm = (size_t)size * size;
+  hipError_t e = hipMalloc(&w->storage, mm * 16);
+  if (e == hipSuccess)
+    e = hipMemsetAsync(w->storage, 0, mm * 16, fft->stream);
+  if (e != hipSuccess)
+  {
+    if (w->storage)
+    {
+      (void)hipStreamSynchronize(fft->stream);
+      (void)hipFree(w->storage);
+    }
+    delete w;
+    return alloc_fail(e, who);
+  }
+  w->fft = fft;
+  w->acc = static_cast<long long*>(w->storage);
+  w->h = reinterpret_cast<float*>(w->acc + mm);
+  w->h_prev = w->h + mm;
+  *out = w;
+  return OCEAN_OK;
+}
+
+int ocean_wake_size(const ocean_wake* w) { return w ? w->m : 0; }
+
+int ocean_wake_kernel(const ocean_wake* w, float out[49])
+{
+  if (!w || !out)
+    return fail(OCEAN_ERR_INVALID, "ocean_wake_kernel: null argument");
+  std::memcpy(out, w->taps, sizeof(w->taps));
+  return OCEAN_OK;
+}
+
+double ocean_wake_max_substep(const ocean_wake* w, float gravity)
+{
+  if (!w || !(gravity > 0.0f))
+    return 0.0;
+  return 2.0 * std::sqrt((double)w->dx / ((double)gravity * w->sum_abs));
+}
+
+int ocean_wake_origin(const ocean_wake* w, float out[2])
+{
+  if (!w || !out)
+    return fail(OCEAN_ERR_INVALID, "ocean_wake_origin: null argument");
+  const WakeCall c = wake_call(w);
+  out[0] = c.ox;
+  out[1] = c.oz;
+  return OCEAN_OK;
+}
+
+float* ocean_wake_height(ocean_wake* w) { return w ? w->h : nullptr; }
+
+int ocean_wake_reset(ocean_wake* w)
+{
+  const char* who = "ocean_wake_reset";
+  if (!w)
+    return fail(OCEAN_ERR_INVALID, "ocean_wake_reset: null wake");
+  TRY(wake_device(w, who));
+  float* first = w->h < w->h_prev ? w->h : w->h_prev;  // the two maps are neighbours
+  HIP_TRY(hipMemsetAsync(first, 0, (size_t)w->m * w->m * 2 * sizeof(float), w->fft->stream), who);
+  w->hs = 0.0f;
+  return OCEAN_OK;
+}
+
+int ocean_wake_shift(ocean_wake* w, int di, int dj)
+{
+  const char* who = "ocean_wake_shift";
+  if (!w)
+    return fail(OCEAN_ERR_INVALID, "ocean_wake_shift: null wake");
+  if (di < -1048576 || di > 1048576 || dj < -1048576 || dj > 1048576)
+    return fail(OCEAN_ERR_INVALID, "ocean_wake_shift: di or dj outside -1048576..1048576");
+  TRY(wake_device(w, who));
+  if (di != 0 || dj != 0)
+    HIP_TRY(launch_wake_shift(wake_call(w), di, dj, w->fft->stream, w->fft->cus), who);
+  w->off_i += di;
+  w->off_j += dj;
+  return OCEAN_OK;
+}
+
+void ocean_default_wake_settings(ocean_wake_settings* s)
+{
+  if (s)
+    *s = ocean_wake_settings{1.0f / 60.0f, 4, 9.8f, 9810.0f, 0.05f, 8.0f, 16};
+}
+
+int ocean_wake_step(ocean_wake* w, const ocean_wake_settings* s, const float* records, const int64_t* count_device,
+                    int64_t max_records)
+{
+#pragma clang fp contract(off)
+  const char* who = "ocean_wake_step";
+  if (!w)
+    return fail(OCEAN_ERR_INVALID, "ocean_wake_step: null wake");
+  if (!s)
+    return fail(OCEAN_ERR_INVALID, "ocean_wake_step: null settings");
+  if (!(s->dt > 0.0f) || !std::isfinite(s->dt))
+    return fail(OCEAN_ERR_INVALID, "ocean_wake_step: dt must be finite and > 0");
+  if (s->substeps < 1 || s->substeps > 64)
+    return fail(OCEAN_ERR_INVALID, "ocean_wake_step: substeps outside 1..64");
+  if (!(s->gravity > 0.0f) || !std::isfinite(s->gravity))
+    return fail(OCEAN_ERR_INVALID, "ocean_wake_step: gravity must be finite and > 0");
+  if (!(s->rho_g > 0.0f) || !std::isfinite(s->rho_g))
+    return fail(OCEAN_ERR_INVALID, "ocean_wake_step: rho_g must be finite and > 0");
+  if (!(s->damp >= 0.0f) || !std::isfinite(s->damp))
+    return fail(OCEAN_ERR_INVALID, "ocean_wake_step: damp must be finite and >= 0");
+  if (!(s->edge_damp >= 0.0f) || !std::isfinite(s->edge_damp))
+    return fail(OCEAN_ERR_INVALID, "ocean_wake_step: edge_damp must be finite and >= 0");
+  if (s->border < 0 || s->border > w->m / 2)
+    return fail(OCEAN_ERR_INVALID, "ocean_wake_step: border outside 0..size/2");
+  if (max_records < 0 || max_records > ((int64_t)1 << 28))
+    return fail(OCEAN_ERR_INVALID, "ocean_wake_step: max_records outside 0..2^28");
+  if (!records && max_records > 0)
+    return fail(OCEAN_ERR_INVALID, "ocean_wake_step: null records with max_records > 0");
+  const float hs = s->dt / (float)s->substeps;
+  if (!((double)hs < ocean_wake_max_substep(w, s->gravity)))
+    return fail(OCEAN_ERR_INVALID, "ocean_wake_step: dt / substeps is at or above ocean_wake_max_substep");
+  TRY(wake_device(w, who));
+  WakeCall c = wake_call(w);
+  c.border = s->border;
+  c.c = ((hs * hs) * s->gravity) / w->dx;
+  c.hb = 0.5f * hs;
+  c.inv = 1.0f / ((s->rho_g * w->dx) * w->dx);
+  c.damp = s->damp;
+  c.edge_damp = s->edge_damp;
+  c.records = records;
+  c.count_device = count_device;
+  c.max_records = max_records;
+  const hipError_t e = launch_wake_step(c, s->substeps, w->fft->stream, w->fft->cus);
+  w->h = c.h;  // as far as the substeps were issued
+  w->h_prev = c.h_prev;
+  if (e != hipSuccess)
+  {
+    // a launch failed part way: the maps hold an unfinished step, and the accumulators are zeroed here so that
+    // "all zero between calls" holds for the next call, whatever the splat had added
+    (void)hipMemsetAsync(w->acc, 0, (size_t)w->m * w->m * sizeof(long long), w->fft->stream);
+    return hip_fail(e, who);
+  }
+  w->hs = hs;
+  return OCEAN_OK;
+}
+
+int ocean_wake_sample(ocean_wake* w, const float* xz, int64_t n, float* out)
+{
+  const char* who = "ocean_wake_sample";
+  if (!w)
+    return fail(OCEAN_ERR_INVALID, "ocean_wake_sample: null wake");
+  if (n < 0 || n > 2147483647LL)
+    return fail(OCEAN_ERR_INVALID, "ocean_wake_sample: n outside 0..2^31-1");
+  if (n > 0 && (!xz || !out))
+    return fail(OCEAN_ERR_INVALID, "ocean_wake_sample: null xz or out with n > 0");
+  TRY(wake_device(w, who));
+  HIP_TRY(launch_wake_sample(wake_call(w), xz, n, out, w->fft->stream, w->fft->cus), who);
   return OCEAN_OK;
 }
 

@@ -648,6 +648,35 @@ void foam_deposit_scratch(void* scratch, FoamDepositCall& c);
 // Three launches: accumulate, apply, fold the counts. merge: runs of neighbouring lanes on one texel are
 // folded within the wave before the atomics (the same words either way).
 hipError_t launch_foam_deposit(FoamDepositCall c, bool merge, hipStream_t stream, int cus);
+// Wake windows (ocean_wake, include/oceanfft.h, device/k_wake.h): a square height field forced by the hulls'
+// vertical loads and stepped with the 13 x 13 deep-water operator. What every launch of a window shares.
+constexpr int kWakeRadius = 6;        // the operator's halo
+constexpr int kWakeTile = 32;         // a substep item is a kWakeTile x kWakeTile tile of outputs
+constexpr int kWakeThreads = 256;     // of every wake kernel; a splat item is kWakeThreads records
+constexpr int kWakeSplatMaxGrid = 4096;
+struct WakeCall
+{
+  float* h;        // [m][m], index j * m + i
+  float* h_prev;   // the substep writes the new h over it; the host swaps the two afterwards
+  long long* acc;  // [m][m] units of 2^-20, all zero between calls
+  int m;
+  int border;
+  float dx, ox, oz;    // ox = origin_x + (float)off_i * dx
+  float c, hb, inv;    // the host constants of ocean_wake_step
+  float damp, edge_damp;
+  float hs;            // sample: the last call's substep, 0 before any step and after a reset
+  const float* records;         // [max_records][8]: slots 0, 2 and 5 are read
+  const int64_t* count_device;  // or null: max_records
+  int64_t max_records;
+  float taps[28];  // T[a][b], b <= a, at a (a + 1) / 2 + b
+};
+// The splat (skipped when c.max_records == 0), `substeps` substep launches that swap c.h and c.h_prev, and
+// the launch that zeroes the accumulators the splat touched: substeps + 2 launches at most
+hipError_t launch_wake_step(WakeCall& c, int substeps, hipStream_t stream, int cus);
+// Two launches through the accumulators' storage and a memset that zeroes it again
+hipError_t launch_wake_shift(const WakeCall& c, int di, int dj, hipStream_t stream, int cus);
+// One launch: xz [n][2] -> out [n][4]
+hipError_t launch_wake_sample(const WakeCall& c, const float* xz, int64_t n, float* out, hipStream_t stream, int cus);
 void launch_surface_atlas(const SurfaceParams& p, hipStream_t stream, int cus);
 size_t surface_atlas_texels(const SurfaceParams& p);
 bool surface_use_atlas(const SurfaceParams& p, int64_t points);
